@@ -5,6 +5,12 @@ SincNet/conv/biGRU encoder in train mode + intent GRU trained; forward, loss, ba
 all-reduce, Adam) — through models.Model / training.Trainer on the HIP kernels.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload no_unfreezing|unfreeze_all|asr_pretrain]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, `dtype`, ...).  `--full`
+adds every other measurement described below (parity on the golden batch, steady state, roofline / PMC, scaling model,
+large-batch point, host inputs, feature parity, front end, CPU baseline, side runs of the other arithmetics and workloads).
+`--dump-outputs DIR` writes what the timed loop computed, right after its last step, as DIR/<name>.npy (see dump_outputs).
 
 `--gpus N` with N > 1 launches the N ranks itself (one process per GPU, RCCL over xGMI) unless the
 process was already started by torch.distributed.run (WORLD_SIZE set), which works as well:
@@ -108,19 +114,57 @@ def setup(workload, rank, batch, samples, n_batches, hidden=0):
     return config, model, trainer, train_ds, work
 
 
-def run_steps(model, trainer, batches, n, asr=False, first_done=None):
+def run_steps(model, trainer, batches, n, asr=False, first_done=None, last=None):
     """n optimisation steps through Trainer's own step loop (forward, loss, backward, gradient
     all-reduce, Adam; with the frozen-encoder look-ahead pipeline when it applies).
-    first_done: optional timing event recorded when the first step has been enqueued completely."""
+    first_done: optional timing event recorded when the first step has been enqueued completely.
+    last: optional list that receives the metrics the loop yielded for its last step (no copy is made)."""
     import contextlib
     loader = [batches[i % len(batches)] for i in range(n)]
     # accumulate=True: the epoch statistics are kept on the device by the loop itself (trainer.epoch_sums), as
     # Trainer.train() runs it — no accumulation launch per step here
     with contextlib.closing(trainer._iterate(loader, True, asr, accumulate=True)) as steps:
-        for i, _ in enumerate(steps):
+        for i, (vals, _) in enumerate(steps):
             if i == 0 and first_done is not None:
                 first_done.record()
+            if last is not None:
+                last[:] = [vals]
     return trainer.epoch_sums.clone()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, model, sums, last_vals):
+    """--dump-outputs: what the timed loop hands its caller after its last step, as float32 / float64 DIR/<name>.npy —
+    `last_step_metrics` (the metrics the loop yielded for that step: loss, accuracy, ...), `epoch_sums` (float64: the
+    batch-weighted sums of the metrics over the K timed steps) and `param.<name>` for every trainable parameter as the
+    last step's Adam update left it.  Should they exceed 64 MB in all, every array is replaced by a fixed seeded sample of
+    its flattened elements (indices in increasing order), the same in every run."""
+    import numpy as np
+
+    def host(t):
+        a = t.detach().cpu()
+        return (a if a.dtype == torch.float64 else a.float()).numpy()
+    if torch.is_tensor(last_vals):
+        metrics = host(last_vals).reshape(-1)
+    else:
+        metrics = np.array([host(v).reshape(()) for v in last_vals], dtype=np.float32)
+    arrays = {"last_step_metrics": metrics, "epoch_sums": host(sums)}
+    for name, p in model.named_parameters():
+        if p.requires_grad:
+            arrays["param." + name] = host(p)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        frac = 0.99 * DUMP_LIMIT_BYTES / float(total)              # (room for the .npy headers)
+        for name, a in arrays.items():
+            k = max(1, int(a.size * frac))
+            if k < a.size:
+                idx = np.sort(np.random.default_rng(1234).choice(a.size, k, replace=False))
+                arrays[name] = a.reshape(-1)[idx]
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -616,7 +660,7 @@ def side_run(extra_args, env_extra=None, timeout=600):
     env = dict(os.environ)
     env.update(env_extra or {})
     env.pop("SLU_BENCH_VERBOSE", None)
-    cmd = [sys.executable, os.path.abspath(__file__), "--sub", "--no-cpu-baseline", "--no-large-batch", "--no-kernel-table"] + extra_args
+    cmd = [sys.executable, os.path.abspath(__file__), "--sub", "--full", "--no-cpu-baseline", "--no-large-batch", "--no-kernel-table"] + extra_args
     try:
         out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
         d = json.loads(out.stdout.strip().splitlines()[-1])
@@ -1060,6 +1104,11 @@ def main():
     ap.add_argument("--hidden", type=int, default=0,
                     help="GRU hidden size of every layer (default: the cfg's 128); any other value is a labelled "
                          "synthetic variant (SURVEY 8.0-A: H = 512 extra point), never the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="every measurement beside the headline (parity, steady state, roofline, scaling model, large batch, "
+                         "host inputs, front end, CPU baseline, side runs); the --no-* options below trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed loop computed in its last step to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-large-batch", action="store_true",
                     help="skip the extra large-batch point (B=2048/GPU, forward-dominant kernels throughput-bound)")
@@ -1098,7 +1147,7 @@ def main():
     if args.sub:
         args.no_side_runs = True
     parity = None
-    if rank == 0:
+    if rank == 0 and args.full:
         note("parity on the golden batch")
         parity = parity_check(dev)
     note("setup")
@@ -1126,9 +1175,10 @@ def main():
     fence()
     note("timed region")
     ev0, ev_first = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    last = []
     t0 = time.perf_counter()
     ev0.record()
-    sums = run_steps(model, trainer, batches, args.steps, asr, first_done=ev_first)
+    sums = run_steps(model, trainer, batches, args.steps, asr, first_done=ev_first, last=last)
     fence()
     elapsed = time.perf_counter() - t0
     fill_ms = ev0.elapsed_time(ev_first)
@@ -1140,9 +1190,13 @@ def main():
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
     elapsed = tmax.item()
     loss_mean = (sums[0] / (args.steps * args.batch)).item()
+    if args.dump_outputs and rank == 0:
+        # before anything else runs a step: the measurements of --full train the same model further
+        note("outputs -> %s" % args.dump_outputs)
+        dump_outputs(args.dump_outputs, model, sums, last[0])
     graphs = trainer.graph_stats()
     dp_costs = None
-    if trainer.data_parallel:
+    if trainer.data_parallel and args.full:
         note("data parallel: the collective alone, the loop without it")
         try:
             dp_costs = dp_point(model, trainer, batches, args.steps, asr, fence)
@@ -1157,7 +1211,7 @@ def main():
     # steady state of the same loop (long run), reported beside `value` when K is short: the first
     # super-batch of a run has to be computed before its first step can start (pipeline fill)
     steady = None
-    if args.steps < 256 and world == 1 and os.environ.get("SLU_BENCH_NO_STEADY", "0") != "1":      # (the env: timeline traces of the K-step region)
+    if args.full and args.steps < 256 and world == 1 and os.environ.get("SLU_BENCH_NO_STEADY", "0") != "1":      # (the env: timeline traces of the K-step region)
         n_long = 512
         run_steps(model, trainer, batches, n_long, asr)
         run_steps(model, trainer, batches, n_long, asr)
@@ -1204,7 +1258,7 @@ def main():
             out["rccl"]["collective"] = graphs.get("collective")
             if "SLU_LOCAL_DEVICE" in os.environ:
                 out["config"]["parallelism"] += " (ranks share the visible GPU(s): functional check only)"
-        if world == 1 and not args.no_kernel_table:
+        if args.full and world == 1 and not args.no_kernel_table:
             note("kernel table")
             table = kernel_table(model, trainer, args.batch, samples, width, asr)
             top = table[0]
@@ -1270,7 +1324,7 @@ def main():
                             r_["bound_measured"] = r_["bound"]
         # The side measurements run on rank 0 at N = 1 only: under data parallelism a Trainer built by
         # one rank alone would issue gradient all-reduces the other ranks never join.
-        if world == 1 and args.workload == "no_unfreezing" and depth and not args.sub and not args.no_kernel_table:
+        if args.full and world == 1 and args.workload == "no_unfreezing" and depth and not args.sub and not args.no_kernel_table:
             note("scaling model (suffix / prefix alone, one-rank collective)")
             try:
                 ss = steady["ms_per_step"] if steady else 1e3 * elapsed / args.steps
@@ -1278,10 +1332,10 @@ def main():
                 out["config"]["predicted_weak_scaling_efficiency_8_gpus"] = out["scaling_model"].get("predicted_weak_scaling_efficiency_8_gpus")
             except Exception as e:                           # noqa: BLE001 - a side measurement never takes the headline down
                 out["scaling_model"] = {"error": str(e)[:200]}
-        if world == 1 and not args.no_large_batch and args.workload == "no_unfreezing" and not args.hidden:
+        if args.full and world == 1 and not args.no_large_batch and args.workload == "no_unfreezing" and not args.hidden:
             note("large-batch point")
             out["large_batch_point"] = large_batch_point(rank, samples)
-        default_line = (world == 1 and args.workload == "no_unfreezing" and not args.hidden and args.dtype == "f32"
+        default_line = (args.full and world == 1 and args.workload == "no_unfreezing" and not args.hidden and args.dtype == "f32"
                         and not args.no_side_runs)
         if default_line:
             note("host-input point")
@@ -1296,7 +1350,7 @@ def main():
                 out.setdefault("other_workloads", {})["frontend_fwd"] = frontend_fwd_point(model, config, args.batch, samples)
             except Exception as e:
                 out.setdefault("other_workloads", {})["frontend_fwd"] = {"error": str(e)[:200]}
-        if world == 1 and not args.no_cpu_baseline and not asr:
+        if args.full and world == 1 and not args.no_cpu_baseline and not asr:
             note("cpu baseline")
             out["cpu_baseline"] = (cpu_baseline_seq2seq(config, args.batch, samples) if args.workload == "seq2seq"
                                    else cpu_baseline(config, args.batch, samples))

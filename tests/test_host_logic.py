@@ -190,6 +190,41 @@ def test_bench_stdout_carries_the_json_line_only(tmp_path):
     assert "noise from a library" in r.stderr and "noise from a child process" in r.stderr
 
 
+def test_bench_dump_outputs_writes_float_arrays_under_the_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the last step's metrics, the epoch sums and the TRAINABLE parameters as float32 / float64
+    .npy files; beyond the size cap every array is cut to the same seeded sample in every run."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(64, 32), torch.nn.Linear(32, 8))
+    model[0].weight.requires_grad = False
+    model[1].bias.data = model[1].bias.data.double()
+    sums = torch.tensor([3.0, 1.5, 0.0, 0.0], dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "a"), model, sums, torch.tensor([0.25, 0.5]))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["epoch_sums.npy", "last_step_metrics.npy", "param.0.bias.npy", "param.1.bias.npy", "param.1.weight.npy"]
+    got = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    assert got["epoch_sums"].dtype == np.float64 and got["epoch_sums"].tolist() == [3.0, 1.5, 0.0, 0.0]
+    assert got["last_step_metrics"].dtype == np.float32 and got["last_step_metrics"].tolist() == [0.25, 0.5]
+    assert got["param.1.bias"].dtype == np.float64
+    assert np.array_equal(got["param.1.weight"], model[1].weight.detach().numpy())
+    # a list of scalar metrics (the eager loop's form) is one float32 vector as well
+    bench.dump_outputs(str(tmp_path / "b"), model, sums, [torch.tensor(1.0), torch.tensor(2.0)])
+    assert np.load(tmp_path / "b" / "last_step_metrics.npy").tolist() == [1.0, 2.0]
+    # over the cap: a fixed sample, identical from run to run, within the cap
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 512)
+    for d in ("c", "d"):
+        bench.dump_outputs(str(tmp_path / d), model, sums, torch.tensor([0.25, 0.5]))
+    total = sum(os.path.getsize(tmp_path / "c" / n) - 128 for n in os.listdir(tmp_path / "c"))   # less the .npy headers
+    assert total <= 512
+    for n in os.listdir(tmp_path / "c"):
+        a, b = np.load(tmp_path / "c" / n), np.load(tmp_path / "d" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+    w = model[1].weight.detach().numpy().reshape(-1)
+    assert np.isin(np.load(tmp_path / "c" / "param.1.weight.npy"), w).all()
+
+
 def test_ramp_plan_of_the_first_super_batches(monkeypatch):
     """training._ramp_plan: by default ONE capped first super-batch of ceil(5 + 0.4 n) batches for a run that fits in two
     super-batches (the prefix latency in units of step + per-batch prefix cost, plus the share of the run whose steps hide

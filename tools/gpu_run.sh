@@ -10,10 +10,10 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   echo "pytest rc=$?" >> $OUT/pytest.log
   tail -5 $OUT/pytest.log
 fi
-timeout 300 python bench.py --steps 20 --warmup 5 > $OUT/bench_20.json 2> $OUT/bench_20.err; echo "bench20 rc=$?"
-timeout 300 python bench.py --no-cpu-baseline --no-large-batch > $OUT/bench_512.json 2> $OUT/bench_512.err; echo "bench512 rc=$?"
-timeout 300 python bench.py --workload unfreeze_all --no-cpu-baseline --steps 100 --warmup 10 > $OUT/bench_unfrozen.json 2> $OUT/bench_unfrozen.err; echo "unfrozen rc=$?"
-timeout 300 python bench.py --workload asr_pretrain --steps 100 --warmup 10 > $OUT/bench_asr.json 2> $OUT/bench_asr.err; echo "asr rc=$?"
+timeout 300 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_20.json 2> $OUT/bench_20.err; echo "bench20 rc=$?"
+timeout 300 python bench.py --full --no-cpu-baseline --no-large-batch > $OUT/bench_512.json 2> $OUT/bench_512.err; echo "bench512 rc=$?"
+timeout 300 python bench.py --full --workload unfreeze_all --no-cpu-baseline --steps 100 --warmup 10 > $OUT/bench_unfrozen.json 2> $OUT/bench_unfrozen.err; echo "unfrozen rc=$?"
+timeout 300 python bench.py --full --workload asr_pretrain --steps 100 --warmup 10 > $OUT/bench_asr.json 2> $OUT/bench_asr.err; echo "asr rc=$?"
 for f in bench_20 bench_512 bench_unfrozen bench_asr; do echo "== $f"; tail -c 1500 $OUT/$f.err | tail -5; python - <<PY
 import json
 try:

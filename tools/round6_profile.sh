@@ -6,7 +6,7 @@ TAG=${1:-r06_z}
 R=$PWD
 O=$R/gpurun_out/$TAG; mkdir -p $O
 export SLU_BENCH_VERBOSE=1
-B="--no-kernel-table --no-cpu-baseline --no-large-batch --no-side-runs"
+B="--full --no-kernel-table --no-cpu-baseline --no-large-batch --no-side-runs"
 cd /tmp && export TMPDIR=/tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_default -o d -- python $R/bench.py $B > $O/bench_default_under_rocprofv3.json 2> $O/bench_default_prof.err
 cd $R
@@ -79,7 +79,7 @@ for w in unfreeze_all asr_pretrain; do
 done
 # BASELINE configs[4]: unfreeze_all, 10 s utterances, 32 per GPU, bf16 and fp32 (+ the traced bf16 step)
 for d in bf16 f32; do
-  timeout 400 python bench.py --dtype $d --workload unfreeze_all --seconds 10 --batch 32 --steps 40 --warmup 10 --no-cpu-baseline --no-kernel-table > $O/bench_cfg4_$d.json 2> $O/bench_cfg4_$d.err; echo "cfg4 $d rc=$?"
+  timeout 400 python bench.py --full --dtype $d --workload unfreeze_all --seconds 10 --batch 32 --steps 40 --warmup 10 --no-cpu-baseline --no-kernel-table > $O/bench_cfg4_$d.json 2> $O/bench_cfg4_$d.err; echo "cfg4 $d rc=$?"
 done
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_cfg4 -o u -- python $R/bench.py $B --dtype bf16 --workload unfreeze_all --seconds 10 --batch 32 --steps 40 --warmup 10 > $O/bench_cfg4_bf16_under_rocprofv3.json 2> $O/bench_cfg4_prof.err
@@ -87,10 +87,10 @@ cd $R
 f=$(find $O/trace_cfg4 -name "*kernel_trace.csv" | head -1)
 python tools/rocprof_summary.py $f 40 --by-shape > $O/cfg4_bf16_kernel_stats_by_shape.txt
 rm -rf $O/trace_cfg4
-timeout 1200 python bench.py --steps 20 --warmup 5 > $O/bench_20.json 2> $O/bench_20.err; echo "bench20 rc=$?"
-timeout 400 python bench.py --no-cpu-baseline --no-large-batch --no-side-runs > $O/bench_512.json 2> $O/bench_512.err; echo "bench512 rc=$?"
-timeout 400 python bench.py --gpus 2 --share-gpu --steps 20 --warmup 5 --no-cpu-baseline --no-large-batch --no-side-runs --no-kernel-table > $O/bench_2ranks_one_gpu.json 2> $O/bench_2ranks_one_gpu.err; echo "bench 2 ranks rc=$?"
-timeout 400 python bench.py --gpus 4 --share-gpu --steps 20 --warmup 5 --no-cpu-baseline --no-large-batch --no-side-runs --no-kernel-table > $O/bench_4ranks_one_gpu.json 2> $O/bench_4ranks_one_gpu.err; echo "bench 4 ranks rc=$?"
+timeout 1200 python bench.py --full --steps 20 --warmup 5 > $O/bench_20.json 2> $O/bench_20.err; echo "bench20 rc=$?"
+timeout 400 python bench.py --full --no-cpu-baseline --no-large-batch --no-side-runs > $O/bench_512.json 2> $O/bench_512.err; echo "bench512 rc=$?"
+timeout 400 python bench.py --full --gpus 2 --share-gpu --steps 20 --warmup 5 --no-cpu-baseline --no-large-batch --no-side-runs --no-kernel-table > $O/bench_2ranks_one_gpu.json 2> $O/bench_2ranks_one_gpu.err; echo "bench 2 ranks rc=$?"
+timeout 400 python bench.py --full --gpus 4 --share-gpu --steps 20 --warmup 5 --no-cpu-baseline --no-large-batch --no-side-runs --no-kernel-table > $O/bench_4ranks_one_gpu.json 2> $O/bench_4ranks_one_gpu.err; echo "bench 4 ranks rc=$?"
 head -24 $O/default_kernel_stats.txt | cut -c1-170
 python - <<PY
 import json
