@@ -963,14 +963,39 @@ extern "C" int slu_gemm_f32(const float* A, int64_t a_rs, int64_t a_cs, const fl
   return SLU_OK;
 }
 
+// The launch arguments of slu_gemm_tn_batched and slu_gemm_tn_batched_splitk: the checks every problem and the row-sum
+// job share, the problems with tile_m x tile_n output tiles numbered problem after problem (tile_end: running count), the
+// row-sum job and its workgroups (rs_blocks).
+static int tn_fill_args(const char* fn, TnArgs& a, const float* const* A, const int64_t* lda, const float* const* B,
+                        const int64_t* ldb, float* const* C, const int64_t* ldc, const int64_t* M, const int64_t* N,
+                        const int64_t* K, int64_t count, int tile_m, int tile_n, const float* rowsum_src,
+                        int64_t rowsum_rows, int64_t rowsum_cols, float* rowsum_dst) {
+  SLU_REQUIRE((rowsum_src == nullptr) == (rowsum_dst == nullptr), "%s: rowsum_src and rowsum_dst go together", fn);
+  SLU_REQUIRE(!rowsum_src || (rowsum_rows >= 1 && rowsum_cols >= 1 && rowsum_rows < (1LL << 30) && rowsum_cols < (1LL << 30)),
+              "%s: bad row-sum size", fn);
+  int tiles = 0;
+  for (int q = 0; q < (int)count; ++q) {
+    SLU_REQUIRE(A[q] && B[q] && C[q] && M[q] > 0 && N[q] > 0 && K[q] > 0, "%s: bad problem %d", fn, q);
+    SLU_REQUIRE(M[q] < (1LL << 30) && N[q] < (1LL << 30) && K[q] < (1LL << 30), "%s: size overflow", fn);
+    a.p[q].A = A[q]; a.p[q].B = B[q]; a.p[q].C = C[q];
+    a.p[q].lda = lda[q]; a.p[q].ldb = ldb[q]; a.p[q].ldc = ldc[q];
+    a.p[q].M = (int)M[q]; a.p[q].N = (int)N[q]; a.p[q].K = (int)K[q];
+    a.p[q].tiles_n = (int)cdiv(N[q], tile_n);
+    tiles += (int)(cdiv(M[q], tile_m) * cdiv(N[q], tile_n));
+    a.p[q].tile_end = tiles;
+  }
+  a.count = (int)count;
+  a.tiles = tiles;
+  a.rs_src = rowsum_src; a.rs_dst = rowsum_dst; a.rs_rows = (int)rowsum_rows; a.rs_cols = (int)rowsum_cols;
+  a.rs_blocks = rowsum_src ? (int)cdiv(rowsum_cols, 256) : 0;
+  return SLU_OK;
+}
+
 extern "C" int slu_gemm_tn_batched(const float* const* A, const int64_t* lda, const float* const* B, const int64_t* ldb,
                                    float* const* C, const int64_t* ldc, const int64_t* M, const int64_t* N,
                                    const int64_t* K, int64_t count, const float* rowsum_src, int64_t rowsum_rows,
                                    int64_t rowsum_cols, float* rowsum_dst, void* stream) {
   SLU_REQUIRE(A && B && C && lda && ldb && ldc && M && N && K, "slu_gemm_tn_batched: null pointer");
-  SLU_REQUIRE((rowsum_src == nullptr) == (rowsum_dst == nullptr), "slu_gemm_tn_batched: rowsum_src and rowsum_dst go together");
-  SLU_REQUIRE(!rowsum_src || (rowsum_rows >= 1 && rowsum_cols >= 1 && rowsum_rows < (1LL << 30) && rowsum_cols < (1LL << 30)),
-              "slu_gemm_tn_batched: bad row-sum size");
   SLU_REQUIRE(count >= 1 && count <= 4, "slu_gemm_tn_batched: 1..4 problems per call");
   // tile height: 64 rows (16-byte A loads) where the shapes allow it, else 48 rows (12-byte loads).  Measured for the
   // intent layer (144 tiles of 64 rows vs 192 of 48 on 64 CUs): 52 vs 57 us — the even spread of the 48-row tiles does
@@ -1000,46 +1025,41 @@ extern "C" int slu_gemm_tn_batched(const float* const* A, const int64_t* lda, co
       if (okw && wt >= 32) mt = 8;
     }
   }
-  TnArgs a;
-  int tiles = 0;
-  for (int q = 0; q < (int)count; ++q) {
-    SLU_REQUIRE(A[q] && B[q] && C[q] && M[q] > 0 && N[q] > 0 && K[q] > 0, "slu_gemm_tn_batched: bad problem %d", q);
-    SLU_REQUIRE(M[q] < (1LL << 30) && N[q] < (1LL << 30) && K[q] < (1LL << 30), "slu_gemm_tn_batched: size overflow");
+  for (int q = 0; q < (int)count; ++q)
     if ((N[q] | ldb[q]) & 1 || ((uintptr_t)B[q] & 7))
       SLU_FAIL(SLU_ERR_UNSUPPORTED, "slu_gemm_tn_batched: N and ldb must be even (B 8-byte aligned)");
-    a.p[q].A = A[q]; a.p[q].B = B[q]; a.p[q].C = C[q];
-    a.p[q].lda = lda[q]; a.p[q].ldb = ldb[q]; a.p[q].ldc = ldc[q];
-    a.p[q].M = (int)M[q]; a.p[q].N = (int)N[q]; a.p[q].K = (int)K[q];
-    const int tile_n = mt == 8 ? 64 : 32, tile_m = mt == 8 ? 64 : 16 * mt;
-    a.p[q].tiles_n = (int)cdiv(N[q], tile_n);
-    tiles += (int)(cdiv(M[q], tile_m) * cdiv(N[q], tile_n));
-    a.p[q].tile_end = tiles;
-  }
-  a.count = (int)count;
-  a.tiles = tiles;
-  a.rs_src = rowsum_src; a.rs_dst = rowsum_dst; a.rs_rows = (int)rowsum_rows; a.rs_cols = (int)rowsum_cols;
-  const int extra = rowsum_src ? (int)cdiv(rowsum_cols, 256) : 0;
-  a.rs_blocks = extra;
+  TnArgs a;
+  const int rc = tn_fill_args("slu_gemm_tn_batched", a, A, lda, B, ldb, C, ldc, M, N, K, count, mt == 8 ? 64 : 16 * mt,
+                              mt == 8 ? 64 : 32, rowsum_src, rowsum_rows, rowsum_cols, rowsum_dst);
+  if (rc != SLU_OK) return rc;
+  const dim3 grid((unsigned)(a.tiles + a.rs_blocks));
   if (mt == 8)
-    hipLaunchKernelGGL(gemm_tn_small_wide_kernel, dim3((unsigned)(tiles + extra)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(gemm_tn_small_wide_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
   else if (mt == 4)
-    hipLaunchKernelGGL(gemm_tn_small_kernel, dim3((unsigned)(tiles + extra)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(gemm_tn_small_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
   else
-    hipLaunchKernelGGL(gemm_tn_small_mt_kernel<3>, dim3((unsigned)(tiles + extra)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(gemm_tn_small_mt_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, a);
   SLU_CHECK_LAUNCH("gemm_tn_small_kernel");
   return SLU_OK;
 }
 
 // Split-K form of slu_gemm_tn_batched for long k ranges (include/slu_hip.h).
-static int tn_splitk_factor(int64_t tiles, int64_t kmin, int64_t max_wg = 0) {
+static int tn_splitk_factor(const int64_t* M, const int64_t* N, const int64_t* K, int64_t count, int64_t max_wg,
+                            int64_t* tiles_out) {
   // ONE round of workgroups: two fit a CU (216 VGPRs), 512 on the chip — 654 workgroups (nine splits of a layer's 72 tiles)
   // ran as two rounds, the second a quarter full: 168 us per launch against 141-150 with seven; at least 256 k rows per
   // split, at most 16.  (Eight splits put split ks on XCD ks — linear id tile * 8 + ks — so that a k row crosses HBM -> L2
   // once: FETCH_SIZE 266 -> 91 MB per launch, L2 hits 39 -> 75 %, and the launch got SLOWER, 174 us: nine eighths of a round,
   // and the bound is not HBM but the L1's outstanding requests — k-slow 16-byte loads, 8 MAC per operand byte, ~16 B/clk per
   // CU needed at the MFMA peak; profiles/r04_am_pmc_tn_splitk.txt.)
-  // max_wg > 0 (slu_gemm_tn_batched_splitk_wg): a smaller budget — a launch that runs BESIDE a latency-bound recurrence on a
-  // branch of its own must leave whole CUs empty for it (192-216 workgroups spread one per CU)
+  // max_wg > 0: a smaller budget — a launch that runs BESIDE a latency-bound recurrence on a branch of its own must leave
+  // whole CUs empty for it (192-216 workgroups spread one per CU)
+  int64_t tiles = 0, kmin = K[0];
+  for (int q = 0; q < (int)count; ++q) {
+    tiles += cdiv(M[q], 64) * cdiv(N[q], 64);
+    kmin = K[q] < kmin ? K[q] : kmin;
+  }
+  *tiles_out = tiles;
   int64_t ks = (max_wg > 0 ? max_wg : 512) / tiles;
   ks = ks < 1 ? 1 : ks;
   if (ks > 16) ks = 16;
@@ -1056,73 +1076,40 @@ static bool tn_splitk_shapes_ok(const float* const* A, const int64_t* lda, const
   return true;
 }
 
-extern "C" size_t slu_gemm_tn_splitk_workspace_bytes_wg(const int64_t* M, const int64_t* N, const int64_t* K, int64_t count,
-                                                        int64_t max_workgroups) {
+extern "C" size_t slu_gemm_tn_splitk_workspace_bytes(const int64_t* M, const int64_t* N, const int64_t* K, int64_t count,
+                                                     int64_t max_workgroups) {
   if (!M || !N || !K || count < 1 || count > 4) return 0;
-  int64_t tiles = 0, kmin = K[0];
-  for (int q = 0; q < (int)count; ++q) {
-    tiles += cdiv(M[q], 64) * cdiv(N[q], 64);
-    kmin = K[q] < kmin ? K[q] : kmin;
-  }
-  return (size_t)tiles * tn_splitk_factor(tiles, kmin, max_workgroups) * 4096 * sizeof(float);
-}
-
-extern "C" size_t slu_gemm_tn_splitk_workspace_bytes(const int64_t* M, const int64_t* N, const int64_t* K, int64_t count) {
-  return slu_gemm_tn_splitk_workspace_bytes_wg(M, N, K, count, 0);
-}
-
-extern "C" int slu_gemm_tn_batched_splitk_wg(const float* const* A, const int64_t* lda, const float* const* B, const int64_t* ldb,
-                                             float* const* C, const int64_t* ldc, const int64_t* M, const int64_t* N,
-                                             const int64_t* K, int64_t count, const float* rowsum_src, int64_t rowsum_rows,
-                                             int64_t rowsum_cols, float* rowsum_dst, void* workspace, size_t workspace_bytes,
-                                             uint32_t* tickets, int64_t n_tickets, int64_t max_workgroups, void* stream) {
-  SLU_REQUIRE(A && B && C && lda && ldb && ldc && M && N && K, "slu_gemm_tn_batched_splitk: null pointer");
-  SLU_REQUIRE((rowsum_src == nullptr) == (rowsum_dst == nullptr), "slu_gemm_tn_batched_splitk: rowsum_src and rowsum_dst go together");
-  SLU_REQUIRE(!rowsum_src || (rowsum_rows >= 1 && rowsum_cols >= 1 && rowsum_rows < (1LL << 30) && rowsum_cols < (1LL << 30)),
-              "slu_gemm_tn_batched_splitk: bad row-sum size");
-  SLU_REQUIRE(count >= 1 && count <= 4, "slu_gemm_tn_batched_splitk: 1..4 problems per call");
-  if (!tn_splitk_shapes_ok(A, lda, B, ldb, M, N, count))
-    SLU_FAIL(SLU_ERR_UNSUPPORTED, "slu_gemm_tn_batched_splitk: M, lda, N, ldb must be multiples of 4 and A, B 16-byte aligned");
-  TnArgs a;
-  int tiles = 0;
-  int64_t kmin = K[0];
-  for (int q = 0; q < (int)count; ++q) {
-    SLU_REQUIRE(A[q] && B[q] && C[q] && M[q] > 0 && N[q] > 0 && K[q] > 0, "slu_gemm_tn_batched_splitk: bad problem %d", q);
-    SLU_REQUIRE(M[q] < (1LL << 30) && N[q] < (1LL << 30) && K[q] < (1LL << 30), "slu_gemm_tn_batched_splitk: size overflow");
-    a.p[q].A = A[q]; a.p[q].B = B[q]; a.p[q].C = C[q];
-    a.p[q].lda = lda[q]; a.p[q].ldb = ldb[q]; a.p[q].ldc = ldc[q];
-    a.p[q].M = (int)M[q]; a.p[q].N = (int)N[q]; a.p[q].K = (int)K[q];
-    a.p[q].tiles_n = (int)cdiv(N[q], 64);
-    tiles += (int)(cdiv(M[q], 64) * cdiv(N[q], 64));
-    a.p[q].tile_end = tiles;
-    kmin = K[q] < kmin ? K[q] : kmin;
-  }
-  SLU_REQUIRE(max_workgroups >= 0, "slu_gemm_tn_batched_splitk: negative workgroup budget");
-  const int ksplit = tn_splitk_factor(tiles, kmin, max_workgroups);
-  if (ksplit > 1) {
-    const size_t need = (size_t)tiles * ksplit * 4096 * sizeof(float);
-    if (!workspace || workspace_bytes < need)
-      SLU_FAIL(SLU_ERR_WORKSPACE, "slu_gemm_tn_batched_splitk: workspace too small (%zu < %zu)", workspace_bytes, need);
-    SLU_REQUIRE(tickets && n_tickets >= tiles, "slu_gemm_tn_batched_splitk: needs %d zeroed ticket words", tiles);
-  }
-  a.count = (int)count;
-  a.tiles = tiles;
-  a.rs_src = rowsum_src; a.rs_dst = rowsum_dst; a.rs_rows = (int)rowsum_rows; a.rs_cols = (int)rowsum_cols;
-  const int extra = rowsum_src ? (int)cdiv(rowsum_cols, 256) : 0;
-  a.rs_blocks = extra;
-  hipLaunchKernelGGL(gemm_tn_wide_splitk_kernel, dim3((unsigned)(tiles * ksplit + extra)), dim3(256), 0, (hipStream_t)stream,
-                     a, ksplit, reinterpret_cast<float*>(workspace), (unsigned*)tickets);
-  SLU_CHECK_LAUNCH("gemm_tn_wide_splitk_kernel");
-  return SLU_OK;
+  int64_t tiles;
+  const int ksplit = tn_splitk_factor(M, N, K, count, max_workgroups, &tiles);
+  return (size_t)tiles * ksplit * 4096 * sizeof(float);
 }
 
 extern "C" int slu_gemm_tn_batched_splitk(const float* const* A, const int64_t* lda, const float* const* B, const int64_t* ldb,
                                           float* const* C, const int64_t* ldc, const int64_t* M, const int64_t* N,
                                           const int64_t* K, int64_t count, const float* rowsum_src, int64_t rowsum_rows,
                                           int64_t rowsum_cols, float* rowsum_dst, void* workspace, size_t workspace_bytes,
-                                          uint32_t* tickets, int64_t n_tickets, void* stream) {
-  return slu_gemm_tn_batched_splitk_wg(A, lda, B, ldb, C, ldc, M, N, K, count, rowsum_src, rowsum_rows, rowsum_cols, rowsum_dst,
-                                       workspace, workspace_bytes, tickets, n_tickets, 0, stream);
+                                          uint32_t* tickets, int64_t n_tickets, int64_t max_workgroups, void* stream) {
+  SLU_REQUIRE(A && B && C && lda && ldb && ldc && M && N && K, "slu_gemm_tn_batched_splitk: null pointer");
+  SLU_REQUIRE(count >= 1 && count <= 4, "slu_gemm_tn_batched_splitk: 1..4 problems per call");
+  if (!tn_splitk_shapes_ok(A, lda, B, ldb, M, N, count))
+    SLU_FAIL(SLU_ERR_UNSUPPORTED, "slu_gemm_tn_batched_splitk: M, lda, N, ldb must be multiples of 4 and A, B 16-byte aligned");
+  TnArgs a;
+  const int rc = tn_fill_args("slu_gemm_tn_batched_splitk", a, A, lda, B, ldb, C, ldc, M, N, K, count, 64, 64, rowsum_src,
+                              rowsum_rows, rowsum_cols, rowsum_dst);
+  if (rc != SLU_OK) return rc;
+  SLU_REQUIRE(max_workgroups >= 0, "slu_gemm_tn_batched_splitk: negative workgroup budget");
+  int64_t tiles;
+  const int ksplit = tn_splitk_factor(M, N, K, count, max_workgroups, &tiles);
+  if (ksplit > 1) {
+    const size_t need = (size_t)tiles * ksplit * 4096 * sizeof(float);
+    if (!workspace || workspace_bytes < need)
+      SLU_FAIL(SLU_ERR_WORKSPACE, "slu_gemm_tn_batched_splitk: workspace too small (%zu < %zu)", workspace_bytes, need);
+    SLU_REQUIRE(tickets && n_tickets >= tiles, "slu_gemm_tn_batched_splitk: needs %d zeroed ticket words", (int)tiles);
+  }
+  hipLaunchKernelGGL(gemm_tn_wide_splitk_kernel, dim3((unsigned)(a.tiles * ksplit + a.rs_blocks)), dim3(256), 0,
+                     (hipStream_t)stream, a, ksplit, reinterpret_cast<float*>(workspace), (unsigned*)tickets);
+  SLU_CHECK_LAUNCH("gemm_tn_wide_splitk_kernel");
+  return SLU_OK;
 }
 
 extern "C" int slu_colsum_f32(const float* X, int64_t x_rs, float* out, int64_t M, int64_t N,

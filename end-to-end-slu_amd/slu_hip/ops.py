@@ -785,13 +785,10 @@ def gru_seq_fwd_bf16(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, T, B, H, D, nsplit, wan
 TN_SMALL_ROWS = 4096      # weight gradients of a GRU layer with T*B up to this many rows go through ONE batched launch
 
 
-def gemm_tn_batched(problems, rowsum=None):
-    """problems: [(A (K, M), B (K, N), C (M, N))] 2-D fp32 views with unit column stride (row strides free);
-    C_q = A_q^T B_q for up to four problems in one launch (slu_gemm_tn_batched).
-    rowsum: optional (src (R, ...) contiguous fp32, dst (numel of a row)) — dst = src.sum(0) in the same launch."""
+def _tn_args(problems, rowsum):
+    """The checks and ctypes arguments the two batched TN launches share: the nine per-problem host arrays (A, lda, B, ldb,
+    C, ldc, M, N, K), the count and the row-sum job (src, rows, cols, dst)."""
     import ctypes
-    L = _lib.load()
-    n = len(problems)
     for A, B, C in problems:
         assert A.stride(1) == 1 and B.stride(1) == 1 and C.stride(1) == 1 and A.shape[0] == B.shape[0]
         assert C.shape == (A.shape[1], B.shape[1])
@@ -799,16 +796,22 @@ def gemm_tn_batched(problems, rowsum=None):
         src, dst = rowsum
         assert src.is_contiguous() and dst.is_contiguous() and src.dtype == dst.dtype == torch.float32
         assert src.numel() == src.shape[0] * dst.numel()
-    vp, i64 = ctypes.c_void_p, ctypes.c_int64
+    n = len(problems)
     arr = lambda ty, vals: (ty * n)(*vals)
-    _lib.check(L.slu_gemm_tn_batched(arr(vp, [p[0].data_ptr() for p in problems]), arr(i64, [p[0].stride(0) for p in problems]),
-                                     arr(vp, [p[1].data_ptr() for p in problems]), arr(i64, [p[1].stride(0) for p in problems]),
-                                     arr(vp, [p[2].data_ptr() for p in problems]), arr(i64, [p[2].stride(0) for p in problems]),
-                                     arr(i64, [p[2].shape[0] for p in problems]), arr(i64, [p[2].shape[1] for p in problems]),
-                                     arr(i64, [p[0].shape[0] for p in problems]), n,
-                                     rowsum[0].data_ptr() if rowsum else None, rowsum[0].shape[0] if rowsum else 0,
-                                     rowsum[1].numel() if rowsum else 0, rowsum[1].data_ptr() if rowsum else None,
-                                     _stream()), "slu_gemm_tn_batched")
+    args = []
+    for j in range(3):
+        args += [arr(ctypes.c_void_p, [p[j].data_ptr() for p in problems]), arr(ctypes.c_int64, [p[j].stride(0) for p in problems])]
+    args += [arr(ctypes.c_int64, [C.shape[0] for _, _, C in problems]), arr(ctypes.c_int64, [C.shape[1] for _, _, C in problems]),
+             arr(ctypes.c_int64, [A.shape[0] for A, _, _ in problems]), n]
+    return args + ([rowsum[0].data_ptr(), rowsum[0].shape[0], rowsum[1].numel(), rowsum[1].data_ptr()] if rowsum
+                   else [None, 0, 0, None])
+
+
+def gemm_tn_batched(problems, rowsum=None):
+    """problems: [(A (K, M), B (K, N), C (M, N))] 2-D fp32 views with unit column stride (row strides free);
+    C_q = A_q^T B_q for up to four problems in one launch (slu_gemm_tn_batched).
+    rowsum: optional (src (R, ...) contiguous fp32, dst (numel of a row)) — dst = src.sum(0) in the same launch."""
+    _lib.check(_lib.load().slu_gemm_tn_batched(*_tn_args(problems, rowsum), _stream()), "slu_gemm_tn_batched")
 
 
 _TN_TICKETS = {}          # (device, stream) -> zeroed ticket words of slu_gemm_tn_batched_splitk (the kernel leaves them zero)
@@ -885,35 +888,41 @@ def gemm_tn_splitk_ok(operands):
                for A, B in operands)
 
 
+def gru_wgrad_plan(T, B, I, H, D, need_ih, need_hh, aligned):
+    """-> (kind, budget, branch mode) of the weight gradients of a trainable GRU layer: T steps x B sequences, I inputs, H
+    hidden, D directions; need_ih: some direction's W_ih needs a gradient; need_hh: per direction, W_hh does; aligned:
+    gemm_tn_splitk_ok of the layer's operand views.  Depends on these and the arithmetic settings only, never on the loop
+    kind (the budget sets the summation order).  Kinds:
+      "batched"  T*B <= TN_SMALL_ROWS (the intent layer): every weight gradient and the bias row sums in ONE
+                 slu_gemm_tn_batched launch (no split-K workspaces, no reduce launches);
+      "splitk"   T*B >= TN_SPLITK_MIN_ROWS in exact-fp32 training (SLU_TN_SPLITK=0: off): the same in ONE
+                 slu_gemm_tn_batched_splitk launch instead of three k-slow GEMMs + three reduce launches + a column sum, with
+                 wgrad_branch()'s workgroup budget and mode ("layer" / "pass": a graph branch in fully trainable loops;
+                 "0": in line, full round);
+      "forked"   everything else (bf16 or split arithmetic, T = 1, weights only partly trainable, shapes neither launch
+                 takes): one GEMM per matrix on _Fork streams, colsum for the biases."""
+    one_launch = T > 1 and need_ih and all(need_hh) and I % 4 == 0 and H % 4 == 0
+    if one_launch and T * B <= TN_SMALL_ROWS:
+        return "batched", 0, "0"
+    if (one_launch and T * B >= TN_SPLITK_MIN_ROWS and train_nsplit(True) == 0 and os.environ.get("SLU_TN_SPLITK", "1") != "0"
+            and aligned):
+        mode, budget = wgrad_branch()
+        return "splitk", budget, mode if budget else "0"
+    return "forked", 0, "0"
+
+
 def gemm_tn_batched_splitk(problems, rowsum=None, max_wg=0):
     """gemm_tn_batched for long k ranges (the weight gradients of a GRU layer with thousands of rows): one launch, the k
-    range split over workgroups, partial tiles folded in a fixed order by each tile's last workgroup."""
-    import ctypes
+    range split over workgroups, partial tiles folded in a fixed order by each tile's last workgroup.
+    max_wg: workgroup budget (0 = a full round)."""
     L = _lib.load()
-    n = len(problems)
-    for A, B, C in problems:
-        assert A.shape[0] == B.shape[0] and C.shape == (A.shape[1], B.shape[1])
-    assert gemm_tn_splitk_ok([(A, B) for A, B, _ in problems]) and all(C.stride(1) == 1 for _, _, C in problems)
-    if rowsum:
-        src, dst = rowsum
-        assert src.is_contiguous() and dst.is_contiguous() and src.dtype == dst.dtype == torch.float32
-        assert src.numel() == src.shape[0] * dst.numel()
-    vp, i64 = ctypes.c_void_p, ctypes.c_int64
-    arr = lambda ty, vals: (ty * n)(*vals)
-    Ms, Ns, Ks = (arr(i64, [p[2].shape[0] for p in problems]), arr(i64, [p[2].shape[1] for p in problems]),
-                  arr(i64, [p[0].shape[0] for p in problems]))
+    assert gemm_tn_splitk_ok([(A, B) for A, B, _ in problems])
+    args = _tn_args(problems, rowsum)
     dev = problems[0][0].device
-    wsb = L.slu_gemm_tn_splitk_workspace_bytes_wg(Ms, Ns, Ks, n, int(max_wg))    # max_wg: workgroup budget (0 = a full round)
+    wsb = L.slu_gemm_tn_splitk_workspace_bytes(*args[6:10], int(max_wg))        # M, N, K, count
     ws = _workspace(wsb, dev)
-    tiles = sum(-(-p[2].shape[0] // 64) * -(-p[2].shape[1] // 64) for p in problems)
-    tk = tn_tickets(dev, tiles)
-    _lib.check(L.slu_gemm_tn_batched_splitk_wg(arr(vp, [p[0].data_ptr() for p in problems]), arr(i64, [p[0].stride(0) for p in problems]),
-                                            arr(vp, [p[1].data_ptr() for p in problems]), arr(i64, [p[1].stride(0) for p in problems]),
-                                            arr(vp, [p[2].data_ptr() for p in problems]), arr(i64, [p[2].stride(0) for p in problems]),
-                                            Ms, Ns, Ks, n,
-                                            rowsum[0].data_ptr() if rowsum else None, rowsum[0].shape[0] if rowsum else 0,
-                                            rowsum[1].numel() if rowsum else 0, rowsum[1].data_ptr() if rowsum else None,
-                                            ws.data_ptr(), wsb, tk.data_ptr(), tk.numel(), int(max_wg), _stream()),
+    tk = tn_tickets(dev, sum(-(-C.shape[0] // 64) * -(-C.shape[1] // 64) for _, _, C in problems))
+    _lib.check(L.slu_gemm_tn_batched_splitk(*args, ws.data_ptr(), wsb, tk.data_ptr(), tk.numel(), int(max_wg), _stream()),
                "slu_gemm_tn_batched_splitk")
 
 
@@ -1336,6 +1345,99 @@ def _gru_dx(g2, w_ih, T, B, I, H, D):
     return gemm_nt(g2, w_ih.t(), grad=True).view(T, B, I)     # (N = I, K = D*3H) view of the stacked weight
 
 
+def _gru_wgrad_operands(x, raw, d_gx, d_gh, T, B, I, H, D):
+    """-> ((g2, x2), [(ga, hp) per direction]): dW_ih = g2^T x2 for both directions at once (d_gx^T x), dW_hh of direction d =
+    ga^T hp (d_gh^T h_{t-1}: the forward scan's h_{t-1} is raw[t-1], so gradient rows t >= 1 against raw rows t - 1; the
+    reverse scan's is raw[t+1]).  T = 1: no h_{t-1} rows."""
+    n = (T - 1) * B
+    h2, r2 = d_gh.view(T * B, D * 3 * H), raw.view(T * B, D * H)
+    hh = [(h2[B:, :3 * H], r2[:n, :H])]
+    if D == 2:
+        hh.append((h2[:n, 3 * H:], r2[B:, H:]))
+    return (d_gx.view(T * B, D * 3 * H), x.view(T * B, I)), hh
+
+
+def _per_direction(dW, D):
+    """dW_ih of each direction: views of the rows of the stacked (D*3H, I) buffer"""
+    H3 = dW.shape[0] // D
+    return [dW[d * H3:(d + 1) * H3] for d in range(D)]
+
+
+def _bias_colsum(dbp):
+    """(tiles, D, 6H) per-tile partials -> (D, 6H): [d(b_ih) (3H) | d(b_hh) (3H)]  (slu_colsum_f32, deterministic)"""
+    return colsum(dbp.view(dbp.shape[0], -1)).view(dbp.shape[1:])
+
+
+# The three executors of gru_wgrad_plan's kinds: (g2, x2), [(ga, hp)] from _gru_wgrad_operands, dbp the (tiles, D, 6H) bias
+# partials of slu_gru_seq_bwd or None -> (dW_ih per direction, dW_hh per direction, bias gradients (D, 6H) or None, join the
+# auxiliary streams at the end of the layer's backward?)
+
+def _wgrad_batched(ih, hh, dbp, splitk=False):
+    """Kind "batched" (and "splitk" at a full round, in line): ONE launch for every weight gradient of the layer — dW_ih one
+    stacked buffer, the bias gradients summed from dbp's per-tile partials by the same launch."""
+    (g2, x2), dev = ih, ih[0].device
+    dW = torch.empty(g2.shape[1], x2.shape[1], dtype=torch.float32, device=dev)
+    dW_hh = [torch.empty(ga.shape[1], hp.shape[1], dtype=torch.float32, device=dev) for ga, hp in hh]
+    db = rowsum = None
+    if dbp is not None:
+        db = torch.empty(dbp.shape[1:], dtype=torch.float32, device=dev)
+        rowsum = (dbp.contiguous(), db)
+    (gemm_tn_batched_splitk if splitk else gemm_tn_batched)([(g2, x2, dW)] + [(*o, w) for o, w in zip(hh, dW_hh)], rowsum)
+    return _per_direction(dW, len(hh)), dW_hh, db, False
+
+
+def _wgrad_splitk(ih, hh, dbp, budget, mode):
+    """Kind "splitk": one slu_gemm_tn_batched_splitk launch with a workgroup budget; budget 0 is the batched form.  Else, in
+    fully trainable loops (_Fork.defer; wgrad_branch has the modes and the measurements), the launch goes to an auxiliary
+    stream / graph branch beside this layer's data-gradient GEMM, to be joined at the end of the layer's backward or — mode
+    "pass" — by the trainer's single join after the whole backward pass.  What makes the open form safe:
+     * every gradient it writes is a tensor of its own (not a view of a stacked buffer): AccumulateGrad takes such a tensor
+       over without reading it — a view it would CLONE, on the main stream, before the branch has written it;
+     * the bias sums (views of one small buffer) are formed on the main stream by slu_colsum_f32;
+     * operands and results are recorded on the branch's stream (record_stream marks the storage a view belongs to), so
+       that the allocator does not hand their memory out again before the branch has used it (in "pass" mode long after
+       the backward function has returned)."""
+    if not budget:
+        return _wgrad_batched(ih, hh, dbp, splitk=True)
+    (g2, x2), dev = ih, ih[0].device
+    H3 = g2.shape[1] // len(hh)
+    dW_ih = [torch.empty(H3, x2.shape[1], dtype=torch.float32, device=dev) for _ in hh]
+    probs = [(g2[:, d * H3:(d + 1) * H3], x2, w) for d, w in enumerate(dW_ih)]
+    dW_hh = [torch.empty(ga.shape[1], hp.shape[1], dtype=torch.float32, device=dev) for ga, hp in hh]
+    probs += [(*o, w) for o, w in zip(hh, dW_hh)]
+    db = _bias_colsum(dbp) if dbp is not None else None
+    branch = mode != "0" and _Fork.defer
+    fork = _Fork(dev, 0) if branch else contextlib.nullcontext()
+    with fork:
+        gemm_tn_batched_splitk(probs, None, max_wg=budget)
+    if branch and fork.active:
+        for t in (t for prob in probs for t in prob):
+            t.record_stream(fork.side)
+    return dW_ih, dW_hh, db, branch and fork.active and mode == "layer"
+
+
+def _wgrad_forked(ih, hh, dbp, need_ih, need_hh, T):
+    """Kind "forked": the weight-gradient GEMMs are independent of each other and of the data-gradient GEMM: they run on
+    auxiliary streams (graph branches under capture) — dW_ih on 0, dW_hh of direction d on 1 + d — while dx proceeds on
+    the main stream.  T = 1: dW_hh is zero."""
+    (g2, x2), dev = ih, ih[0].device
+    db = _bias_colsum(dbp) if dbp is not None else None
+    dW_ih = None
+    if need_ih:
+        dW = torch.empty(g2.shape[1], x2.shape[1], dtype=torch.float32, device=dev)
+        with _Fork(dev, 0):
+            _wgrad(g2, x2, dW)
+        dW_ih = _per_direction(dW, len(hh))
+    dW_hh = [None] * len(hh)
+    for d, (ga, hp) in enumerate(hh):
+        if need_hh[d]:
+            dW_hh[d] = (torch.zeros if T == 1 else torch.empty)(ga.shape[1], hp.shape[1], dtype=torch.float32, device=dev)
+            if T > 1:
+                with _Fork(dev, 1 + d):
+                    _wgrad(ga, hp, dW_hh[d])
+    return dW_ih, dW_hh, db, True
+
+
 class GRULayerFn(torch.autograd.Function):
     """nn.GRU (1 layer, h0 = 0) -> RNNSelect -> Dropout -> Downsample  (models.py:232-253).
     x time-major (T, B, I) -> (T_out, B, D*H).
@@ -1393,133 +1495,28 @@ class GRULayerFn(torch.autograd.Function):
         ng = ctx.needs_input_grad
         # positions: 0 x | 1 w_ih 2 b_ih (storage, no grad) | 3 w_ih_f 4 w_ih_r 5 b_ih_f 6 b_ih_r |
         #            7 w_hh_f 8 b_hh_f 9 w_hh_r 10 b_hh_r
-        need_bias = ng[5] or ng[6] or ng[8] or ng[10]
-        x2 = x.view(T * B, I)
-        g2 = d_gx.view(T * B, D * 3 * H)
-        h2 = d_gh.view(T * B, D * 3 * H)
-        r2 = raw.view(T * B, D * H)
+        need_ih, need_hh = ng[3] or ng[4], [ng[7 + 2 * d] for d in range(D)]
+        bias_part = dbp if ng[5] or ng[6] or ng[8] or ng[10] else None
+        ih, hh = _gru_wgrad_operands(x, raw, d_gx, d_gh, T, B, I, H, D)
+        kind, budget, mode = gru_wgrad_plan(T, B, I, H, D, need_ih, need_hh, gemm_tn_splitk_ok([ih] + hh))
+        if kind == "batched":
+            dW_ih, dW_hh, db, join = _wgrad_batched(ih, hh, bias_part)
+        elif kind == "splitk":
+            dW_ih, dW_hh, db, join = _wgrad_splitk(ih, hh, bias_part, budget, mode)
+        else:
+            dW_ih, dW_hh, db, join = _wgrad_forked(ih, hh, bias_part, need_ih, need_hh, T)
         grads = [None] * 19
-        dev = x.device
-        small = (T * B <= TN_SMALL_ROWS and T > 1 and (ng[3] or ng[4]) and all(ng[7 + 2 * d] for d in range(D))
-                 and I % 4 == 0 and H % 4 == 0)
-        # long layers (thousands of rows) in exact-fp32 training: the same ONE launch with the k range split over workgroups
-        # (slu_gemm_tn_batched_splitk) instead of three k-slow GEMMs + three reduce launches + a column sum
-        long_rows = (not small and T > 1 and T * B >= TN_SPLITK_MIN_ROWS and (ng[3] or ng[4]) and all(ng[7 + 2 * d] for d in range(D))
-                     and I % 4 == 0 and H % 4 == 0 and train_nsplit(True) == 0
-                     and os.environ.get("SLU_TN_SPLITK", "1") != "0")
-        if long_rows:
-            n = (T - 1) * B
-            long_rows = gemm_tn_splitk_ok([(g2, x2)] + [
-                ((h2[:, d * 3 * H:(d + 1) * 3 * H][B:], r2[:n, :H]) if d == 0
-                 else (h2[:, d * 3 * H:(d + 1) * 3 * H][:n], r2[B:, H:])) for d in range(D)])
-        small = small or long_rows
-        if need_bias and not small:
-            # (tiles, D, 6H) per-tile partials -> (D, 6H): [d(b_ih) (3H) | d(b_hh) (3H)]  (slu_colsum_f32, deterministic)
-            dbp = colsum(dbp.view(dbp.shape[0], D * 6 * H)).view(D, 6 * H)
-        if small:
-            # a few thousand rows (the intent layer of the look-ahead pipeline): every weight gradient of the layer
-            # in ONE launch (no split-K workspaces, no reduce launches).  The choice depends on the shape only.
-            n = (T - 1) * B
-            # Round 5, fully trainable loops (_Fork.defer; wgrad_branch has the modes and the measurements): the launch goes to
-            # an auxiliary stream / graph branch with a workgroup budget, beside this layer's data-gradient GEMM — or, mode
-            # "pass", stays open until the trainer's single join after the whole backward pass.  What makes the open form safe:
-            #  * every gradient it writes is a tensor of its own (not a view of a stacked buffer): AccumulateGrad takes such
-            #    a tensor over without reading it — a view it would CLONE, on this stream, before the branch has written it;
-            #  * the bias sums (views of one small buffer) are formed on THIS stream by slu_colsum_f32;
-            #  * the operands are recorded on the branch's stream, so the allocator does not hand their memory out again
-            #    before the branch has read them.
-            # The budget (and with it the split count = the summation order) depends on the SHAPE only, so that every loop
-            # kind — captured, eager, look-ahead with trainable long layers — produces the same bits; the branch itself only
-            # where nothing runs beside the step (_Fork.defer).
-            mode, budget = wgrad_branch() if long_rows else ("0", 0)
-            branch = bool(budget) and _Fork.defer
-            join_here = False
-            outs = []
-            if budget:
-                dWs = [torch.empty(3 * H, I, dtype=torch.float32, device=dev) for _ in range(D)]
-                probs = [(g2[:, d * 3 * H:(d + 1) * 3 * H], x2, dWs[d]) for d in range(D)]
-            else:
-                dW = torch.empty(D * 3 * H, I, dtype=torch.float32, device=dev)
-                probs = [(g2, x2, dW)]
-            for d in range(D):
-                hd = h2[:, d * 3 * H:(d + 1) * 3 * H]
-                ga, hp = (hd[B:], r2[:n, :H]) if d == 0 else (hd[:n], r2[B:, H:])
-                dWh = torch.empty(3 * H, H, dtype=torch.float32, device=dev)
-                probs.append((ga, hp, dWh))
-                outs.append(dWh)
-            rowsum = None
-            if need_bias and budget:
-                dbp = colsum(dbp.view(dbp.shape[0], D * 6 * H)).view(D, 6 * H)
-            elif need_bias:                                # the per-tile bias partial sums, summed by the same launch
-                db = torch.empty(dbp.shape[1:], dtype=torch.float32, device=dev)
-                rowsum = (dbp.contiguous(), db)
-                dbp = db
-            if budget:
-                fork = _Fork(dev, 0) if branch else contextlib.nullcontext()
-                with fork:
-                    gemm_tn_batched_splitk(probs, None, max_wg=budget)
-                if branch and fork.active:
-                    # operands AND results: the results are written on the branch's stream (in "pass" mode long after this
-                    # function has returned), the allocator must not recycle them for the main stream before that
-                    for t in (d_gx, d_gh, x, raw, *dWs, *outs):
-                        t.record_stream(fork.side)
-                    if mode == "layer":
-                        join_here = True                 # after the data-gradient GEMM below
-                grads[3] = dWs[0]
-                if D == 2:
-                    grads[4] = dWs[1]
-            else:
-                (gemm_tn_batched_splitk if long_rows else gemm_tn_batched)(probs, rowsum)
-                grads[3] = dW[:3 * H]
-                if D == 2:
-                    grads[4] = dW[3 * H:]
-            for d in range(D):
-                grads[7 + 2 * d] = outs[d]
-                if ng[8 + 2 * d]:
-                    grads[8 + 2 * d] = dbp[d, 3 * H:]
-            if ng[0]:
-                grads[0] = _gru_dx(g2, w_ih, T, B, I, H, D)
-            if ng[5]:
-                grads[5] = dbp[0, :3 * H]
-            if D == 2 and ng[6]:
-                grads[6] = dbp[1, :3 * H]
-            if join_here:
-                _Fork.join(dev)
-            return tuple(grads)
-        # The weight-gradient GEMMs are independent of each other and of the data-gradient GEMM: they
-        # run on auxiliary streams (graph branches under capture) while dx proceeds on this one.
-        if ng[3] or ng[4]:                                 # dW_ih = d_gx^T x, one GEMM for both directions
-            dW = torch.empty(D * 3 * H, I, dtype=torch.float32, device=dev)
-            with _Fork(dev, 0):
-                _wgrad(g2, x2, dW)
-            grads[3] = dW[:3 * H]
-            if D == 2:
-                grads[4] = dW[3 * H:]
-        for d in range(D):
-            wpos, bpos = 7 + 2 * d, 8 + 2 * d              # (w_hh, b_hh) of direction d
-            if ng[wpos]:                                   # dW_hh = d_gh^T h_{t-1}
-                if T > 1:
-                    n = (T - 1) * B
-                    hd = h2[:, d * 3 * H:(d + 1) * 3 * H]
-                    if d == 0:     # h_{t-1} = raw[t-1]: gradient rows t >= 1 against raw rows t-1
-                        ga, hp = hd[B:], r2[:n, :H]
-                    else:          # reverse scan: h_prev(t) = raw[t+1]
-                        ga, hp = hd[:n], r2[B:, H:]
-                    dWh = torch.empty(3 * H, H, dtype=torch.float32, device=dev)
-                    with _Fork(dev, 1 + d):
-                        _wgrad(ga, hp, dWh)
-                    grads[wpos] = dWh
-                else:
-                    grads[wpos] = torch.zeros(3 * H, H, dtype=torch.float32, device=dev)
-            if ng[bpos]:
-                grads[bpos] = dbp[d, 3 * H:]
         if ng[0]:                                          # dx = d_gx W_ih (both directions, K = D*3H)
-            grads[0] = _gru_dx(g2, w_ih, T, B, I, H, D)
-        if ng[5]:
-            grads[5] = dbp[0, :3 * H]
-        if D == 2 and ng[6]:
-            grads[6] = dbp[1, :3 * H]
-        _Fork.join(dev)
+            grads[0] = _gru_dx(ih[0], w_ih, T, B, I, H, D)
+        for d in range(D):
+            grads[3 + d] = dW_ih[d] if dW_ih else None
+            grads[7 + 2 * d] = dW_hh[d]
+            if ng[5 + d]:
+                grads[5 + d] = db[d, :3 * H]
+            if ng[8 + 2 * d]:
+                grads[8 + 2 * d] = db[d, 3 * H:]
+        if join:
+            _Fork.join(x.device)
         return tuple(grads)
 
 

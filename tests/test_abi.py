@@ -20,12 +20,12 @@ def test_header_and_binding_table_agree():
     assert header_functions() == sorted(lib.SIGNATURES)
 
 
-def test_library_loads_and_exports_every_symbol():
+def test_library_loads_at_abi_10_and_exports_every_symbol():
     from slu_hip import lib
     L = lib.load()
     for name in header_functions():
         assert hasattr(L, name), name
-    assert L.slu_version() == lib.ABI_VERSION == 9
+    assert L.slu_version() == lib.ABI_VERSION == 10
     assert isinstance(L.slu_last_error(), bytes)
 
 

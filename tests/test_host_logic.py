@@ -267,3 +267,67 @@ def test_data_plane_selection_without_a_gpu(monkeypatch):
         dp._typed_flats({torch.float16: torch.zeros(2, dtype=torch.float16)})
     a, b = torch.zeros(3), torch.zeros(2, dtype=torch.float64)
     assert dp._typed_flats({torch.float64: b, torch.float32: a}) == (a, b) and dp._typed_flats({}) == (None, None)
+
+
+def test_gru_weight_gradient_plan(monkeypatch):
+    """ops.gru_wgrad_plan: which launch computes a trainable GRU layer's weight gradients ("batched", "splitk" or
+    "forked") with which workgroup budget and branch mode.  The GRU layers at the benchmark's B = 64 x 3 s (600 SincNet
+    frames, max-pooled to 300, then Downsample(avg, 2) after every phoneme and word layer): phoneme 300 x 60 -> 150 x 256,
+    word 75 x 256 -> 38 x 256, intent 19 x 256; H = 128, bidirectional.  no_unfreezing trains the intent layer only,
+    asr_pretrain the phoneme and word layers, unfreeze_all all five.  The layers with at most TN_SMALL_ROWS rows (the second
+    word layer: 2432, the intent layer: 1216) take the batched launch in every arithmetic."""
+    from slu_hip import ops
+    for k in ("SLU_TRAIN_MATH", "SLU_DTYPE", "SLU_TN_SPLITK", "SLU_WGRAD_BRANCH", "SLU_WGRAD_WGS"):
+        monkeypatch.delenv(k, raising=False)
+
+    def plan(T, I=256, B=64, H=128, D=2, need_ih=True, need_hh=(True, True), aligned=True):
+        monkeypatch.setattr(ops, "_WGRAD", [None])         # re-read SLU_WGRAD_BRANCH / SLU_WGRAD_WGS
+        return ops.gru_wgrad_plan(T, B, I, H, D, need_ih, need_hh, aligned)
+
+    long_layers = [(300, 60), (150, 256), (75, 256)]                        # 19200, 9600, 4800 rows
+    assert plan(38) == plan(19) == ("batched", 0, "0")
+    for T, I in long_layers:                                                # exact fp32
+        assert plan(T, I) == ("splitk", 216, "layer")
+    for env in ("SLU_TRAIN_MATH", "bf16x3"), ("SLU_TRAIN_MATH", "split"), ("SLU_DTYPE", "bf16"):
+        monkeypatch.setenv(*env)
+        assert plan(38) == plan(19) == ("batched", 0, "0")                  # the batched launch is exact fp32 always
+        for T, I in long_layers:
+            assert plan(T, I) == ("forked", 0, "0")
+        monkeypatch.delenv(env[0])
+
+    # row bounds: batched up to TN_SMALL_ROWS inclusive, split-K from TN_SPLITK_MIN_ROWS inclusive
+    assert ops.TN_SMALL_ROWS == 4096 and ops.TN_SPLITK_MIN_ROWS == 2048
+    assert plan(64, B=64) == ("batched", 0, "0") and plan(4097, B=1) == ("splitk", 216, "layer")
+    assert plan(2047, B=1) == plan(2048, B=1) == ("batched", 0, "0")
+    with monkeypatch.context() as m:
+        m.setenv("SLU_TRAIN_MATH", "bf16x3")
+        assert plan(4096, B=1) == ("batched", 0, "0") and plan(4097, B=1) == ("forked", 0, "0")
+    with monkeypatch.context() as m:
+        m.setattr(ops, "TN_SMALL_ROWS", 1024)               # the split-K lower bound, below the batched one
+        assert plan(1024, B=1) == ("batched", 0, "0")
+        assert plan(2047, B=1) == ("forked", 0, "0") and plan(2048, B=1) == ("splitk", 216, "layer")
+
+    # shapes and gradients neither one-launch form takes
+    for T in (19, 300):
+        assert plan(1, B=T * 64) == ("forked", 0, "0")                      # T = 1: no h_{t-1}, zero dW_hh
+        assert plan(T, I=62) == ("forked", 0, "0")                          # I % 4 != 0
+        assert plan(T, H=126) == ("forked", 0, "0")                         # H % 4 != 0
+        assert plan(T, need_hh=(True, False)) == ("forked", 0, "0")         # one W_hh frozen
+        assert plan(T, need_ih=False) == ("forked", 0, "0")                 # W_ih frozen
+    assert plan(19, D=1, need_hh=(True,)) == ("batched", 0, "0")
+    assert plan(300, D=1, need_hh=(True,)) == ("splitk", 216, "layer")
+    assert plan(19, aligned=False) == ("batched", 0, "0")                   # the batched launch takes 12-byte loads too
+    assert plan(300, aligned=False) == ("forked", 0, "0")
+    monkeypatch.setenv("SLU_TN_SPLITK", "0")
+    assert plan(300, 60) == ("forked", 0, "0") and plan(19) == ("batched", 0, "0")
+    monkeypatch.delenv("SLU_TN_SPLITK")
+
+    # SLU_WGRAD_BRANCH / SLU_WGRAD_WGS: the budget and branch mode of the split-K launch (nothing else changes)
+    for mode, want in (("layer", (216, "layer")), ("pass", (216, "pass")), ("0", (0, "0"))):
+        monkeypatch.setenv("SLU_WGRAD_BRANCH", mode)
+        assert plan(300, 60) == ("splitk",) + want and plan(19) == ("batched", 0, "0")
+    monkeypatch.setenv("SLU_WGRAD_BRANCH", "layer")
+    monkeypatch.setenv("SLU_WGRAD_WGS", "144")
+    assert plan(150) == ("splitk", 144, "layer")
+    monkeypatch.setenv("SLU_WGRAD_WGS", "0")                 # no budget: in line, full round
+    assert plan(150) == ("splitk", 0, "0")
