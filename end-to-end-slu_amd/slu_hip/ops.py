@@ -88,7 +88,7 @@ class _Fork:
     _used = {}
 
     capture_forks = False     # set by pipeline.StepGraph while it captures a step with nothing running beside it
-    # Round 5: set by training.Trainer._iterate_full_steps for the steps of a FULLY trainable loop (nothing runs beside them):
+    # Round 5: set (defer_forks, below) by training.Trainer._iterate_full_steps for the steps of a FULLY trainable loop (nothing runs beside them):
     # the batched weight-gradient launch of a GRU layer with thousands of rows goes to an auxiliary stream / graph branch
     # (ops.wgrad_branch: joined at the end of the layer's backward, or — mode "pass" — left open until the trainer's single
     # join after loss.backward()).
@@ -130,6 +130,24 @@ class _Fork:
     # by more than the GEMMs' own time (the likely cause; the measurement is the fact); (2) it is not safe under autograd as is: AccumulateGrad CLONES a gradient it
     # cannot steal (a view of a stacked buffer, or a tensor someone else still references) on the main stream, i.e.
     # before the branch has written it.
+
+
+class defer_forks:
+    """with defer_forks(on): ...   _Fork.defer = on for the body (ONE optimisation step: never hold it across a yield of
+    a step loop); the previous value comes back on exit, also after an exception, so the scopes nest.  A plain class, and
+    one object may be entered again and again: a step loop makes it once and pays 0.3 us of host time per step (a
+    generator-based context manager: 1.5 us)."""
+    __slots__ = ("on", "was")
+
+    def __init__(self, on):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.was, _Fork.defer = _Fork.defer, self.on
+
+    def __exit__(self, *exc):
+        _Fork.defer = self.was
+        return False
 
 
 def _workspace(nbytes, device):

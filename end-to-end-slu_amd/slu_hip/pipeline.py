@@ -256,7 +256,7 @@ class PrefixSlot:
         for k, x in enumerate(xs):
             if x.dtype != x_cat.dtype:
                 # copy_ would CONVERT: float [-1, 1) samples into an int16 buffer are all zeros, int16 PCM into a float
-                # buffer is 32768 times too large — a super-batch holds one sample format (training.launch_next)
+                # buffer is 32768 times too large — a super-batch holds one sample format (training._Lookahead.read_group)
                 raise TypeError("look-ahead super-batch of %s batches received a %s batch" % (x_cat.dtype, x.dtype))
             x_cat[k * B:(k + 1) * B].copy_(x, non_blocking=True)
 

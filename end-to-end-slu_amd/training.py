@@ -24,8 +24,8 @@ import torch
 from tqdm import tqdm
 
 from data import SLUDataset, ASRDataset
-from models import PretrainedModel, Model
-from slu_hip import dp
+from models import PretrainedModel, Model, next_rng_step
+from slu_hip import dp, ops, pipeline
 
 
 def models_masks_injected():
@@ -39,9 +39,59 @@ def _lookahead_env():
     return -1 if v == "auto" else int(v)
 
 
+def _lookahead_slots():
+    """SLU_LOOKAHEAD_SLOTS: look-ahead super-batches in flight, at least 2; default 2."""
+    # two slots: one super-batch is consumed while the next is computed (a third slot only reads further ahead:
+    # 342 -> 323 k utt/s steady state, profiles/r05_a_sweep.txt)
+    return max(2, int(os.environ.get("SLU_LOOKAHEAD_SLOTS", "2")))
+
+
 def _max_step_graphs():
-    """Distinct step shapes kept as captured hipGraphs (each owns its activations: ~0.2 GB at B = 64)."""
+    """SLU_MAX_STEP_GRAPHS: distinct step shapes kept as captured hipGraphs (each owns its activations: ~0.2 GB at
+    B = 64); default 8."""
     return int(os.environ.get("SLU_MAX_STEP_GRAPHS", "8"))
+
+
+def _ramp_env():
+    """SLU_RAMP: "0" (default) = one capped first super-batch, "auto" = three side by side, "a,b,c" = explicit sizes
+    (_ramp_plan has the rule and the measurements)."""
+    return os.environ.get("SLU_RAMP", "0")
+
+
+def _ramp_side():
+    """SLU_RAMP_SIDE: explicit SLU_RAMP sizes started side by side — 1: all of them; k >= 2: the first k; default 0: none."""
+    return int(os.environ.get("SLU_RAMP_SIDE", "0"))
+
+
+def _ramp_whole_n():
+    """SLU_RAMP_WHOLE_N: of a ramp that starts side by side, how many first super-batches take the whole chip; default 0."""
+    return int(os.environ.get("SLU_RAMP_WHOLE_N", "0"))
+
+
+def _prefix_chain():
+    """SLU_PREFIX_CHAIN: "1" (default) = a super-batch waits for its predecessor; "0" = see below."""
+    # SLU_PREFIX_CHAIN=0 (experiment): super-batches of different slots never wait for each other
+    return os.environ.get("SLU_PREFIX_CHAIN", "1") != "0"
+
+
+def _host_wait():
+    """SLU_HOST_WAIT: "all" (default) | "first" | "0" — which look-ahead super-batches the host waits for."""
+    # The host WAITS for a super-batch before it enqueues that group's steps.  For the run's first one
+    # nothing can run before it anyway, and step graphs queued on the (high-priority) training stream
+    # behind its event slow the running super-batch down — measured, tools/diag_whole_chip.py,
+    # profiles/r06_y_first_super_batch.txt: 13 batches on the whole chip 2.7 - 3.0 ms with the steps
+    # queued, 2.3 ms with the host waiting.  In steady state the super-batch is normally through when the
+    # previous group's steps are (the prefix bounds the loop), so the wait is short; it keeps the host
+    # at most one group ahead and is worth 0.5 % there (363.2 - 365.0 -> 365.8 - 367.2 k utt/s,
+    # profiles/r06_y_host_wait_all.txt).  "first": only the run's first super-batch.  (Queuing the
+    # group's first 1 / 2 / 4 steps BEFORE the wait, to hide the host's wake-up: 227 / 228 / 226 k
+    # against 230 k utt/s for the 20-step command — not kept.)
+    return os.environ.get("SLU_HOST_WAIT", "all")
+
+
+def _graph_forks():
+    """SLU_GRAPH_FORKS: "1" (default) = the steps of a loop with nothing beside them raise ops._Fork.defer; "0" = never."""
+    return os.environ.get("SLU_GRAPH_FORKS", "1") != "0"
 
 
 def _param_signature(model):
@@ -58,7 +108,6 @@ def _lookahead_width(depth, batch_size):
     a wider first super-batch is a longer pipeline fill."""
     if depth > 0:
         return depth
-    from slu_hip import pipeline
     cus = 256
     if torch.cuda.is_available():
         cus = pipeline.n_compute_units(torch.cuda.current_device()) - pipeline.cu_split()
@@ -83,10 +132,10 @@ def _ramp_plan(n_run, width, n_slots, latency_steps=5.0, slope=0.4):
     SLU_RAMP=a,b,c: explicit sizes, one behind the other (SLU_RAMP_SIDE=1 with as many look-ahead slots: side by side — measured
     slower, profiles/r05_a_sweep.txt: CU-masked streams have no priorities, super-batches side by side share the partition and
     ALL finish late)."""
-    env = os.environ.get("SLU_RAMP", "0")
+    env = _ramp_env()
     if env not in ("auto", "0"):
         sizes = [max(1, int(v)) for v in env.split(",") if v.strip()]
-        k = int(os.environ.get("SLU_RAMP_SIDE", "0"))           # 1: all of them side by side; k >= 2: the first k
+        k = _ramp_side()                                        # 1: all of them side by side; k >= 2: the first k
         side = min(len(sizes), n_slots) if k == 1 and n_slots >= len(sizes) else (min(k, len(sizes), n_slots) if k >= 2 else 0)
         return sizes, side
     T = min(n_run, width)
@@ -97,6 +146,99 @@ def _ramp_plan(n_run, width, n_slots, latency_steps=5.0, slope=0.4):
     a = max(2, int(T / 7.0 + 0.5))
     b = max(a, int(2 * T / 7.0 + 0.5))
     return [a, b, T - a - b], 3
+
+
+def _same_form(batch, first):
+    """Do the waveforms of `batch` have the shape and the sample format (float32 or PCM16) of the group's first batch?"""
+    return tuple(batch[0].shape) == tuple(first[0].shape) and batch[0].dtype == first[0].dtype
+
+
+def _input_version(batch):
+    return batch[0]._version if batch[0].is_cuda else None
+
+
+# a look-ahead super-batch in flight: the batches, their concatenated prefix features, the event recorded behind them, the
+# batches' dropout-stream indices, the PrefixSlot that ran it, the input tensors' versions WHEN THEY WERE READ, the range guard
+_SuperBatch = collections.namedtuple("_SuperBatch", "group feats done steps slot versions guard")
+
+
+class _Lookahead:
+    """The reading side of one look-ahead run (Trainer._iterate_lookahead): takes groups of equally-shaped batches off the
+    loader — the first ones sized by _ramp_plan (pipeline fill) — and starts each group's frozen prefix as one super-batch
+    on the next PrefixSlot.  Nothing here touches the device before start_next() calls slot.run."""
+
+    def __init__(self, model, slots, loader, depth, n_prefix):
+        self.model, self.slots, self.depth, self.n_prefix = model, slots, depth, n_prefix
+        try:
+            self.n_run = len(loader)
+        except TypeError:
+            self.n_run = 1 << 30
+        self.it = iter(loader)
+        self.carry = []                               # a batch read ahead that did not fit its group
+        self.launched = 0                             # groups taken off the loader so far
+        self.sizes, self.side = [], 0                 # _ramp_plan: sizes of the first super-batches, how many start side by side
+        self.last_done = None                         # the `done` event of the super-batch started last
+        self.pending = collections.deque()            # _SuperBatch in flight, in reading order
+        self.use_graph = pipeline.graphs_enabled()
+        self.chain = _prefix_chain()
+        self.whole_n = _ramp_whole_n()
+        # several ranks on ONE GPU (the --share-gpu / SLU_LOCAL_DEVICE test set-up): a whole-chip super-batch of one process
+        # would run over the other processes' training partitions (measured: 4 ranks 185 -> 83 k utt/s)
+        self.own_gpu = not dp._shared_device()
+
+    def width(self, batch_size):
+        """Batches in the group that is read next.  The ramp is planned at the first call, from the first group's batch size."""
+        w = _lookahead_width(self.depth, batch_size)
+        if self.launched == 0:
+            self.sizes, self.side = _ramp_plan(self.n_run, w, len(self.slots))
+        return min(self.sizes[self.launched], w) if self.launched < len(self.sizes) else w
+
+    def read_group(self):
+        """-> (up to width() equally-shaped batches in loader order, their input versions); ([], []) at the end of the loader."""
+        group = [self.carry.pop()] if self.carry else []
+        versions = [_input_version(b) for b in group]      # tensor version of every batch WHEN IT WAS READ
+        width = self.width(len(group[0][0])) if group else 0
+        while not group or len(group) < width:
+            try:
+                batch = next(self.it)
+            except StopIteration:
+                break
+            if not group:
+                width = self.width(len(batch[0]))
+            elif not _same_form(batch, group[0]):
+                self.carry.append(batch)         # a super-batch holds ONE shape and ONE sample format (float32 or PCM16)
+                break
+            group.append(batch)
+            versions.append(_input_version(batch))
+        if group:
+            self.launched += 1
+        return group, versions
+
+    def start_next(self):
+        """Read up to `depth` equally-shaped batches and start their frozen prefix as one super-batch."""
+        group, versions = self.read_group()
+        if not group:
+            return False
+        n = self.launched                                               # this super-batch is the n-th of the run
+        slot = self.slots[(n - 1) % len(self.slots)]
+        steps = [next_rng_step() for _ in group]                        # consecutive by construction
+        # whole_chip: the capped first super-batch of a SHORT run (one that _ramp_plan splits: fewer than two full
+        # super-batches, e.g. the driver's 20 steps) is replayed on the whole chip — the training partition has
+        # nothing to do until it is through, and in a short run that wait is a large share of the run (14 batches:
+        # 2.6 -> 2.3 ms).  Decided by the run's length alone, not by stream.query(): which captured graph a run uses
+        # must not be a race.  Long runs keep every super-batch on the look-ahead partition (one key per slot).
+        # the first `side` super-batches of the run start side by side; from then on each waits for its predecessor
+        # (two full-width super-batches side by side would only delay the one the training stream is waiting for)
+        feats, done, guard = slot.run(self.model, [b[0] for b in group], self.n_prefix, steps[0], self.use_graph,
+                                      after=None if (n <= self.side or not self.chain) else self.last_done,
+                                      whole_chip=(self.own_gpu and bool(self.sizes)
+                                                  and n <= (1 if self.side == 0 else self.whole_n)))
+        self.last_done = done
+        # device-resident batches are read IN PLACE by the (asynchronous) super-batch: remember their tensor
+        # versions, so that a loader that recycles its device buffers is caught instead of silently training on
+        # whatever the buffer holds by then (INTEGRATION.md: batches must stay unchanged until consumed)
+        self.pending.append(_SuperBatch(group, feats, done, steps, slot, versions, guard))
+        return True
 
 
 class Trainer:
@@ -111,10 +253,9 @@ class Trainer:
             self.checkpoint_path = os.path.join(self.config.folder, "training")
         # same optimiser and defaults as the reference (training.py:19); on a GPU the update runs as one
         # launch per dtype on the HIP kernel (slu_hip/optim.py: same rule and per-parameter step counts)
-        on_gpu = all(p.is_cuda for p in model.parameters())
+        on_gpu = self._on_gpu()
         if on_gpu:
-            from slu_hip import ops as _ops
-            self.wgrad = _ops.resolve_wgrad()      # (mode, workgroup budget) of the weight-gradient launches, fixed for this trainer
+            self.wgrad = ops.resolve_wgrad()       # (mode, workgroup budget) of the weight-gradient launches, fixed for this trainer
             from slu_hip.optim import HipAdam
             self.optimizer = HipAdam(model.parameters(), lr=self.lr)
         else:
@@ -126,7 +267,7 @@ class Trainer:
         # GPU) what gives the gradients fixed addresses for hipGraph-captured steps
         self.data_parallel = dp.data_parallel()      # world size > 1 (or the one-rank test mode SLU_DP_SINGLE=1)
         self.bucket = dp.GradBucket(model.parameters()) if (self.data_parallel or on_gpu) else None
-        self._step_graphs, self._eager_steps = {}, {}
+        self._step_graphs, self._eager_steps, self._last_key = {}, {}, None
         self.capture_failures = 0
         self._hip_adam = on_gpu
         if on_gpu and self.data_parallel:
@@ -175,7 +316,6 @@ class Trainer:
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward()
         if loss.is_cuda:
-            from slu_hip import ops
             ops._Fork.join(loss.device)          # branches left open by the backward pass (ops._Fork.defer): one join
         if self.bucket is not None:
             self.bucket.allreduce_mean()
@@ -230,6 +370,10 @@ class Trainer:
             self._plist = (self.model, list(self.model.parameters()))
         return self._plist[1]
 
+    def _on_gpu(self):
+        """Are all parameters on a GPU?  (asked live: a model may be moved after the trainer was built)"""
+        return all(p.is_cuda for p in self._parameters())
+
     def lookahead_depth(self, train, asr):
         """How many batches ahead the FROZEN prefix of the encoder is evaluated on side HIP streams
         (0 = plain sequential steps).  Only SLU training with a frozen prefix qualifies: a frozen
@@ -241,7 +385,7 @@ class Trainer:
         depth = _lookahead_env()
         if not train or asr or depth in (0, 1) or not hasattr(self.model, "prefix_features"):
             return 0, 0
-        if not all(p.is_cuda for p in self._parameters()) or models_masks_injected():
+        if not self._on_gpu() or models_masks_injected():
             return 0, 0
         n = self.model.frozen_prefix_len()
         # a CNN-block dropout inside the frozen prefix has no per-sub-batch stream (all shipped cfgs have
@@ -255,9 +399,8 @@ class Trainer:
     def _graphable(self):
         """Captured steps need the HIP optimiser (device-resident step counters), fixed gradient addresses
         (the bucket) and the in-kernel Philox dropout (injected masks change per call)."""
-        from slu_hip import pipeline
         return (pipeline.graphs_enabled() and self.bucket is not None and self._hip_adam
-                and not models_masks_injected() and all(p.is_cuda for p in self.model.parameters()))
+                and not models_masks_injected() and self._on_gpu())
 
     def graph_stats(self):
         """{"step_graphs": captured optimisation steps, "prefix_graphs": captured look-ahead super-batch
@@ -274,30 +417,46 @@ class Trainer:
                                  "eager call between two hipGraphs")
         return out
 
+    def _captured_step(self, key, inputs, forward, stream, forks, guard):
+        """The StepGraph of `key`, captured now if three eager steps of that key have run; None: the step runs eagerly."""
+        sg = self._step_graphs.get(key)
+        if sg is not None:
+            self._step_graphs[key] = self._step_graphs.pop(key)          # most recently used last
+            if sg.signature == self.bucket.signature:
+                return sg                               # (else: trainable set changed since capture)
+        if self._eager_steps.get(key, 0) < 3 or not self.bucket.active:
+            return None
+        if key not in self._step_graphs and len(self._step_graphs) >= _max_step_graphs():
+            self._step_graphs.pop(next(iter(self._step_graphs)))         # evict the LEAST RECENTLY USED capture
+        try:
+            sg = self._step_graphs[key] = pipeline.StepGraph(self, inputs, forward, stream, forks, guard)
+            return sg
+        except RuntimeError as e:                       # keep training eagerly if capture fails
+            print("hipGraph capture of the training step failed (%s); staying eager" % (e,))
+            self._eager_steps[key] = -(1 << 30)
+            self._step_graphs.pop(key, None)
+            self.capture_failures += 1
+            return None
+
+    def _count_eager_step(self, key):
+        """An eager step of `key` is about to run: count it towards that key's capture (_captured_step)."""
+        # only runs of equally-shaped steps are worth a capture (~50 ms, a private activation pool): with ragged
+        # batches (real-data loaders without length bucketing) the count restarts at every shape change
+        if self._last_key != key and self._eager_steps.get(key, 0) >= 0:
+            self._eager_steps[key] = 0
+        self._last_key = key
+        self._eager_steps[key] = self._eager_steps.get(key, 0) + 1
+        if len(self._eager_steps) > 256:                # ragged real-data shapes: keep the table bounded
+            self._eager_steps = {k: v for k, v in self._eager_steps.items() if v < 0 or k == key or k in self._step_graphs}
+
     def _graph_step(self, key, inputs, step, forward, stream, forks=False, guard=None):
         """One optimisation step on `inputs` (device tensors): replay of the hipGraph captured for `key`
         (captured after three eager steps of that key), else eagerly.  -> metrics (tensor or list).
         guard: the step evaluates FROZEN stages on guarded f16x2 (pipeline.StepGraph): a violation repeats the step
         eagerly — where the model's own guard re-runs the frozen stages on bf16x3 — before the optimiser has run."""
-        from slu_hip import pipeline
         if guard is not None:
             key = key + ("guarded",)
-        sg = self._step_graphs.get(key)
-        if sg is not None:
-            self._step_graphs[key] = self._step_graphs.pop(key)          # most recently used last
-        if sg is not None and sg.signature != self.bucket.signature:
-            sg = None                                   # trainable set changed since capture
-        if sg is None and self._eager_steps.get(key, 0) >= 3 and self.bucket.active:
-            if key not in self._step_graphs and len(self._step_graphs) >= _max_step_graphs():
-                self._step_graphs.pop(next(iter(self._step_graphs)))     # evict the LEAST RECENTLY USED capture
-            try:
-                sg = pipeline.StepGraph(self, inputs, forward, stream, forks, guard)
-                self._step_graphs[key] = sg
-            except RuntimeError as e:                   # keep training eagerly if capture fails
-                print("hipGraph capture of the training step failed (%s); staying eager" % (e,))
-                self._eager_steps[key] = -(1 << 30)
-                self._step_graphs.pop(key, None)
-                self.capture_failures += 1
+        sg = self._captured_step(key, inputs, forward, stream, forks, guard)
         if sg is not None:
             self._last_key = key
             try:
@@ -309,19 +468,9 @@ class Trainer:
                                   % max(trip.seen))
                 self._step_graphs.pop(key, None)
                 self._eager_steps[key] = 0
-                self.bucket.release_grads()
-                metrics, loss = forward(inputs, step)          # eager: run_stages' own guard / pin decides the arithmetic
-                self._step(loss)
-                return metrics
-        # only runs of equally-shaped steps are worth a capture (~50 ms, a private activation pool): with ragged
-        # batches (real-data loaders without length bucketing) the count restarts at every shape change
-        if getattr(self, "_last_key", None) != key and self._eager_steps.get(key, 0) >= 0:
-            self._eager_steps[key] = 0
-        self._last_key = key
-        self._eager_steps[key] = self._eager_steps.get(key, 0) + 1
-        if len(self._eager_steps) > 256:                # ragged real-data shapes: keep the table bounded
-            keep = {k: v for k, v in self._eager_steps.items() if v < 0 or k == key or k in self._step_graphs}
-            self._eager_steps = keep
+                self.bucket.release_grads()             # eager: run_stages' own guard / pin decides the arithmetic
+        else:
+            self._count_eager_step(key)
         metrics, loss = forward(inputs, step)
         self._step(loss)
         return metrics
@@ -329,8 +478,6 @@ class Trainer:
     def _slu_forward(self, n_prefix, sums=None):
         """sums: float64 device tensor the intent head's own launch adds B * (loss, acc) to (the epoch statistics
         of reference training.py:100-104), so that the loop needs no accumulation kernel per step."""
-        from slu_hip import ops
-
         def forward(ins, rng):
             ops.IntentHeadFn.epoch_sums = sums
             try:
@@ -373,7 +520,6 @@ class Trainer:
         """Training with nothing to look ahead to (ASR pre-training, SLU with an unfrozen first layer or
         SLU_LOOKAHEAD=0): each step is ~100 short launches, so fixed-shape steps are captured as hipGraphs
         (StepGraph) on a dedicated stream; the losses and parameters are those of the eager loop."""
-        from models import next_rng_step
         dev = next(self.model.parameters()).device
         outer = torch.cuda.current_stream()
         if getattr(self, "_full_stream", None) is None:
@@ -397,11 +543,10 @@ class Trainer:
             if pm is None or not any(not any(q.requires_grad for q in st.parameters()) for st in pm._stages()):
                 return None
             return pm.range_guard() if pm.f16x2_allowed() else None
-        from slu_hip import ops as _ops
-        was_defer = _ops._Fork.defer
         # nothing runs beside these steps: the weight-gradient launches of long GRU layers go to a graph branch
         # (ops.GRULayerFn.backward, ops.wgrad_branch); the flag is raised per step, never across a yield
-        defer = os.environ.get("SLU_GRAPH_FORKS", "1") != "0"
+        defer = _graph_forks()
+        deferring = ops.defer_forks(defer)
         try:
             with torch.cuda.stream(main):
                 pm.warm_weight_caches()
@@ -413,101 +558,65 @@ class Trainer:
                     fused_now = fused and guard is None
                     fwd = forward if (fused_now or not fused) else forward_plain
                     key = ("full", asr, trainable, fused_now) + tuple((tuple(t.shape), t.dtype) for t in ins)
-                    _ops._Fork.defer = defer
-                    try:
+                    with deferring:
                         vals = self._graph_step(key, ins, next_rng_step(), fwd, main, forks=defer, guard=guard)
-                    finally:
-                        _ops._Fork.defer = was_defer
                     if sums is not None and not fused_now:
                         self._accumulate(sums, vals, len(batch[0]))
                     yield vals, len(batch[0])
         finally:
-            _ops._Fork.defer = was_defer
             outer.wait_stream(main)
 
-    def _iterate(self, loader, train, asr, accumulate=False):
-        """Yields ([metric tensors], batch_size) per batch, doing the optimisation step when `train`.
-        NOTE for consumers: the metrics of a hipGraph-captured step are ONE static device buffer that the next replay
-        overwrites — read (or .clone()) them before advancing the generator, as _run does at print intervals.
-        accumulate: also keep the epoch statistics on the device — self.epoch_sums[:n] (float64, zeroed here)
-        receives batch_size * metrics of every batch, inside the step's own kernels where they are captured
-        (no per-step accumulation launch); the consumer reads it when the generator is exhausted."""
-        sums = None
-        if accumulate:
-            sums = self._sums_buffer()
-            sums.zero_()
-        depth, n_prefix = self.lookahead_depth(train, asr)
-        group_eval = (not train and not asr and hasattr(self.model, "eval_group") and not models_masks_injected()
-                      and not getattr(self.model, "seq2seq", False)
-                      and all(p.is_cuda for p in self.model.parameters())
-                      and _lookahead_env() not in (0, 1))
-        if group_eval:
-            # evaluation has no step-to-step dependency at all: whole batches are grouped
-            group = []
+    def _eval_group(self, group, sums):
+        res = self.model.eval_group([b[0] for b in group], [b[1] for b in group])
+        out = [([l, a], len(b[0])) for (l, a), b in zip(res, group)]
+        if sums is not None:
+            for vals, bs in out:
+                self._accumulate(sums, vals, bs)
+        return out
 
-            def flush():
-                res = self.model.eval_group([b[0] for b in group], [b[1] for b in group])
-                out = [([l, a], len(b[0])) for (l, a), b in zip(res, group)]
-                if sums is not None:
-                    for vals, bs in out:
-                        self._accumulate(sums, vals, bs)
-                group.clear()
-                return out
+    def _iterate_eval_groups(self, loader, sums=None):
+        """Evaluation has no step-to-step dependency at all: whole batches are grouped (model.eval_group), as many of one
+        shape as a look-ahead super-batch holds."""
+        depth = _lookahead_env()
+        group = []
+        for batch in loader:
+            if group and (not _same_form(batch, group[0]) or len(group) == _lookahead_width(depth, len(group[0][0]))):
+                yield from self._eval_group(group, sums)
+                group = []
+            group.append(batch)
+        if group:
+            yield from self._eval_group(group, sums)
 
-            for batch in loader:
-                if group and (tuple(batch[0].shape) != tuple(group[0][0].shape) or batch[0].dtype != group[0][0].dtype
-                              or len(group) == _lookahead_width(_lookahead_env(), len(group[0][0]))):
-                    yield from flush()
-                group.append(batch)
-            if group:
-                yield from flush()
-            return
-        if depth == 0:
-            if train and self._graphable():
-                yield from self._iterate_full_steps(loader, asr, sums)
-                return
-            # the same arithmetic as the captured loop (the weight-gradient branch of long GRU layers and its workgroup
-            # budget, ops.wgrad_branch): SLU_GRAPHS=0 and =1 stay bit-identical
-            from slu_hip import ops as _ops
-            was_defer = _ops._Fork.defer
-            on_gpu = train and all(p.is_cuda for p in self.model.parameters())
-            try:
-                for batch in loader:
-                    _ops._Fork.defer = on_gpu and os.environ.get("SLU_GRAPH_FORKS", "1") != "0"
-                    try:
-                        with torch.set_grad_enabled(train):
-                            vals, loss = self._forward_losses(batch, asr)
-                            if train:
-                                self._step(loss)
-                    finally:
-                        _ops._Fork.defer = was_defer
-                    if sums is not None:
-                        self._accumulate(sums, vals, len(batch[0]))
-                    yield vals, len(batch[0])
-            finally:
-                _ops._Fork.defer = was_defer
-            return
-        # ---- encoder look-ahead pipeline (slu_hip/pipeline.py) --------------------------------------
-        import collections
-        from models import next_rng_step
-        from slu_hip import pipeline
+    def _iterate_eager(self, loader, train, asr, sums=None):
+        """The plain loop: evaluation, the CPU, injected dropout masks, SLU_GRAPHS=0."""
+        # the same arithmetic as the captured loop (the weight-gradient branch of long GRU layers and its workgroup
+        # budget, ops.wgrad_branch): SLU_GRAPHS=0 and =1 stay bit-identical
+        deferring = ops.defer_forks(train and self._on_gpu() and _graph_forks())
+        for batch in loader:
+            with deferring, torch.set_grad_enabled(train):                      # per step, never across a yield
+                vals, loss = self._forward_losses(batch, asr)
+                if train:
+                    self._step(loss)
+            if sums is not None:
+                self._accumulate(sums, vals, len(batch[0]))
+            yield vals, len(batch[0])
+
+    def _iterate_lookahead(self, loader, depth, n_prefix, sums=None):
+        """The encoder look-ahead pipeline (slu_hip/pipeline.py): the frozen prefix of the NEXT group of batches runs as one
+        super-batch on a side stream (_Lookahead) while the training stream does the current group's optimisation steps."""
         # The trainable part runs on a dedicated non-default stream: autograd pins each parameter's
         # gradient-accumulation node to the stream of its first use, and hipGraph capture (which cannot
         # happen on the default stream) needs the eager warm-up steps and the capture to agree on it.
         outer = torch.cuda.current_stream()
         dev = next(self.model.parameters()).device
         if getattr(self, "_train_stream", None) is None:
-            from slu_hip import pipeline as _pl
-            n_cu = _pl.cu_split()
-            self._train_stream = (_pl.cu_range_stream(dev, 0, n_cu, priority=-1) if n_cu > 0
+            n_cu = pipeline.cu_split()
+            self._train_stream = (pipeline.cu_range_stream(dev, 0, n_cu, priority=-1) if n_cu > 0
                                   else torch.cuda.Stream(dev, priority=-1))     # ahead of the look-ahead streams
         main = self._train_stream
         main.wait_stream(outer)
         if getattr(self, "_slots", None) is None:
-            # two slots: one super-batch is consumed while the next is computed (a third slot only reads further ahead:
-            # 342 -> 323 k utt/s steady state, profiles/r05_a_sweep.txt)
-            n_slots = max(2, int(os.environ.get("SLU_LOOKAHEAD_SLOTS", "2")))
-            self._slots = [pipeline.PrefixSlot(dev) for _ in range(n_slots)]   # in-flight super-batches
+            self._slots = [pipeline.PrefixSlot(dev) for _ in range(_lookahead_slots())]   # in-flight super-batches
         pm = self.model.pretrained_model
         with torch.cuda.stream(main):
             pm.warm_weight_caches()
@@ -517,123 +626,49 @@ class Trainer:
                 slot.invalidate()
                 slot.signature = signature
             slot.stream.wait_stream(main)
-        use_graph = pipeline.graphs_enabled()
         # (what the optimisation steps need — step graphs, the forward closure, the parameter signature — is set up AFTER
         # the first super-batches are on their way, below: the device is idle until the first of them is enqueued, and
         # ~0.15 ms of host work in front of it was ~2 % of a 20-step run)
         # the first super-batches of a run are sized and started by _ramp_plan (pipeline fill)
-        try:
-            n_run = len(loader)
-        except TypeError:
-            n_run = 1 << 30
-        pending = collections.deque()
-        it = iter(loader)
-        carry = []                                    # a batch read ahead that did not fit its group
-        launched = 0
-        last_done = [None]
-        ramp = [[], 0]                                # [sizes of the first super-batches, how many start side by side]
-        # SLU_PREFIX_CHAIN=0 (experiment): super-batches of different slots never wait for each other
-        chain = os.environ.get("SLU_PREFIX_CHAIN", "1") != "0"
-        # several ranks on ONE GPU (the --share-gpu / SLU_LOCAL_DEVICE test set-up): a whole-chip super-batch of one process
-        # would run over the other processes' training partitions (measured: 4 ranks 185 -> 83 k utt/s)
-        own_gpu = not dp._shared_device()
-
-        def launch_next():
-            """Read up to `depth` equally-shaped batches and start their frozen prefix as one super-batch."""
-            nonlocal launched
-            group = [carry.pop()] if carry else []
-            ver = lambda b: b[0]._version if b[0].is_cuda else None
-            versions = [ver(b) for b in group]                 # tensor version of every batch WHEN IT WAS READ
-            wcache = {}
-
-            def width():
-                bs = len(group[0][0])
-                if bs not in wcache:
-                    w = _lookahead_width(depth, bs)
-                    if launched == 0:
-                        ramp[0], ramp[1] = _ramp_plan(n_run, w, len(self._slots))
-                    wcache[bs] = min(ramp[0][launched], w) if launched < len(ramp[0]) else w
-                return wcache[bs]
-            while not group or len(group) < width():
-                try:
-                    batch = next(it)
-                except StopIteration:
-                    break
-                if group and (tuple(batch[0].shape) != tuple(group[0][0].shape) or batch[0].dtype != group[0][0].dtype):
-                    carry.append(batch)          # a super-batch holds ONE shape and ONE sample format (float32 or PCM16)
-                    break
-                group.append(batch)
-                versions.append(ver(batch))
-            if not group:
-                return False
-            slot = self._slots[launched % len(self._slots)]
-            launched += 1
-            steps = [next_rng_step() for _ in group]                        # consecutive by construction
-            # whole_chip: the capped first super-batch of a SHORT run (one that _ramp_plan splits: fewer than two full
-            # super-batches, e.g. the driver's 20 steps) is replayed on the whole chip — the training partition has
-            # nothing to do until it is through, and in a short run that wait is a large share of the run (14 batches:
-            # 2.6 -> 2.3 ms).  Decided by the run's length alone, not by stream.query(): which captured graph a run uses
-            # must not be a race.  Long runs keep every super-batch on the look-ahead partition (one key per slot).
-            # the first ramp[1] super-batches of the run start side by side; from then on each waits for its predecessor
-            # (two full-width super-batches side by side would only delay the one the training stream is waiting for)
-            feats, done, guard = slot.run(self.model, [b[0] for b in group], n_prefix, steps[0], use_graph,
-                                          after=None if (launched <= ramp[1] or not chain) else last_done[0],
-                                          whole_chip=(own_gpu and bool(ramp[0])
-                                                      and launched <= (1 if ramp[1] == 0 else int(os.environ.get("SLU_RAMP_WHOLE_N", "0")))))
-            last_done[0] = done
-            # device-resident batches are read IN PLACE by the (asynchronous) super-batch: remember their tensor
-            # versions, so that a loader that recycles its device buffers is caught instead of silently training on
-            # whatever the buffer holds by then (INTEGRATION.md: batches must stay unchanged until consumed)
-            pending.append((group, feats, done, steps, slot, versions, guard))
-            return True
-
+        ahead = _Lookahead(self.model, self._slots, loader, depth, n_prefix)
         # The consumer's per-step work (metric accumulation in _run) runs with `main` as the current
         # stream: ordered after the step without touching the default stream, whose legacy
         # synchronisation with blocking streams (the CU-masked ones) would serialise the pipeline.
         try:
             with torch.cuda.stream(main):
-                launch_next()
-                step_graphs = use_graph and self._graphable()
+                ahead.start_next()
+                step_graphs = ahead.use_graph and self._graphable()
                 fused = step_graphs and self._fused_sums()
                 forward = self._slu_forward(n_prefix, sums if fused else None)
                 trainable = _param_signature(self.model)
                 for _ in self._slots[1:]:
-                    launch_next()
-                host_wait = os.environ.get("SLU_HOST_WAIT", "all")          # "all" | "first" | "0"
-                while pending:
-                    group, feats_cat, done, steps, slot, versions, guard = pending.popleft()
-                    for b, v in zip(group, versions):
+                    ahead.start_next()
+                host_wait = _host_wait()
+                while ahead.pending:
+                    sb = ahead.pending.popleft()
+                    group, feats_cat, done, steps = sb.group, sb.feats, sb.done, sb.steps
+                    for b, v in zip(group, sb.versions):
                         if v is not None and b[0]._version != v:
                             raise RuntimeError(
                                 "a device-resident input batch was modified in place while its look-ahead super-batch was "
                                 "still reading it (the loader recycles device buffers): hand over fresh tensors per batch or "
                                 "host batches, or set SLU_LOOKAHEAD=0")
                     if host_wait != "0":
-                        # The host WAITS for a super-batch before it enqueues that group's steps.  For the run's first one
-                        # nothing can run before it anyway, and step graphs queued on the (high-priority) training stream
-                        # behind its event slow the running super-batch down — measured, tools/diag_whole_chip.py,
-                        # profiles/r06_y_first_super_batch.txt: 13 batches on the whole chip 2.7 - 3.0 ms with the steps
-                        # queued, 2.3 ms with the host waiting.  In steady state the super-batch is normally through when the
-                        # previous group's steps are (the prefix bounds the loop), so the wait is short; it keeps the host
-                        # at most one group ahead and is worth 0.5 % there (363.2 - 365.0 -> 365.8 - 367.2 k utt/s,
-                        # profiles/r06_y_host_wait_all.txt).  "first": only the run's first super-batch.  (Queuing the
-                        # group's first 1 / 2 / 4 steps BEFORE the wait, to hide the host's wake-up: 227 / 228 / 226 k
-                        # against 230 k utt/s for the 20-step command — not kept.)
-                        done.synchronize()
+                        done.synchronize()                      # (_host_wait has the measurements)
                         if host_wait == "first":
                             host_wait = "0"
-                    if guard is not None:
+                    if sb.guard is not None:
                         # f16x2 ran under the slot's range guard: read its words BEFORE the features are used (the
                         # super-batch normally finished while the previous group's steps were running: the wait is short
                         # and the training stream still has that group's tail to run)
                         done.synchronize()
-                        overflow, quiet, seen = guard.verdict()
+                        overflow, quiet, seen = sb.guard.verdict()
                         if overflow or quiet:
                             if overflow:
                                 pm.pin_bf16x3("a split-precision stage of a look-ahead super-batch saw |value| = %.3g "
                                               "(limit 65504)" % max(seen))
-                            feats_cat, done, _ = slot.run(self.model, [b[0] for b in group], n_prefix, steps[0],
-                                                          use_graph, after=None, guarded=False)
+                            feats_cat, done, _ = sb.slot.run(self.model, [b[0] for b in group], n_prefix, steps[0],
+                                                             ahead.use_graph, after=None, guarded=False)
                     B = group[0][0].shape[0]
                     for k, batch in enumerate(group):
                         if k == 0:
@@ -651,12 +686,40 @@ class Trainer:
                         if sums is not None and not fused:
                             self._accumulate(sums, vals, len(batch[0]))
                         if k == len(group) - 1:
-                            slot.consumed = torch.cuda.Event()
-                            slot.consumed.record(main)
-                            launch_next()
+                            sb.slot.consumed = torch.cuda.Event()       # after the group's last step, before the next launch
+                            sb.slot.consumed.record(main)
+                            ahead.start_next()
                         yield vals, len(batch[0])
         finally:
             outer.wait_stream(main)
+
+    def _iterate(self, loader, train, asr, accumulate=False):
+        """Yields ([metric tensors], batch_size) per batch, doing the optimisation step when `train`.
+        NOTE for consumers: the metrics of a hipGraph-captured step are ONE static device buffer that the next replay
+        overwrites — read (or .clone()) them before advancing the generator, as _run does at print intervals.
+        accumulate: also keep the epoch statistics on the device — self.epoch_sums[:n] (float64, zeroed here)
+        receives batch_size * metrics of every batch, inside the step's own kernels where they are captured
+        (no per-step accumulation launch); the consumer reads it when the generator is exhausted.
+        The loops that train on a GPU yield with THEIR stream as the current one and give the caller's back in their
+        own `finally` (contextlib.closing in _run restores it on an early exit)."""
+        sums = None
+        if accumulate:
+            sums = self._sums_buffer()
+            sums.zero_()
+        depth, n_prefix = self.lookahead_depth(train, asr)
+        group_eval = (not train and not asr and hasattr(self.model, "eval_group") and not models_masks_injected()
+                      and not getattr(self.model, "seq2seq", False)
+                      and self._on_gpu()
+                      and _lookahead_env() not in (0, 1))
+        if group_eval:
+            yield from self._iterate_eval_groups(loader, sums)
+        elif depth == 0:
+            if train and self._graphable():
+                yield from self._iterate_full_steps(loader, asr, sums)
+            else:
+                yield from self._iterate_eager(loader, train, asr, sums)
+        else:
+            yield from self._iterate_lookahead(loader, depth, n_prefix, sums)
 
     def _run(self, dataset, train, print_interval):
         asr = self._is_asr(dataset)

@@ -331,3 +331,142 @@ def test_gru_weight_gradient_plan(monkeypatch):
     assert plan(150) == ("splitk", 144, "layer")
     monkeypatch.setenv("SLU_WGRAD_WGS", "0")                 # no budget: in line, full round
     assert plan(150) == ("splitk", 0, "0")
+
+
+def _cpu_batch(x):
+    return (x, torch.zeros(len(x), 3, dtype=torch.long))
+
+
+def test_lookahead_reader_groups_batches_of_one_shape_and_format(monkeypatch):
+    """training._Lookahead.read_group: a group holds up to width() batches of ONE waveform shape and sample format; a
+    batch that does not fit is carried into the next group — none lost, loader order kept.  No device is touched."""
+    import training
+    for k in ("SLU_RAMP", "SLU_RAMP_SIDE"):
+        monkeypatch.delenv(k, raising=False)
+    for odd in (torch.zeros(4, 120), torch.zeros(4, 100, dtype=torch.int16)):        # another length / PCM16 samples
+        batches = [_cpu_batch(torch.zeros(4, 100)) for _ in range(5)]
+        batches[2] = _cpu_batch(odd)
+        ahead = training._Lookahead(None, [None, None], (b for b in batches), 3, 7)      # no len(): no ramp, width 3
+        groups = [ahead.read_group() for _ in range(4)]
+        assert [len(g) for g, _ in groups] == [2, 1, 2, 0]
+        assert [id(b) for g, _ in groups for b in g] == [id(b) for b in batches]
+        assert all(versions == [None] * len(g) for g, versions in groups)            # host batches carry no version
+        assert ahead.launched == 3 and not ahead.carry and (ahead.sizes, ahead.side) == ([], 0)
+    # a full group ends at the width, and a carried batch alone fills a group of width 1 without reading further
+    monkeypatch.setenv("SLU_RAMP", "2,1,1")
+    batches = [_cpu_batch(torch.zeros(4, 100)), _cpu_batch(torch.zeros(4, 100)), _cpu_batch(torch.zeros(4, 120)),
+               _cpu_batch(torch.zeros(4, 100))]
+    ahead = training._Lookahead(None, [None, None], batches, 3, 7)
+    assert len(ahead.read_group()[0]) == 2 and not ahead.carry
+    assert ahead.read_group()[0] == [batches[2]] and not ahead.carry                # width 1: the next batch stays unread
+    assert ahead.read_group()[0] == [batches[3]] and ahead.read_group() == ([], [])
+
+
+def test_ramp_sizes_only_the_first_super_batches_of_a_run(monkeypatch):
+    """training._Lookahead.width: the plan of _ramp_plan is made once, from the first group's batch size, and applies to the
+    run's first super-batches only — the driver's 20 steps at width 20 on two slots are 13 + 7 batches."""
+    import training
+    for k in ("SLU_RAMP", "SLU_RAMP_SIDE"):
+        monkeypatch.delenv(k, raising=False)
+
+    def sizes(n_run, depth, n_slots=2):
+        ahead = training._Lookahead(None, [None] * n_slots, [_cpu_batch(torch.zeros(64, 8)) for _ in range(n_run)], depth, 7)
+        out = []
+        while True:
+            group, _ = ahead.read_group()
+            if not group:
+                return out, ahead
+            out.append(len(group))
+
+    got, ahead = sizes(20, 20)
+    assert got == [13, 7] and (ahead.sizes, ahead.side, ahead.n_run, ahead.launched) == ([13], 0, 20, 2)
+    assert sizes(30, 20)[0] == [17, 13] and sizes(8, 20)[0] == [8]
+    assert sizes(45, 20)[0] == [20, 20, 5]                              # a long run: no ramp
+    monkeypatch.setenv("SLU_RAMP", "2,4")
+    assert sizes(20, 20)[0] == [2, 4, 14] and sizes(30, 5)[0] == [2, 4, 5, 5, 5, 5, 4]      # capped by the width after the ramp
+    monkeypatch.setenv("SLU_RAMP", "auto")
+    got, ahead = sizes(20, 20, 3)
+    assert got == [3, 6, 11] and ahead.side == 3
+
+
+def test_defer_forks_restores_and_nests():
+    """ops.defer_forks: _Fork.defer holds the given value inside the block and the previous one after it, also when the
+    block raises; scopes nest."""
+    import pytest
+    from slu_hip import ops
+    assert ops._Fork.defer is False
+    with ops.defer_forks(True):
+        assert ops._Fork.defer is True
+        with ops.defer_forks(False):
+            assert ops._Fork.defer is False
+            with ops.defer_forks(True):
+                assert ops._Fork.defer is True
+            assert ops._Fork.defer is False
+        assert ops._Fork.defer is True
+        with pytest.raises(KeyError):
+            with ops.defer_forks(False):
+                raise KeyError("inside")
+        assert ops._Fork.defer is True
+    assert ops._Fork.defer is False
+    with pytest.raises(KeyError):
+        with ops.defer_forks(True):
+            raise KeyError("inside")
+    assert ops._Fork.defer is False
+
+
+def test_eager_step_counter_and_capture_policy(monkeypatch):
+    """Trainer._count_eager_step / _captured_step: a step is captured once THREE consecutive eager steps of its key have run;
+    another key in between restarts the count; the negative mark of a failed capture survives further steps and shape
+    changes; the table of counts is trimmed above 256 keys (failed and captured keys and the current one stay)."""
+    import types
+    import training
+    captures = []
+
+    class FakeStepGraph:
+        def __init__(self, trainer, inputs, *rest):
+            if inputs == "fails":
+                raise RuntimeError("no capture")
+            captures.append(inputs)
+            self.signature = trainer.bucket.signature
+
+    monkeypatch.setattr(training.pipeline, "StepGraph", FakeStepGraph)
+    monkeypatch.delenv("SLU_MAX_STEP_GRAPHS", raising=False)
+    tr = training.Trainer.__new__(training.Trainer)
+    tr._step_graphs, tr._eager_steps, tr._last_key, tr.capture_failures = {}, {}, None, 0
+    tr.bucket = types.SimpleNamespace(active=True, signature=("sig", 1))
+
+    def captured(key, inputs="ok"):
+        return tr._captured_step(key, inputs, None, None, False, None)
+
+    for n in (1, 2):
+        tr._count_eager_step("a")
+        assert tr._eager_steps["a"] == n and captured("a") is None
+    tr._count_eager_step("b")                           # a shape change ...
+    tr._count_eager_step("a")                           # ... restarts the count of "a"
+    assert tr._eager_steps == {"a": 1, "b": 1} and captured("a") is None
+    tr._count_eager_step("a")
+    tr._count_eager_step("a")
+    assert tr._eager_steps["a"] == 3
+    sg = captured("a")
+    assert sg is not None and tr._step_graphs == {"a": sg} and captures == ["ok"] and captured("a") is sg
+    tr.bucket.signature = ("sig", 2)                    # the trainable set changed: captured again, same key
+    assert captured("a") is not sg and len(captures) == 2 and list(tr._step_graphs) == ["a"]
+    tr.bucket.active = False
+    for _ in range(3):
+        tr._count_eager_step("c")
+    assert captured("c") is None                        # no gradient bucket in place: no capture
+    tr.bucket.active = True
+    for _ in range(3):
+        tr._count_eager_step("f")
+    assert captured("f", "fails") is None and tr.capture_failures == 1 and "f" not in tr._step_graphs
+    assert tr._eager_steps["f"] < 0
+    tr._count_eager_step("f")
+    tr._count_eager_step("b")
+    for _ in range(4):
+        tr._count_eager_step("f")
+    assert tr._eager_steps["f"] < 0 and captured("f") is None and tr.capture_failures == 1
+    for i in range(300):                                # ragged shapes
+        tr._count_eager_step(("ragged", i))
+        assert len(tr._eager_steps) <= 257
+    assert tr._eager_steps["f"] < 0 and tr._eager_steps["a"] == 3 and tr._eager_steps[("ragged", 299)] == 1
+    assert "b" not in tr._eager_steps and len(tr._eager_steps) < 60
