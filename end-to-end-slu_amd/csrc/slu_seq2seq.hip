@@ -10,6 +10,7 @@
 // reduction trees — deterministic) rather than clever.  One workgroup per utterance where a reduction is needed.
 #include "slu_common.h"
 #include "slu_philox.h"
+#include "slu_reduce.h"
 
 namespace slu {
 
@@ -98,33 +99,6 @@ gru_cell_bwd_kernel(const CellBwdArgs a) {
 // context[b] = sum_t a_t values[b,t].  keys / values are addressed as ptr + t * s_t + b * s_b (+ k): time-major or
 // batch-major alike.  One workgroup of 256 threads per utterance.
 // ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
-// block-wide sum / max of one value per thread (256 threads), result broadcast; `red` = 4 floats of LDS
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-__device__ __forceinline__ float block_max(float v, float* red) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-
 struct AttArgs {
   const float* keys; const float* values; long long s_t, s_b, v_t, v_b;
   const float* query; long long ld_q;         // (B, Kd)
@@ -227,13 +201,7 @@ logsoftmax_dot_fwd_kernel(const float* __restrict__ logits, const float* __restr
   const int b = blockIdx.x, tid = threadIdx.x;
   const float* lg = logits + (size_t)b * V;
   const float* yy = y + (size_t)b * ld_y;
-  float m = -INFINITY;
-  for (int v = tid; v < V; v += 256) m = fmaxf(m, lg[v]);
-  m = block_max(m, red);
-  float z = 0.0f;
-  for (int v = tid; v < V; v += 256) z += expf(lg[v] - m);
-  z = block_sum(z, red);
-  const float lse = m + logf(z);
+  const float lse = block_row_lse(lg, V, red);
   float acc = 0.0f;
   for (int v = tid; v < V; v += 256) acc = fmaf(lg[v] - lse, yy[v], acc);
   acc = block_sum(acc, red);

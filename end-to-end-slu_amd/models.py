@@ -171,6 +171,19 @@ def guarded_frozen_nsplit(model=None):
     return 2 if (pm is None or pm.f16x2_allowed()) else 3
 
 
+_BEAM_SEARCH = ("device", "host")
+
+
+def beam_search_mode():
+    """SLU_BEAM_SEARCH: where the seq2seq decoder's beam search keeps its books when Model.predict_intents / decode_intents
+    decode: "device" (default) — Seq2SeqDecoder.search, slu_beam_select after every step and one slu_beam_backtrack;
+    "host" — Seq2SeqDecoder.infer, torch bookkeeping as in the reference.  Same hypotheses, same scores."""
+    mode = os.environ.get("SLU_BEAM_SEARCH", "device")
+    if mode not in _BEAM_SEARCH:
+        raise ValueError("SLU_BEAM_SEARCH=%r: expected one of %s" % (mode, sorted(_BEAM_SEARCH)))
+    return mode
+
+
 def _require_device(t):
     if not t.is_cuda:
         raise _lib.SluHipError("the HIP kernels are the only compute path of this package: move the "
@@ -415,7 +428,8 @@ def _named(layer, name):
 # ------------------------------------------------------------------------------------------------
 # seq2seq intent head (reference models.py:381-651): same class / attribute / state_dict names; every contraction,
 # the GRUCell gates, the attention and the log-softmax pick run on the HIP kernels (ops.Seq2SeqDecoderFn and
-# ops.decoder_step); the beam bookkeeping (top-k, re-ordering of hypotheses) is host-side torch as in the reference.
+# ops.decoder_step); the beam bookkeeping (top-k, re-ordering of hypotheses) is host-side torch as in the reference in
+# Seq2SeqDecoder.infer and device code (ops.beam_select / beam_backtrack, csrc/slu_beam.hip) in Seq2SeqDecoder.search.
 # ------------------------------------------------------------------------------------------------
 class Seq2SeqEncoder(torch.nn.Module):
     """Stack of bidirectional GRU layers, each followed by RNNSelect and Dropout(0.5) (reference models.py:381-416)."""
@@ -658,6 +672,110 @@ class Seq2SeqDecoder(torch.nn.Module):
             beam = torch.zeros(W, bsz, U, V, dtype=torch.float32, device=dev)
             beam.scatter_(3, hyp.unsqueeze(3), 1.0)
         return scores, beam
+
+
+    # steps per captured chunk of the device search: U = 200 is 25 replays; a U that is no multiple runs its last chunk to
+    # the end (slu_beam_select does nothing once an utterance's counter has reached U, and the surplus decoder steps only
+    # touch scratch buffers)
+    SEARCH_CHUNK = 8
+    SEARCH_PLANS = 4            # captured shapes kept (ragged evaluation batches differ in T), least recently used out
+
+    def _search_plan(self, P, dev, bsz, T, W, U, V):
+        """Static buffers (+ the captured chunk of SEARCH_CHUNK steps) of one search shape."""
+        from slu_hip import pipeline as _pipeline
+        use_graph = _pipeline.graphs_enabled()
+        key = (bsz, T, W, U, V, str(dev), use_graph, tuple((n, t.data_ptr(), tuple(t.shape)) for n, t in P.items()
+                                                          if torch.is_tensor(t)))
+        plans = self.__dict__.setdefault("_search_plans", {})
+        plan = plans.pop(key, None)
+        if plan is None:
+            plan = self._build_search_plan(P, dev, bsz, T, W, U, V, use_graph)
+            while len(plans) >= self.SEARCH_PLANS:
+                plans.pop(next(iter(plans)))
+        plans[key] = plan                                   # most recently used last
+        return plan
+
+    def _build_search_plan(self, P, dev, bsz, T, W, U, V, use_graph):
+        from slu_hip import pipeline as _pipeline
+        Kd, Vd = P["key.weight"].shape[0], P["value.weight"].shape[0]
+        Lc, Dd = P["initial_state"].shape
+        E = P["embed.weight"].shape[0]
+        R = W * bsz
+        f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+        b = {"keys": f(T, R, Kd), "values": f(T, R, Vd), "state": f(R, Lc, Dd), "state_next": f(R, Lc, Dd),
+             "q": f(R, Kd), "inp0": f(R, E + Vd), "att_w": f(R, T), "logits": f(R, V), "gi": f(R, 3 * Dd),
+             "gh": f(Lc, R, 3 * Dd), "drop": [f(R, Dd) for _ in range(Lc - 1)],
+             # step counters (bsz int32) and running scores (W * bsz fp32) share one buffer: ONE fill re-arms a search
+             "ctl": i32(bsz + R), "backptr": i32(U, W, bsz), "labels": i32(U, W, bsz), "graph": None}
+        b["ctl"].zero_()
+        b["step"], b["scores"] = b["ctl"][:bsz], b["ctl"][bsz:].view(torch.float32).view(W, bsz)
+        embed = (P["embed.weight"], P["embed.bias"], b["inp0"])
+
+        def chunk():
+            for _ in range(self.SEARCH_CHUNK):
+                # y_prev=None: slu_beam_select has written the embedding half of inp0 (the bias before the first step)
+                _ops.decoder_step(P, b["keys"], b["values"], b["state"], b["state_next"], None, b["q"], b["inp0"],
+                                  b["att_w"], b["gi"], b["gh"], None, b["drop"], b["logits"], 0,
+                                  (0.0, None, 0, 0, None, R * Dd))
+                _ops.beam_select(b["logits"], b["scores"], b["state_next"], b["state"], b["step"], b["backptr"],
+                                 b["labels"], None, embed)
+        b["chunk"] = chunk
+        if use_graph:
+            # warm-up on the capture stream (lazy initialisation happens outside the capture), on zeroed operands
+            for t in (b["keys"], b["values"], b["state"], b["inp0"]):
+                t.zero_()
+            side = torch.cuda.Stream(dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                chunk()
+            side.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with _pipeline.capture(graph, side):            # one linear chain: no forked stream inside
+                chunk()
+            torch.cuda.current_stream(dev).wait_stream(side)
+            b["graph"] = graph
+        return b
+
+    def search(self, encoder_outputs, Sy, B=4, y_lengths=None, want_beam=False):
+        """infer's beam search with the books kept on the device -> (scores (B, batch) float32, labels (B, batch, U) int64)
+        [, beam (B, batch, U, |Sy|) one-hot float32 when want_beam], U = 200 or max(y_lengths): the hypotheses, bit-equal
+        scores and tie rule of infer (tests/test_hip_beam.py).  Per step: ops.decoder_step (its embedding GEMM left out:
+        slu_beam_select writes embed.weight[:, label] + embed.bias, what that GEMM gives for a one-hot row) and ONE
+        slu_beam_select; after the last step ONE slu_beam_backtrack.  No torch op and no host read in between; with
+        SLU_GRAPHS=1 the steps are a hipGraph of SEARCH_CHUNK steps replayed ceil(U / SEARCH_CHUNK) times, captured once
+        per shape and parameter storage (the graph reads the parameters in place: optimiser updates are seen)."""
+        _require_device(encoder_outputs)
+        dev = encoder_outputs.device
+        W, bsz, V = B, encoder_outputs.shape[0], len(Sy)
+        U = 200 if y_lengths is None else max(y_lengths)
+        names, tensors = self._params()
+        P = {n: t.detach() for n, t in zip(names, tensors)}
+        P["inv_scale"] = 1.0 / float(self.attention.scale_factor)
+        Kd, Vd = P["key.weight"].shape[0], P["value.weight"].shape[0]
+        E = P["embed.weight"].shape[0]
+        with torch.no_grad():
+            enc = encoder_outputs.detach().float().transpose(0, 1).contiguous()          # (T, bsz, C)
+            T = enc.shape[0]
+            enc2 = enc.view(T * bsz, -1)
+            p = self._search_plan(P, dev, bsz, T, W, U, V)
+            R = W * bsz
+            # set-up as in infer: keys / values once, replicated per hypothesis; initial state; all-zero first input
+            p["keys"].view(T, W, bsz, Kd).copy_(_ops.gemm(enc2, P["key.weight"].t(), P["key.bias"]).view(T, 1, bsz, Kd).expand(T, W, bsz, Kd))
+            p["values"].view(T, W, bsz, Vd).copy_(_ops.gemm(enc2, P["value.weight"].t(), P["value.bias"]).view(T, 1, bsz, Vd).expand(T, W, bsz, Vd))
+            _ops.broadcast_rows(P["initial_state"].contiguous().view(-1), p["state"].view(R, -1))
+            _ops.broadcast_rows(P["embed.bias"], p["inp0"][:, :E])                        # embed(0) = bias
+            p["ctl"].zero_()                                                            # step counters and scores
+            labels = torch.empty(W, bsz, U, dtype=torch.int64, device=dev)
+            beam = torch.empty(W, bsz, U, V, dtype=torch.float32, device=dev) if want_beam else None
+            for _ in range(-(-U // self.SEARCH_CHUNK)):
+                if p["graph"] is not None:
+                    p["graph"].replay()
+                else:
+                    p["chunk"]()
+            _ops.beam_backtrack(p["backptr"], p["labels"], labels, beam)
+            scores = p["scores"].clone()
+        return (scores, labels, beam) if want_beam else (scores, labels)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1254,7 +1372,10 @@ class Model(torch.nn.Module):
         """-> (intent_logits (B, num_values_total), predicted_intent (B, num_slots)) (models.py:830-846)"""
         h = self._intent_features_tm(x).contiguous()
         if self.seq2seq:                                         # beam search, width 4 (models.py:848-851)
-            return self.decoder.infer(h.transpose(0, 1), self.Sy_intent, B=4)
+            if beam_search_mode() == "host":
+                return self.decoder.infer(h.transpose(0, 1), self.Sy_intent, B=4)
+            scores, _, beam = self.decoder.search(h.transpose(0, 1), self.Sy_intent, B=4, want_beam=True)
+            return scores, beam
         cls = self.intent_layers[-2]
         _, logits, pred, _, _ = _ops.cls_maxpool_ce_fwd(h.detach(), cls.weight.detach(), cls.bias.detach(), None,
                                                         tuple(self.values_per_slot), False)
@@ -1262,9 +1383,16 @@ class Model(torch.nn.Module):
 
     def decode_intents(self, x):
         """-> list (batch) of lists (slots) of slot-value strings (reference models.py:853-865)."""
+        if self.seq2seq and beam_search_mode() == "device":
+            # best hypothesis of every utterance (models.py:866-874) from its labels (batch, U): the string
+            # one_hot_to_string builds, without the one-hot beam crossing to the host
+            h = self._intent_features_tm(x).contiguous()
+            _, labels = self.decoder.search(h.transpose(0, 1), self.Sy_intent, B=4)
+            S = self.Sy_intent
+            return ["".join([S[c] for c in row]).lstrip("<sos>").rstrip("<eos>") for row in labels[0].cpu().tolist()]
         _, pred = self.predict_intents(x)
         pred = pred.cpu()
-        if self.seq2seq:                                         # best hypothesis of every utterance (models.py:866-874)
+        if self.seq2seq:                                         # SLU_BEAM_SEARCH=host
             return [self.one_hot_to_string(pred[0, i], self.Sy_intent) for i in range(pred.shape[1])]
         inverse = [{idx: value for value, idx in self.Sy_intent[slot].items()} for slot in self.Sy_intent]
         return [[inverse[s][int(row[s])] for s in range(len(inverse)) if int(row[s]) in inverse[s]]

@@ -46,6 +46,9 @@ SIGNATURES = {
     "slu_neg_mean_f32": (c_int, [vp, vp, c_i64, vp]),
     "slu_fill_scaled_f32": (c_int, [vp, c_i64, vp, c_f32, vp]),
     "slu_broadcast_rows_f32": (c_int, [vp, vp, c_i64, c_i64, c_i64, vp]),
+    "slu_beam_select": (c_int, [vp, vp, vp, vp, vp, vp, vp, vp, c_i64, vp, c_i64, vp, vp, c_i64, c_i64, c_i64, c_i64, c_i64,
+                                c_i64, c_i64, c_i64, vp]),
+    "slu_beam_backtrack": (c_int, [vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, vp]),
     "slu_sinc_filters_fwd": (c_int, [vp, vp, vp, c_i64, c_i64, c_f64, vp]),
     "slu_sinc_filters_bwd": (c_int, [vp, vp, vp, vp, vp, c_i64, c_i64, c_f64, vp]),
     "slu_wconv_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),

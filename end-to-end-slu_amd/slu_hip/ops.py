@@ -1603,6 +1603,56 @@ def broadcast_rows(src, dst2d):
                "slu_broadcast_rows_f32")
 
 
+def beam_select(logits, scores, state_next, state, step, backptr, labels, y_prev=None, embed=None):
+    """The beam bookkeeping of one decoding step in one launch (csrc/slu_beam.hip; include/slu_hip.h has the rule).
+    logits (W * batch, V); scores (W, batch) fp32, in place; state_next -> state (W * batch, L, Dd), two buffers; step
+    (batch) int32 device counters (read, then advanced); backptr / labels (U, W, batch) int32 history planes.
+    Next input: y_prev (W * batch, V) gets the one-hot rows, and / or embed = (weight (E, V), bias (E), inp (W * batch,
+    >= E)) gets the embedded label directly."""
+    L = _lib.load()
+    W, batch = scores.shape
+    R, V = logits.shape
+    Lc, Dd = state.shape[1], state.shape[2]
+    U = backptr.shape[0]
+    assert R == W * batch and tuple(state.shape) == tuple(state_next.shape) == (R, Lc, Dd)
+    assert tuple(backptr.shape) == tuple(labels.shape) == (U, W, batch) and step.numel() == batch
+    assert backptr.dtype == labels.dtype == step.dtype == torch.int32
+    for t in (logits, scores, state_next, state):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    assert backptr.is_contiguous() and labels.is_contiguous() and step.is_contiguous()
+    ew = eb = inp = None
+    E = 0
+    if embed is not None:
+        ew, eb, inp = embed
+        E = ew.shape[0]
+        assert ew.shape[1] == V and ew.stride(1) == 1 and eb.is_contiguous() and eb.numel() == E
+        assert inp.shape[0] == R and inp.shape[1] >= E and inp.stride(1) == 1
+    if y_prev is not None:
+        assert tuple(y_prev.shape) == (R, V) and y_prev.stride(1) == 1
+    _lib.check(L.slu_beam_select(logits.data_ptr(), scores.data_ptr(), state_next.data_ptr(), state.data_ptr(),
+                                 step.data_ptr(), backptr.data_ptr(), labels.data_ptr(), _ptr(y_prev),
+                                 0 if y_prev is None else y_prev.stride(0), _ptr(ew), 0 if ew is None else ew.stride(0),
+                                 _ptr(eb), _ptr(inp), 0 if inp is None else inp.stride(0), E, W, batch, V, Lc, Dd, U,
+                                 _stream()), "slu_beam_select")
+
+
+def beam_backtrack(backptr, labels, out, one_hot=None):
+    """History planes (U, W, batch) int32 -> out (W, batch, U) int64 label sequences and, when given, the one-hot beam
+    (W, batch, U, V) float32 (written whole)."""
+    L = _lib.load()
+    U, W, batch = backptr.shape
+    assert tuple(labels.shape) == (U, W, batch) and backptr.dtype == labels.dtype == torch.int32
+    assert backptr.is_contiguous() and labels.is_contiguous()
+    assert tuple(out.shape) == (W, batch, U) and out.dtype == torch.int64 and out.is_contiguous()
+    if one_hot is not None:
+        assert one_hot.dtype == torch.float32 and one_hot.is_contiguous() and tuple(one_hot.shape[:3]) == (W, batch, U)
+        V = one_hot.shape[3]
+    else:
+        V = (1 << 31) - 1     # labels are clamped to [0, V): no one-hot, no bound
+    _lib.check(L.slu_beam_backtrack(backptr.data_ptr(), labels.data_ptr(), out.data_ptr(), _ptr(one_hot), W, batch, U, V,
+                                    _stream()), "slu_beam_backtrack")
+
+
 def decoder_step(P, keys, values, state_prev, state_next, y_prev, q, inp0, att_w, gi, gh, save, drop, logits, step,
                  drop_cfg):
     """One decoding step (models.py:528-536) on the HIP kernels, shared by the teacher-forced forward and the beam

@@ -453,6 +453,32 @@ int slu_neg_mean_f32(const float* x, float* out, int64_t n, void* stream);
 int slu_fill_scaled_f32(float* dst, int64_t n, const float* g, float scale, void* stream);
 int slu_broadcast_rows_f32(const float* src, float* dst, int64_t ld_dst, int64_t rows, int64_t n, void* stream);
 
+/* -------- beam search of the seq2seq decoder on the device (models.py:559-651, Seq2SeqDecoder.infer) — added under ABI 10
+ * (two new entry points; nothing existing changed, so the version number stays).  One slu_beam_select after every decoding
+ * step replaces the host path's top-k / sort / gathers; the step index is DEVICE state, so the arguments are the same for
+ * every step and a captured step replays.  Rows of the step batch are w * batch + b (hypothesis w of utterance b).
+ *   slu_beam_select    logits (W * batch, V) of this step; scores (W, batch) running log-probabilities, updated in place;
+ *                      state_next (W * batch, L, Dd) the step's new decoder states -> state (a different buffer) = the
+ *                      surviving hypotheses' rows; step (batch) int32: u = step[b] is read, u + 1 written (zero it before
+ *                      the first step; a call with u >= U does nothing); backptr / labels (U, W, batch) int32 history planes:
+ *                      plane u receives, per surviving hypothesis, the slot it came from and the label appended.
+ *                      Candidates: per source hypothesis the top W logits (descending, equal logits: lower label first),
+ *                      scored (logit - lse) + score[src] with lse = m + logf(sum expf(l - m)) exactly as
+ *                      slu_logsoftmax_dot_fwd forms it; at u = 0 hypothesis 0 only; the W best of the W * W, descending,
+ *                      stable over the candidate index src * W + ext.  NaN logits are not ordered.
+ *                      Next input, either or both: y_prev (NULL or (W * batch, V), row stride ld_y) = one-hot of the label;
+ *                      inp (NULL or (W * batch, >= E), row stride ld_inp): inp[r, e] = embed_w[e * ld_ew + label] + embed_b[e]
+ *                      (the embedding Linear applied to that one-hot row, bit for bit).
+ *                      SLU_ERR_UNSUPPORTED unless 1 <= W <= 8, V >= W, Dd % 4 == 0 and 16-byte aligned state buffers.
+ *   slu_beam_backtrack after the last step: out (W, batch, U) int64 label sequences, final rank w first; one_hot (NULL or
+ *                      (W, batch, U, V) float32) is written whole (zeros and ones).  3 * U * W * 4 bytes of LDS (<= 60 KiB). */
+int slu_beam_select(const float* logits, float* scores, const float* state_next, float* state, int32_t* step,
+                    int32_t* backptr, int32_t* labels, float* y_prev, int64_t ld_y, const float* embed_w, int64_t ld_ew,
+                    const float* embed_b, float* inp, int64_t ld_inp, int64_t E, int64_t W, int64_t batch, int64_t V,
+                    int64_t L, int64_t Dd, int64_t U, void* stream);
+int slu_beam_backtrack(const int32_t* backptr, const int32_t* labels, int64_t* out, float* one_hot, int64_t W,
+                       int64_t batch, int64_t U, int64_t V, void* stream);
+
 /* -------- Adam: torch.optim.Adam(model.parameters(), lr) (training.py:19, default betas / eps) ------
  * One launch updates up to slu_adam_max_tensors() tensors of one dtype (elem_bytes 4 / 8); the pointer
  * arrays are HOST arrays of device pointers (they travel in the kernel arguments: hipGraph-safe).
