@@ -1,0 +1,223 @@
+// Waveform augmentation in front of the Sinc block (reference data.py:276-316, the chain SLUDataset.__getitem__ carries
+// behind `augment`): random gain, random crop / centre-pad, white noise at a drawn SNR — on the device, on the
+// step-indexed Philox stream, reading fp32 or PCM16 rows where they lie (dense batch or row-pointer table) and writing
+// the dense fp32 batch stage 0 reads.  The row semantics are stated once, in include/slu_hip.h (slu_wave_augment).
+//
+// One row is a dependent chain: len (last non-zero sample) -> drawn window -> window energy -> output.  A row is handled
+// by `split` workgroups (4 below 128 rows, 2 below 256, else 1: 64 rows alone would fill 64 of 256 CUs).  EVERY workgroup
+// of a row computes the row's len and energy itself, with the same thread -> element map and the same reduction tree
+// (slu_reduce.h), so the statistics — and with them every output bit — do not depend on the split; the re-reads of a
+// 192 KB row come from L2.  Only the write pass (Philox + Box-Muller, the arithmetic of the kernel) is divided.
+#include "slu_common.h"
+#include "slu_philox.h"
+#include "slu_reduce.h"
+
+namespace slu {
+
+struct AugParams {
+  const void* in;                       // dense (B, T) rows, or
+  const void* const* in_tab;            // device table of base pointers: row b = in_tab[b / tab_rows] + (b % tab_rows) * T
+  int tab_rows;
+  int pcm16;                            // rows are int16 samples; value = sample * in_scale
+  float in_scale;
+  float* out;                           // dense (B, T)
+  float* params;                        // null, or (B, 8)
+  int B, T, flags, split;
+  unsigned long long seed, offset, sub_stride;
+  const unsigned long long* offset_dev;
+  int sub_batch;
+};
+
+constexpr int AUG_GAIN = 1, AUG_CROP = 2, AUG_NOISE = 4;
+
+// one row of the input: element j of [0, T)
+struct AugRow {
+  const float* f;
+  const short* s;
+  float scale;
+  bool vec;                             // 4 elements at j % 4 == 0 can be read with one 16-byte (fp32) / 8-byte (int16) load
+  __device__ __forceinline__ float at(int j) const { return s ? (float)s[j] * scale : f[j]; }
+  __device__ __forceinline__ void at4(int j, float (&v)[4]) const {       // j % 4 == 0, j + 3 inside the row
+    if (s) {
+      const short4 q = *reinterpret_cast<const short4*>(s + j);
+      v[0] = (float)q.x * scale; v[1] = (float)q.y * scale; v[2] = (float)q.z * scale; v[3] = (float)q.w * scale;
+    } else {
+      const float4 q = *reinterpret_cast<const float4*>(f + j);
+      v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    }
+  }
+};
+
+// samples j0 .. j0 + 3 of the row, zero outside [0, len).  One wide load only when the drawn shift leaves the source
+// aligned (d % 4 == 0, an aligned row); otherwise four scalar loads — two aligned loads and a select would do, left with the
+// 64-row tuning item while the launch is latency-bound.  Rows with T % 4 != 0 also store scalars.
+__device__ __forceinline__ void aug_window4(const AugRow& r, int j0, int len, float (&v)[4]) {
+  if (r.vec && (j0 & 3) == 0 && j0 >= 0 && j0 + 3 < len) {
+    r.at4(j0, v);
+    return;
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int j = j0 + e;
+    v[e] = (j >= 0 && j < len) ? r.at(j) : 0.0f;
+  }
+}
+
+// uniform in (0, 1] that is never 0: the fp32 value of (word >> 8) + 0.5, scaled by 2^-24
+__device__ __forceinline__ float aug_uniform(uint32_t w) { return ((float)(w >> 8) + 0.5f) * (1.0f / 16777216.0f); }
+
+// grid: B * split workgroups of 256 threads, the workgroups of a row adjacent
+__global__ void __launch_bounds__(256)
+wave_augment_kernel(const AugParams p) {
+  __shared__ float red[4];
+  const int tid = threadIdx.x;
+  const int b = blockIdx.x / p.split, part = blockIdx.x - b * p.split;
+  const int T = p.T;
+  const int nchunk = (T + 3) >> 2;
+
+  AugRow r;
+  {
+    const size_t roff = (size_t)(p.in_tab ? b % p.tab_rows : b) * T;
+    const void* base = p.in_tab ? p.in_tab[b / p.tab_rows] : p.in;
+    r.f = p.pcm16 ? nullptr : reinterpret_cast<const float*>(base) + roff;
+    r.s = p.pcm16 ? reinterpret_cast<const short*>(base) + roff : nullptr;
+    r.scale = p.in_scale;
+    r.vec = p.pcm16 ? ((reinterpret_cast<uintptr_t>(r.s) & 7) == 0) : ((reinterpret_cast<uintptr_t>(r.f) & 15) == 0);
+  }
+  float* __restrict__ y = p.out + (size_t)b * T;
+  const bool y_vec = (reinterpret_cast<uintptr_t>(y) & 15) == 0;
+
+  // the row's own stream: row bl of the batch it belongs to, that batch's step
+  unsigned long long off = p.offset + (p.offset_dev ? *p.offset_dev : 0ull);
+  int bl = b;
+  if (p.sub_batch > 0) {
+    const int k = b / p.sub_batch;
+    bl = b - k * p.sub_batch;
+    off += (unsigned long long)k * p.sub_stride;
+  }
+  uint32_t w[4];
+  philox_block(p.seed, off, (1ull << 63) | (unsigned long long)bl, w);
+
+  // ---- len = 1 + index of the last non-zero sample (indices below 2^24 are exact in fp32) ----
+  float last = 0.0f;
+#pragma unroll 4                                             // independent loads in flight: the pass is latency-bound
+  for (int c = tid; c < nchunk; c += 256) {
+    const int j0 = c << 2;
+    float v[4];
+    aug_window4(r, j0, T, v);
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (v[e] != 0.0f) last = (float)(j0 + e + 1);
+  }
+  const int len = (int)block_max(last, red);
+
+  // ---- the drawn parameters ----
+  float g = 1.0f;
+  if (p.flags & AUG_GAIN) {
+    const float dB = -10.0f + 20.0f * philox_to_uniform(w[0]);
+    g = exp2f(dB * 0.16609640474436813f);                      // 10^(dB / 20) = 2^(dB * log2(10) / 20)
+  }
+  int Lp = len, d = 0;                                         // y[i] = g * x[i + d] for i < Lp (x = 0 outside [0, len))
+  if (p.flags & AUG_CROP) {
+    const long long l9 = 9ll * len + 5, l11 = 11ll * len + 5;
+    const int Lmin = (int)(l9 / 10), Lmax = (int)(l11 / 10);
+    Lp = Lmin + (int)(((unsigned long long)w[1] * (unsigned)(Lmax - Lmin)) >> 32);
+    Lp = min(Lp, T);
+    const int s0 = (len - Lp) / 2;                             // truncates toward zero
+    d = s0 < 0 ? s0 : (int)(((unsigned long long)w[2] * (unsigned)(s0 + 1)) >> 32);
+  }
+  const int snr_i = (int)(((unsigned long long)w[3] * 5u) >> 32);
+
+  // ---- energy of the window: sum over i < Lp of x[i + d]^2 (fixed thread map and tree: independent of the split) ----
+  float sigma = 0.0f, energy = 0.0f;
+  if (p.flags & AUG_NOISE) {
+    float a[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    const int nwin = (Lp + 3) >> 2;
+#pragma unroll 4
+    for (int c = tid; c < nwin; c += 256) {
+      const int i0 = c << 2;
+      float v[4];
+      aug_window4(r, i0 + d, len, v);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (i0 + e < Lp) a[e] = fmaf(v[e], v[e], a[e]);
+    }
+    energy = block_sum((a[0] + a[1]) + (a[2] + a[3]), red);
+    const float att = snr_i == 0 ? 1.0f : snr_i == 1 ? 0.5623413251903491f : snr_i == 2 ? 0.31622776601683794f
+                    : snr_i == 3 ? 0.17782794100389228f : 0.1f;                 // 10^(-snr / 20)
+    if (Lp > 0) sigma = sqrtf((1e-12f + g * g * energy) / (float)Lp) * att;
+  }
+
+  if (p.params && part == 0 && tid == 0) {
+    float* q = p.params + (size_t)b * 8;
+    q[0] = (float)len; q[1] = (float)Lp; q[2] = (float)d; q[3] = (float)(5 * snr_i);
+    q[4] = g; q[5] = sigma; q[6] = energy; q[7] = 0.0f;
+  }
+
+  // ---- write pass: this workgroup's share of the row's 4-sample chunks ----
+  const int per = (nchunk + p.split - 1) / p.split;
+  const int c_end = min(nchunk, (part + 1) * per);
+  const unsigned long long blk0 = (unsigned long long)bl * (unsigned long long)nchunk;
+  const bool noise = (p.flags & AUG_NOISE) != 0;
+#pragma unroll 2
+  for (int c = part * per + tid; c < c_end; c += 256) {
+    const int i0 = c << 2;
+    float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (i0 < Lp) {
+      aug_window4(r, i0 + d, len, v);
+      float n[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (noise) {
+        uint32_t z[4];
+        philox_block(p.seed, off, blk0 + (unsigned long long)c, z);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {                          // Box-Muller: words (0, 1) -> samples 0, 1; (2, 3) -> 2, 3
+          const float rad = sqrtf(-2.0f * logf(aug_uniform(z[2 * h])));
+          float sn, cs;
+          sincospif(2.0f * aug_uniform(z[2 * h + 1]), &sn, &cs);
+          n[2 * h] = rad * cs; n[2 * h + 1] = rad * sn;
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float gx = g * v[e];
+        v[e] = (i0 + e < Lp) ? (noise ? fmaf(sigma, n[e], gx) : gx) : 0.0f;
+      }
+    }
+    if (y_vec && i0 + 3 < T) {
+      *reinterpret_cast<float4*>(y + i0) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (i0 + e < T) y[i0 + e] = v[e];
+    }
+  }
+}
+
+}  // namespace slu
+
+using namespace slu;
+
+extern "C" int slu_wave_augment(const void* in, const void* const* in_table, int64_t table_rows, int in_pcm16, float in_scale,
+                                float* out, float* params, int64_t B, int64_t T, int flags, uint64_t seed, uint64_t offset,
+                                const uint64_t* offset_dev, int64_t sub_batch, uint64_t sub_stride, void* stream) {
+  SLU_REQUIRE((in || in_table) && out, "slu_wave_augment: null pointer");
+  SLU_REQUIRE(B > 0 && B < (1 << 29) && T > 0 && T <= (1 << 24), "slu_wave_augment: needs 1 <= B < 2^29 and 1 <= T <= 2^24 (got %lld x %lld)",
+              (long long)B, (long long)T);
+  SLU_REQUIRE(flags >= 0 && flags <= 7, "slu_wave_augment: flags must be a combination of 1 (gain), 2 (crop), 4 (noise)");
+  SLU_REQUIRE(!in_table || (table_rows >= 1 && table_rows <= B && B % table_rows == 0),
+              "slu_wave_augment: bad table_rows (B must be a whole number of tables' rows)");
+  SLU_REQUIRE(sub_batch >= 0 && (sub_batch == 0 || B % sub_batch == 0), "slu_wave_augment: B must be a multiple of sub_batch");
+  SLU_REQUIRE(in_table || ((uintptr_t)in & (in_pcm16 ? 1 : 3)) == 0, "slu_wave_augment: misaligned input");
+  SLU_REQUIRE(((uintptr_t)out & 3) == 0 && (!params || ((uintptr_t)params & 3) == 0), "slu_wave_augment: misaligned output");
+  SLU_REQUIRE(in_table || (const void*)out != in, "slu_wave_augment: out must not alias in");
+  AugParams p;
+  p.in = in_table ? nullptr : in; p.in_tab = in_table; p.tab_rows = (int)(in_table ? table_rows : 1);
+  p.pcm16 = in_pcm16 ? 1 : 0; p.in_scale = in_pcm16 ? in_scale : 1.0f;
+  p.out = out; p.params = params; p.B = (int)B; p.T = (int)T; p.flags = flags;
+  p.split = B < 128 ? 4 : B < 256 ? 2 : 1;
+  p.seed = seed; p.offset = offset; p.sub_stride = sub_stride; p.offset_dev = (const unsigned long long*)offset_dev;
+  p.sub_batch = (int)sub_batch;
+  hipLaunchKernelGGL(wave_augment_kernel, dim3((unsigned)(B * p.split)), dim3(256), 0, (hipStream_t)stream, p);
+  SLU_CHECK_LAUNCH("wave_augment_kernel");
+  return SLU_OK;
+}

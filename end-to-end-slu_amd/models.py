@@ -103,6 +103,25 @@ def _site(module, idx):
     return _SITE_BASE[module] + idx % n + ((idx // n) << _SITE_OVERFLOW_SHIFT)
 
 
+# The waveform augmentation (Model.augment; ops.wave_augment) draws from the same step-indexed stream layout — offset =
+# step * 16, sub-batches 16 apart — under a key of its own: seed ^ AUGMENT_KEY.  All 16 offsets of a step belong to the
+# sites above and deeper stacks spill into << 40 offsets, so no OFFSET is free; a different Philox key is a different stream.
+AUGMENT_KEY = 0xA0761D6478BD642F
+
+
+def _augment(x, training_augment):
+    """x (B, T) waveform batch (fp32 / PCM16 tensor or ops.RowTable) -> its augmentation for the current dropout step
+    (dense fp32), when `training_augment`; else x itself."""
+    if not training_augment:
+        return x
+    seed = (_DropoutState.seed if _DropoutState.seed is not None else torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
+    flags = _ops.augment_flags()
+    with torch.no_grad():
+        if _DropoutState.current_dev is not None:
+            return _ops.wave_augment(x, flags, seed ^ AUGMENT_KEY, 0, _DropoutState.current_dev, _DropoutState.sub_batch)
+        return _ops.wave_augment(x, flags, seed ^ AUGMENT_KEY, _DropoutState.current * 16, None, _DropoutState.sub_batch)
+
+
 class _FrozenMath:
     """State of the frozen stages' arithmetic in the guarded mode (SLU_FROZEN_MATH=auto; slu_hip/guard.py)."""
     scope = None        # the RangeGuard watching the evaluation that is running now: only then auto = f16x2
@@ -1202,6 +1221,10 @@ class Model(torch.nn.Module):
         self.unfreezing_index = config.starting_unfreezing_index
         if config.pretraining_type != 0:
             self.freeze_all_layers()
+        # [training] augment of the cfg: training waveforms pass through ops.wave_augment (SLU_AUGMENT picks the components)
+        self.augment = bool(getattr(config, "augment", False))
+        if self.augment:
+            _ops.augment_flags()                  # an unknown component name fails here, not at the first step
         self.seq2seq = config.seq2seq
         out_dim = config.word_rnn_num_hidden[-1] * (2 if config.word_rnn_bidirectional else 1)
         if self.seq2seq:
@@ -1287,7 +1310,8 @@ class Model(torch.nn.Module):
                 _DropoutState.current = rng_step
             _DropoutState.sub_batch = sub_batch
             try:
-                return self.pretrained_model.run_stages(self.pretrained_model._to_device(x)[0], 0, n_stages)
+                x = _augment(self.pretrained_model._to_device(x)[0], self.augment and self.training)
+                return self.pretrained_model.run_stages(x, 0, n_stages)
             finally:
                 _DropoutState.current_dev = None
                 _DropoutState.sub_batch = 0
@@ -1300,6 +1324,8 @@ class Model(torch.nn.Module):
         else:
             _DropoutState.current = rng_step
         try:
+            if n_stages == 0:
+                h = _augment(h, self.augment and self.training)
             h = pm.run_stages(h, n_stages, len(pm._stages()))
             drop = None
             for st in self._intent_stages:

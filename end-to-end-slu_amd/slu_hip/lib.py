@@ -78,6 +78,7 @@ SIGNATURES = {
     "slu_gru_seq_fwd_pool_bf16": (c_int, [vp, vp, vp, vp, vp, vp, vp, c_i64, vp, c_f32, vp, c_i64, c_i64, vp, vp, c_i64,
                                           c_i64, c_i64, c_i64, c_int, c_int, vp]),
     "slu_dropout_bits": (c_int, [vp, c_f32, c_u64, c_u64, vp, c_i64, c_u64, c_i64, c_i64, c_i64, vp]),
+    "slu_wave_augment": (c_int, [vp, vp, c_i64, c_int, c_f32, vp, vp, c_i64, c_i64, c_int, c_u64, c_u64, vp, c_i64, c_u64, vp]),
     "slu_comm_version": (c_int, []),
     "slu_comm_unique_id": (c_int, [vp]),
     "slu_comm_init": (c_int, [vp, vp, c_i64, c_i64]),

@@ -641,6 +641,45 @@ def dropout_bits(T, B, C, p, seed, offset, offset_dev=None, sub_batch=0, device=
     return bits
 
 
+AUGMENT_FLAGS = {"gain": 1, "crop": 2, "noise": 4}      # flags of slu_wave_augment
+
+
+def augment_flags():
+    """SLU_AUGMENT: the components a model with augment=True applies to its training waveforms — a comma list of gain,
+    crop, noise (default: all three) -> the flags of slu_wave_augment."""
+    text = os.environ.get("SLU_AUGMENT", "gain,crop,noise")
+    flags = 0
+    for name in text.split(","):
+        name = name.strip()
+        if name not in AUGMENT_FLAGS:
+            raise ValueError("SLU_AUGMENT=%r: expected a comma list of %s" % (text, sorted(AUGMENT_FLAGS)))
+        flags |= AUGMENT_FLAGS[name]
+    return flags
+
+
+def wave_augment(x, flags, seed, offset, offset_dev=None, sub_batch=0, want_params=False):
+    """The waveform augmentation of reference data.py:276-316 on the device (slu_wave_augment; the row semantics are in
+    include/slu_hip.h): x = dense fp32 or int16 (B, T) tensor, or a RowTable of either dtype -> dense fp32 (B, T), plus
+    the (B, 8) tensor of what was drawn per row when want_params.  The kernel gathers the rows itself: a row-table
+    super-batch or a PCM16 batch needs no copy or conversion pass in front of it.  Stream arguments as dropout_bits."""
+    L = _lib.load()
+    B, T = x.shape
+    pcm = (1, PCM16_SCALE) if x.dtype == torch.int16 else (0, 1.0)
+    if isinstance(x, RowTable):
+        x_ptr, tab, tab_rows = None, x.ptrs.data_ptr(), x.rows
+    else:
+        if x.dtype not in (torch.float32, torch.int16) or not x.is_cuda or x.dim() != 2:
+            raise TypeError("wave_augment: x must be a float32 or int16 (B, T) CUDA tensor (got %s on %s)" % (x.dtype, x.device))
+        x = x.contiguous()
+        x_ptr, tab, tab_rows = x.data_ptr(), None, 0
+    out = torch.empty(B, T, dtype=torch.float32, device=x.device)
+    params = torch.empty(B, 8, dtype=torch.float32, device=x.device) if want_params else None
+    _lib.check(L.slu_wave_augment(x_ptr, tab, tab_rows, *pcm, out.data_ptr(), _ptr(params), B, T, int(flags),
+                                  int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset), _ptr(offset_dev), int(sub_batch), 16, _stream()),
+               "slu_wave_augment")
+    return (out, params) if want_params else out
+
+
 def gru_pool_fused_ok(H, D, T, p, mask, method, factor):
     """Can the recurrence apply the layer's Dropout + Downsample in its epilogue (slu_gru_seq_fwd_pool_bf16)?  Average
     pooling over two frames with an in-kernel Philox mask (or no dropout): every layer of the reference cfgs.  Injected
@@ -892,10 +931,10 @@ def resolve_wgrad():
 
 def wgrad_signature():
     """What must be EQUAL on every data-parallel rank for the replicas to stay bit-identical: the weight-gradient launch's
-    (mode, workgroup budget) and the arithmetic modes."""
+    (mode, workgroup budget), the arithmetic modes and the augmentation components (SLU_AUGMENT as written: compared, not parsed here)."""
     mode, budget = wgrad_branch()
-    return "%s/%d/%s/%s/%s" % (mode, budget, os.environ.get("SLU_TRAIN_MATH", "fp32"), os.environ.get("SLU_FROZEN_MATH", "bf16x3"),
-                               os.environ.get("SLU_DTYPE", "f32"))
+    return "%s/%d/%s/%s/%s/%s" % (mode, budget, os.environ.get("SLU_TRAIN_MATH", "fp32"), os.environ.get("SLU_FROZEN_MATH", "bf16x3"),
+                                  os.environ.get("SLU_DTYPE", "f32"), os.environ.get("SLU_AUGMENT", "gain,crop,noise"))
 
 
 def gemm_tn_splitk_ok(operands):

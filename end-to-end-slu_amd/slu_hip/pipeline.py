@@ -265,8 +265,10 @@ class PrefixSlot:
         captured graph then reads the batches in place (they must stay alive and unchanged until it has run: the
         training loop keeps them until their steps are done)."""
         pm = getattr(model, "pretrained_model", model)
+        # (an augmenting model reads the table in ops.wave_augment, whatever kernel its first block runs on)
+        augmenting = getattr(model, "augment", False) and model.training
         return (os.environ.get("SLU_ROW_TABLE", "1") != "0" and 1 < len(xs) <= self.MAX_TABLE
-                and hasattr(pm, "accepts_row_table") and pm.accepts_row_table()
+                and (augmenting or (hasattr(pm, "accepts_row_table") and pm.accepts_row_table()))
                 and xs[0].dtype in (torch.float32, torch.int16)
                 and all(x.is_cuda and x.device == self.device and x.dtype == xs[0].dtype and x.is_contiguous()
                         and x.data_ptr() % 16 == 0 for x in xs))

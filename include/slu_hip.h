@@ -355,6 +355,40 @@ int slu_dropout_pool_fwd_planes(const float* x, const float* mask, int64_t m_st,
  * 24-bit uniform per element; the two streams are unrelated.)  C % 32 == 0, T <= 65535, bits 16-byte aligned.           */
 int slu_dropout_bits(uint32_t* bits, float p, uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
                      int64_t sub_batch, uint64_t sub_stride, int64_t T, int64_t B, int64_t C, void* stream);
+/* Waveform augmentation in front of stage 0 (ABI 10, added without a version step as the beam-search entry points were;
+ * reference data.py:276-316, the chain SLUDataset.__getitem__ keeps behind `augment`): out (B, T) dense fp32 = the
+ * augmented rows of the input — dense `in`, or in_table / table_rows as slu_wconv_fwd_bf16 reads them (B % table_rows == 0); in_pcm16 != 0: int16
+ * samples, value = sample * in_scale (as slu_wconv_fwd_bf16).  `out` never aliases the input.  The kernel gathers the rows
+ * itself: a row-table super-batch or a PCM16 batch needs no copy or conversion pass in front of it.
+ * Per row, in the reference's order gain -> crop -> noise; flags bit 0 gain, bit 1 crop, bit 2 noise:
+ *   len    1 + index of the last non-zero sample, 0 for an all-zero row (the collate functions zero-pad and pass no
+ *          lengths: trailing zeros are the padding; they add nothing to the energy, only the divisor depends on this).
+ *          An all-zero row comes out all zero.
+ *   gain   g = 10^(dB / 20), dB = -10 + 20 u, u = (w0 >> 8) 2^-24 (data.py:285-288); without the flag g = 1.
+ *   crop   Lmin = (9 len + 5) / 10, Lmax = (11 len + 5) / 10 (integer division: data.py:298's round()),
+ *          L' = min(T, Lmin + ((w1 * (Lmax - Lmin)) >> 32)); s0 = (len - L') / 2 truncating toward zero (data.py:300);
+ *          s0 < 0: the len samples are placed at left = -s0 inside [0, L'), zeros on both sides (data.py:301-304);
+ *          else start = (w2 * (s0 + 1)) >> 32 in [0, s0] and the window is x[start : start + L'] (data.py:306-307).
+ *          Without the flag L' = len, start = 0.  Deviation: the clamp to T — a row cannot outgrow its buffer.
+ *   noise  snr = 5 * ((w3 * 5) >> 32) dB in {0, 5, 10, 15, 20} (data.py:310);
+ *          sigma = sqrt((1e-12 + g^2 sum_window x^2) / L') 10^(-snr / 20); y[i] = g x_window[i] + sigma n_i for i < L',
+ *          n_i standard normal.  Deviation: the noise has unit variance by construction; the reference divides by the
+ *          measured energy of its own noise sample (data.py:311-315), which differs by O(1 / sqrt(L')).
+ *          Without the flag y[i] = g x_window[i] (flags = 0: the input's values, bit for bit).
+ *   tail   y[i] = 0 for L' <= i < T.
+ *   The reference's `tempo` effect (data.py:279-281) is sox's WSOLA time stretch and is NOT built.
+ * Random numbers: Philox4x32-10 (seed, offset [+ *offset_dev]); row = b, or b % sub_batch on offset + sub_stride *
+ * (b / sub_batch) exactly as slu_dropout_bits (a batch's augmentation does not depend on its place in a super-batch).
+ * w0..w3 = the words of block (1 << 63) | row; sample i of the row takes word i % 4 of block row * ceil(T / 4) + i / 4:
+ * words (0, 1) and (2, 3) of a block each give two normals by Box-Muller, r = sqrt(-2 ln u_a), n = r cos(2 pi u_b),
+ * r sin(2 pi u_b) with u = fp32((w >> 8) + 0.5) 2^-24 in (0, 1].  Every integer draw is (uint64(word) * range) >> 32.
+ * The caller keys the stream apart from the dropout sites' (models.py: seed ^ AUGMENT_KEY, offset = step * 16).
+ * params: NULL, or (B, 8) fp32 = what was drawn per row: len, L', start (>= 0) or -left (< 0), snr in dB, g, sigma,
+ * sum_window x^2, 0.  Rows are split over workgroups without changing a bit of the result; no atomics: the output is
+ * reproducible from run to run.  1 <= T <= 2^24.                                                                        */
+int slu_wave_augment(const void* in, const void* const* in_table, int64_t table_rows, int in_pcm16, float in_scale,
+                     float* out, float* params, int64_t B, int64_t T, int flags, uint64_t seed, uint64_t offset,
+                     const uint64_t* offset_dev, int64_t sub_batch, uint64_t sub_stride, void* stream);
 /* dx (T,B,C) from dy (T_out,B,C); x and y (forward input/output) are needed for method 2 only. */
 int slu_dropout_pool_bwd(const float* dy, const float* x, const float* y, const float* mask,
                          int64_t m_st, int64_t m_sb, float p, uint64_t seed, uint64_t offset,
