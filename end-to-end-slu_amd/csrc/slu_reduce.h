@@ -1,5 +1,6 @@
-// Wave- and block-level reductions shared by the decoder kernels (slu_seq2seq.hip, slu_beam.hip): fixed reduction
-// trees, so every kernel that reduces the same values through them gets the same bits.  Workgroups of 256 threads.
+// Wave- and block-level reductions shared by the decoder kernels (slu_seq2seq.hip, slu_beam.hip) and the waveform
+// augmentation (slu_augment.hip): fixed reduction trees, so every kernel that reduces the same values through them gets
+// the same bits.  Workgroups of 256 threads.
 #pragma once
 #include "slu_common.h"
 
@@ -30,6 +31,28 @@ __device__ __forceinline__ float block_max(float v, float* red) {
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
+// block-wide arg-min of one (value, index) pair per thread (256 threads), result broadcast: the smallest value, and among
+// equal values the smallest index.  A thread without a candidate passes (INFINITY, INT_MAX); NaN values never win.
+// `red_v` / `red_i` = 4 floats / 4 ints of LDS.
+__device__ __forceinline__ void block_argmin(float& v, int& i, float* red_v, int* red_i) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const float ov = __shfl_xor(v, o, 64);
+    const int oi = __shfl_xor(i, o, 64);
+    if (ov < v || (ov == v && oi < i)) { v = ov; i = oi; }
+  }
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) { red_v[threadIdx.x >> 6] = v; red_i[threadIdx.x >> 6] = i; }
+  __syncthreads();
+  v = red_v[0]; i = red_i[0];
+#pragma unroll
+  for (int w = 1; w < 4; ++w) {
+    const float ov = red_v[w];
+    const int oi = red_i[w];
+    if (ov < v || (ov == v && oi < i)) { v = ov; i = oi; }
+  }
 }
 
 // logsumexp of one row of V logits by a whole workgroup (every thread gets the result): m = max, z = sum expf(l - m),

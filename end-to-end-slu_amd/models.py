@@ -111,15 +111,20 @@ AUGMENT_KEY = 0xA0761D6478BD642F
 
 def _augment(x, training_augment):
     """x (B, T) waveform batch (fp32 / PCM16 tensor or ops.RowTable) -> its augmentation for the current dropout step
-    (dense fp32), when `training_augment`; else x itself."""
+    (dense fp32), when `training_augment`; else x itself.  The tempo perturbation (SLU_AUGMENT_TEMPO=1) runs first, on the
+    same stream: its factor comes from a Philox block of its own, so the other effects' draws do not move."""
     if not training_augment:
         return x
     seed = (_DropoutState.seed if _DropoutState.seed is not None else torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
     flags = _ops.augment_flags()
+    if _DropoutState.current_dev is not None:
+        stream = (seed ^ AUGMENT_KEY, 0, _DropoutState.current_dev, _DropoutState.sub_batch)
+    else:
+        stream = (seed ^ AUGMENT_KEY, _DropoutState.current * 16, None, _DropoutState.sub_batch)
     with torch.no_grad():
-        if _DropoutState.current_dev is not None:
-            return _ops.wave_augment(x, flags, seed ^ AUGMENT_KEY, 0, _DropoutState.current_dev, _DropoutState.sub_batch)
-        return _ops.wave_augment(x, flags, seed ^ AUGMENT_KEY, _DropoutState.current * 16, None, _DropoutState.sub_batch)
+        if _ops.tempo_enabled():                  # SLU_AUGMENT_TEMPO=1: the reference's order tempo -> gain -> crop -> noise
+            x = _ops.wave_tempo(x, *stream)
+        return _ops.wave_augment(x, flags, *stream)
 
 
 class _FrozenMath:
@@ -1225,6 +1230,7 @@ class Model(torch.nn.Module):
         self.augment = bool(getattr(config, "augment", False))
         if self.augment:
             _ops.augment_flags()                  # an unknown component name fails here, not at the first step
+            _ops.tempo_enabled()                  # likewise a bad SLU_AUGMENT_TEMPO
         self.seq2seq = config.seq2seq
         out_dim = config.word_rnn_num_hidden[-1] * (2 if config.word_rnn_bidirectional else 1)
         if self.seq2seq:

@@ -79,6 +79,8 @@ SIGNATURES = {
                                           c_i64, c_i64, c_i64, c_int, c_int, vp]),
     "slu_dropout_bits": (c_int, [vp, c_f32, c_u64, c_u64, vp, c_i64, c_u64, c_i64, c_i64, c_i64, vp]),
     "slu_wave_augment": (c_int, [vp, vp, c_i64, c_int, c_f32, vp, vp, c_i64, c_i64, c_int, c_u64, c_u64, vp, c_i64, c_u64, vp]),
+    "slu_wave_tempo": (c_int, [vp, vp, c_i64, c_int, c_f32, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_f32, c_u64, c_u64, vp,
+                               c_i64, c_u64, vp]),
     "slu_comm_version": (c_int, []),
     "slu_comm_unique_id": (c_int, [vp]),
     "slu_comm_init": (c_int, [vp, vp, c_i64, c_i64]),

@@ -680,6 +680,53 @@ def wave_augment(x, flags, seed, offset, offset_dev=None, sub_batch=0, want_para
     return (out, params) if want_params else out
 
 
+def tempo_enabled():
+    """SLU_AUGMENT_TEMPO: does a model with augment=True stretch its training waveforms (wave_tempo) in front of the other
+    effects?  0 (the default) or 1.  A knob of its own, off by default: SLU_AUGMENT keeps naming the components of
+    slu_wave_augment alone."""
+    text = os.environ.get("SLU_AUGMENT_TEMPO", "0")
+    if text not in ("0", "1"):
+        raise ValueError("SLU_AUGMENT_TEMPO=%r: expected 0 or 1" % text)
+    return text == "1"
+
+
+def tempo_defaults(fs=16000):
+    """(segment, overlap, search) in samples: sox's documented `tempo` defaults at the sampling rate fs — 82 ms, 12 ms
+    rounded down to a multiple of 8 samples, 14.68 ms (1312, 192, 235 at 16 kHz)."""
+    fs = int(fs)
+    return (fs * 82 + 500) // 1000, fs * 12 // 1000 // 8 * 8, (fs * 1468 + 50000) // 100000
+
+
+def wave_tempo(x, seed, offset, offset_dev=None, sub_batch=0, segment=None, overlap=None, search=None, fs=16000,
+               fixed_factor=0.0, want_params=False):
+    """The `tempo` effect of reference data.py:279-281 on the device: a WSOLA time stretch by a factor drawn per row from
+    [0.9, 1.1), or by fixed_factor (slu_wave_tempo; the row semantics are in include/slu_hip.h).  x as wave_augment takes
+    it -> dense fp32 (B, T), or (y, shifts (B, ceil(T / hop)) int32, params (B, 4) = f, len, len', segments) when
+    want_params.  segment / overlap / search default to tempo_defaults(fs).  Stream arguments as wave_augment: the factor
+    is drawn from a Philox block of its own on the same stream."""
+    L = _lib.load()
+    B, T = x.shape
+    d_seg, d_ovl, d_search = tempo_defaults(fs)
+    segment, overlap, search = (int(d if v is None else v) for v, d in ((segment, d_seg), (overlap, d_ovl), (search, d_search)))
+    pcm = (1, PCM16_SCALE) if x.dtype == torch.int16 else (0, 1.0)
+    if isinstance(x, RowTable):
+        x_ptr, tab, tab_rows = None, x.ptrs.data_ptr(), x.rows
+    else:
+        if x.dtype not in (torch.float32, torch.int16) or not x.is_cuda or x.dim() != 2:
+            raise TypeError("wave_tempo: x must be a float32 or int16 (B, T) CUDA tensor (got %s on %s)" % (x.dtype, x.device))
+        x = x.contiguous()
+        x_ptr, tab, tab_rows = x.data_ptr(), None, 0
+    if not 1 <= overlap < segment:
+        raise ValueError("wave_tempo: needs 1 <= overlap < segment (got overlap %d, segment %d)" % (overlap, segment))
+    out = torch.empty(B, T, dtype=torch.float32, device=x.device)
+    shifts = torch.empty(B, -(-T // (segment - overlap)), dtype=torch.int32, device=x.device)
+    params = torch.empty(B, 4, dtype=torch.float32, device=x.device) if want_params else None
+    _lib.check(L.slu_wave_tempo(x_ptr, tab, tab_rows, *pcm, out.data_ptr(), shifts.data_ptr(), _ptr(params), B, T, segment, overlap,
+                                search, float(fixed_factor), int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset), _ptr(offset_dev),
+                                int(sub_batch), 16, _stream()), "slu_wave_tempo")
+    return (out, shifts, params) if want_params else out
+
+
 def gru_pool_fused_ok(H, D, T, p, mask, method, factor):
     """Can the recurrence apply the layer's Dropout + Downsample in its epilogue (slu_gru_seq_fwd_pool_bf16)?  Average
     pooling over two frames with an in-kernel Philox mask (or no dropout): every layer of the reference cfgs.  Injected
@@ -931,10 +978,12 @@ def resolve_wgrad():
 
 def wgrad_signature():
     """What must be EQUAL on every data-parallel rank for the replicas to stay bit-identical: the weight-gradient launch's
-    (mode, workgroup budget), the arithmetic modes and the augmentation components (SLU_AUGMENT as written: compared, not parsed here)."""
+    (mode, workgroup budget), the arithmetic modes, the augmentation components and the tempo knob (SLU_AUGMENT and
+    SLU_AUGMENT_TEMPO as written: compared, not parsed here)."""
     mode, budget = wgrad_branch()
-    return "%s/%d/%s/%s/%s/%s" % (mode, budget, os.environ.get("SLU_TRAIN_MATH", "fp32"), os.environ.get("SLU_FROZEN_MATH", "bf16x3"),
-                                  os.environ.get("SLU_DTYPE", "f32"), os.environ.get("SLU_AUGMENT", "gain,crop,noise"))
+    return "%s/%d/%s/%s/%s/%s/%s" % (mode, budget, os.environ.get("SLU_TRAIN_MATH", "fp32"), os.environ.get("SLU_FROZEN_MATH", "bf16x3"),
+                                     os.environ.get("SLU_DTYPE", "f32"), os.environ.get("SLU_AUGMENT", "gain,crop,noise"),
+                                     os.environ.get("SLU_AUGMENT_TEMPO", "0"))
 
 
 def gemm_tn_splitk_ok(operands):

@@ -376,7 +376,7 @@ int slu_dropout_bits(uint32_t* bits, float p, uint64_t seed, uint64_t offset, co
  *          measured energy of its own noise sample (data.py:311-315), which differs by O(1 / sqrt(L')).
  *          Without the flag y[i] = g x_window[i] (flags = 0: the input's values, bit for bit).
  *   tail   y[i] = 0 for L' <= i < T.
- *   The reference's `tempo` effect (data.py:279-281) is sox's WSOLA time stretch and is NOT built.
+ *   The reference's `tempo` effect (data.py:279-281), which runs in front of the gain, is slu_wave_tempo below.
  * Random numbers: Philox4x32-10 (seed, offset [+ *offset_dev]); row = b, or b % sub_batch on offset + sub_stride *
  * (b / sub_batch) exactly as slu_dropout_bits (a batch's augmentation does not depend on its place in a super-batch).
  * w0..w3 = the words of block (1 << 63) | row; sample i of the row takes word i % 4 of block row * ceil(T / 4) + i / 4:
@@ -389,6 +389,40 @@ int slu_dropout_bits(uint32_t* bits, float p, uint64_t seed, uint64_t offset, co
 int slu_wave_augment(const void* in, const void* const* in_table, int64_t table_rows, int in_pcm16, float in_scale,
                      float* out, float* params, int64_t B, int64_t T, int flags, uint64_t seed, uint64_t offset,
                      const uint64_t* offset_dev, int64_t sub_batch, uint64_t sub_stride, void* stream);
+/* Tempo perturbation in front of slu_wave_augment (ABI 10, added without a version step as the beam-search and
+ * augmentation entry points were; reference data.py:279-281, the `tempo` effect of the chain): a duration change of
+ * +-10 % without a pitch change, by WSOLA (waveform-similarity overlap-add).  out (B, T) dense fp32 = the stretched rows of
+ * the input; input forms (dense / in_table, fp32 / PCM16), sub_batch / sub_stride and offset_dev as slu_wave_augment.
+ * Relation to sox: the callers' defaults (ops.tempo_defaults) are sox's documented `tempo` defaults at the model's fs —
+ * segment 82 ms, search 14.68 ms, overlap 12 ms rounded down to a multiple of 8: 1312 / 235 / 192 samples at 16 kHz.
+ * Neither sox nor torchaudio's sox chain is on the build machines, so the definition below is this library's own, and
+ * bit-parity with sox is a stated non-goal.
+ * Notation: S = segment, O = overlap, R = search, hop H = S - O; x = the row, len = 1 + index of its last non-zero sample
+ * (as slu_wave_augment), x = 0 outside [0, len).  Per row:
+ *   f      fixed_factor > 0: f = fixed_factor.  Else f = 0.9 + 0.2 u, u = (w0 >> 8) 2^-24 (data.py:279-280), w0 = word 0
+ *          of Philox block (1 << 63) | (1 << 62) | row on the key, offset, sub-batch and row rule of slu_wave_augment
+ *          (whose draws, from block (1 << 63) | row, do not move when tempo is switched on).  f > 1 shortens the row.
+ *          f, len / f and k H f below are float64, each operation rounded once.
+ *   len'   = min(T, floor(len / f + 0.5)); y[i] = 0 for i >= len'.  Deviation: the clamp to T, as the crop's.  An
+ *          all-zero row comes out all zero.
+ *   segments  k = 0, 1, ... while k H < len'; nominal analysis position a_k = floor(k H f + 0.5) (absolute: no drift).
+ *          delta_0 = 0.  For k >= 1, tail[j] = x[a_{k-1} + delta_{k-1} + H + j], j < O, is the previous chosen segment's
+ *          natural continuation, and delta_k is the delta in [0, R) that minimises
+ *          D(delta) = sum_{j < O} (x[a_k + delta + j] - tail[j])^2, summed as squared differences in fp32 in ascending j
+ *          (never the expanded correlation form, which cancels); on a tie the smallest delta wins.
+ *   synthesis  seg[j] = x[a_k + delta_k + j].  y[k H + j] = tail[j] + (seg[j] - tail[j]) (j / O) for j < O, k >= 1
+ *          (= tail[j] exactly when seg == tail); y[k H + j] = seg[j] for O <= j < H, and for all j < H when k = 0.
+ *          Everything is cut at len'.  f = 1 returns the row bit for bit with every delta_k = 0.
+ * shifts (required): (B, ceil(T / H)) int32 = delta_k, -1 for segments that do not exist.
+ * params: NULL, or (B, 4) fp32 = f, len, len', number of segments.
+ * 1 <= B < 2^29, 1 <= T <= 2^24, 1 <= O, 2 O <= S <= T, 1 <= R <= 1024, fixed_factor 0 or in [0.5, 2].  No allocation,
+ * no synchronisation, no atomics: hipGraph-safe, and reproducible from run to run; rows are split over workgroups
+ * without changing a bit of the result.                                                                                 */
+int slu_wave_tempo(const void* in, const void* const* in_table, int64_t table_rows, int in_pcm16, float in_scale,
+                   float* out, int32_t* shifts, float* params, int64_t B, int64_t T,
+                   int64_t segment, int64_t overlap, int64_t search, float fixed_factor,
+                   uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
+                   int64_t sub_batch, uint64_t sub_stride, void* stream);
 /* dx (T,B,C) from dy (T_out,B,C); x and y (forward input/output) are needed for method 2 only. */
 int slu_dropout_pool_bwd(const float* dy, const float* x, const float* y, const float* mask,
                          int64_t m_st, int64_t m_sb, float p, uint64_t seed, uint64_t offset,

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Micro-benchmark of the waveform-augmentation kernel (slu_wave_augment) at the shapes training feeds it, beside the
-cheapest passes that produce the same output bytes — slu_pcm16_to_f32 and a plain device copy — as the yardstick:
+"""Micro-benchmark of the waveform-augmentation kernels (slu_wave_augment, and slu_wave_tempo in front of it) at the shapes
+training feeds them, beside the cheapest passes that produce the same output bytes — slu_pcm16_to_f32 and a plain
+device copy — as the yardstick:
 
     python tools/bench_augment.py [--out profiles/augment_kernel.txt]
 
@@ -57,6 +58,10 @@ def main():
              % torch.cuda.get_device_name(0),
              "%-34s %10s %10s %10s %12s %12s %10s" % ("input", "all flags", "noise", "gain", "pcm16_to_f32", "device copy",
                                                       "all / copy")]
+    S, O, R = ops.tempo_defaults(16000)
+    tempo_lines = ["", "slu_wave_tempo (segment %d, overlap %d, search %d; factor drawn per row), same run: tempo alone, and tempo + "
+                   "slu_wave_augment (all flags) on its output" % (S, O, R),
+                   "%-34s %10s %16s %10s %16s" % ("input", "tempo", "tempo + augment", "segments", "us per segment")]
 
     def row(name, B, make_x, sub_batch=0):
         x = make_x()
@@ -71,6 +76,22 @@ def main():
         for label, flags in (("all", 7), ("noise", 4), ("gain", 1)):
             t[label] = timeit(lambda: lib.check(L.slu_wave_augment(*args, *pcm, out.data_ptr(), None, B, T, flags, seed, 16, None,
                                                                    sub_batch, 16, st()), "slu_wave_augment"))
+        mid = torch.empty(B, T, dtype=torch.float32, device=dev)
+        shifts = torch.empty(B, -(-T // (S - O)), dtype=torch.int32, device=dev)
+
+        def tempo():
+            lib.check(L.slu_wave_tempo(*args, *pcm, mid.data_ptr(), shifts.data_ptr(), None, B, T, S, O, R, 0.0, seed, 16, None,
+                                       sub_batch, 16, st()), "slu_wave_tempo")
+
+        def tempo_augment():
+            tempo()
+            lib.check(L.slu_wave_augment(mid.data_ptr(), None, 0, 0, 1.0, out.data_ptr(), None, B, T, 7, seed, 16, None,
+                                         sub_batch, 16, st()), "slu_wave_augment")
+
+        t_tempo, t_both = timeit(tempo), timeit(tempo_augment)
+        torch.cuda.synchronize()
+        nseg = int((shifts >= 0).sum(1).max().item())       # the longest search chain of the batch
+        tempo_lines.append("%-34s %10.1f %16.1f %10d %16.2f" % (name, t_tempo, t_both, nseg, t_tempo / max(nseg, 1)))
         src16 = torch.randint(-3000, 3000, (B, T), generator=gen, dtype=torch.int32).to(torch.int16).to(dev)
         t_pcm = timeit(lambda: lib.check(L.slu_pcm16_to_f32(src16.data_ptr(), out.data_ptr(), B * T, ops.PCM16_SCALE, st()),
                                          "slu_pcm16_to_f32"))
@@ -95,7 +116,7 @@ def main():
     row("64 x 48000 fp32", 64, lambda: fp32(64))
     row("64 x 48000 int16", 64, lambda: (fp32(64) * 32768.0).round().clamp(-32768, 32767).to(torch.int16))
     row("1280 x 48000 fp32, table of 20 x 64", 1280, lambda: table(1280, 64), sub_batch=64)
-    text = "\n".join(lines)
+    text = "\n".join(lines + tempo_lines)
     print(text)
     if a.out:
         with open(a.out, "w") as f:
