@@ -11,6 +11,17 @@
 //   top-W of a row: logits descending, equal logits: lower label index first;
 //   W best of the W * W: score descending, STABLE over the candidate index src * W + ext.
 // NaN logits are not ordered (a row with NaNs gives valid indices, nothing more).
+//
+// Finished hypotheses (slu_beam_select_eos, eos >= 0; this project's own rule, the reference has none): slot k of
+// utterance b is finished at step u iff u > 0 and labels[u - 1, k, b] == eos.  A finished source has ONE candidate,
+// src * W + 0, label eos, its score the source's score copied bit for bit; its other W - 1 candidates are -inf.  The
+// selection itself is the same.  It always finds W finite candidates: at u = 0 nothing is finished and source 0
+// contributes W (V >= W); at u > 0 there are W sources and each contributes at least one — a finished one exactly one,
+// an unfinished one W.  So a -inf candidate is never among the W best, and a survivor's label is eos exactly when it
+// came from a finished source or chose eos itself.  lengths[k] follows the hypotheses: the source's length if it was
+// finished, else u + 1.  When all W survivors are finished the workgroup fills the planes u + 1 .. U - 1 with
+// backptr = k, labels = eos, sets step[b] = U and adds 1 to *n_done; an utterance that fills its history unfinished adds
+// its 1 too, so the host stops at *n_done == batch.  eos < 0 is slu_beam_select: none of this runs.
 #include <limits.h>
 #include "slu_common.h"
 #include "slu_reduce.h"
@@ -30,6 +41,9 @@ struct BeamArgs {
   const float* embed_w; long long ld_ew; const float* embed_b;   // null or Linear(V, E): weight (E, V), bias (E)
   float* inp; long long ld_inp;        // (W * batch, >= E): inp[r, e] = embed_w[e, label_r] + embed_b[e]
   int E, W, batch, V, row, U;
+  int eos;                             // < 0: no finished hypotheses (slu_beam_select)
+  int* lengths;                        // eos >= 0: (W, batch) hypothesis lengths, updated in place
+  int* n_done;                         // eos >= 0: utterances whose search has ended
 };
 
 // (value, index) a before b: larger value, equal values: lower index
@@ -46,8 +60,9 @@ beam_select_kernel(const BeamArgs a) {
   __shared__ float cand[BEAM_MAX_W * BEAM_MAX_W];
   __shared__ float sel_s[BEAM_MAX_W];
   __shared__ int sel_src[BEAM_MAX_W], sel_lab[BEAM_MAX_W];
+  __shared__ int fin_s[BEAM_MAX_W], len_s[BEAM_MAX_W];
   const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int W = a.W, V = a.V, batch = a.batch;
+  const int W = a.W, V = a.V, batch = a.batch, eos = a.eos;
   const int u = a.step[b];
   if (u < 0 || u >= a.U) return;       // history is full: a replay past the last step changes nothing
 
@@ -56,7 +71,11 @@ beam_select_kernel(const BeamArgs a) {
     const float lse = block_row_lse(a.logits + ((size_t)w * batch + b) * V, V, red);
     if (tid == 0) lse_s[w] = lse;
   }
-  if (tid < BEAM_MAX_W) { sel_s[tid] = -INFINITY; sel_src[tid] = 0; sel_lab[tid] = 0; }
+  if (tid < BEAM_MAX_W) { sel_s[tid] = -INFINITY; sel_src[tid] = 0; sel_lab[tid] = 0; fin_s[tid] = 0; len_s[tid] = 0; }
+  if (eos >= 0 && tid < W) {           // the same thread wrote the zero above
+    fin_s[tid] = (u > 0 && a.labels[((size_t)(u - 1) * W + tid) * batch + b] == eos) ? 1 : 0;
+    len_s[tid] = a.lengths[(size_t)tid * batch + b];
+  }
 
   // top W of each row: one wave per row, W passes; a pass takes the first element AFTER the previous pick in the
   // order (value descending, index ascending), so equal logits come out by index and nothing is marked or moved
@@ -82,12 +101,14 @@ beam_select_kernel(const BeamArgs a) {
   }
   __syncthreads();
 
-  // candidate c = src * W + ext: (logit - lse[src]) + score[src]; the first step expands hypothesis 0 only
+  // candidate c = src * W + ext: (logit - lse[src]) + score[src]; the first step expands hypothesis 0 only; a finished
+  // source keeps its score, untouched, in its candidate 0
   const int n_cand = W * W;
   if (tid < n_cand) {
     const int src = tid / W;
     float s = (top_s[tid] - lse_s[src]) + a.scores[(size_t)src * batch + b];
     if (u == 0 && src > 0) s = -INFINITY;
+    if (fin_s[src]) s = tid == src * W ? a.scores[(size_t)src * batch + b] : -INFINITY;
     cand[tid] = s;
   }
   __syncthreads();
@@ -95,7 +116,7 @@ beam_select_kernel(const BeamArgs a) {
     const float s = cand[tid];
     int rank = 0;
     for (int c = 0; c < n_cand; ++c) rank += (cand[c] > s || (cand[c] == s && c < tid)) ? 1 : 0;
-    if (rank < W) { sel_s[rank] = s; sel_src[rank] = tid / W; sel_lab[rank] = top_i[tid]; }
+    if (rank < W) { sel_s[rank] = s; sel_src[rank] = tid / W; sel_lab[rank] = fin_s[tid / W] ? eos : top_i[tid]; }
   }
   __syncthreads();
 
@@ -104,8 +125,20 @@ beam_select_kernel(const BeamArgs a) {
     a.scores[(size_t)tid * batch + b] = sel_s[tid];
     a.backptr[h] = sel_src[tid];
     a.labels[h] = sel_lab[tid];
+    if (eos >= 0) a.lengths[(size_t)tid * batch + b] = fin_s[sel_src[tid]] ? len_s[sel_src[tid]] : u + 1;
   }
-  if (tid == 0) a.step[b] = u + 1;
+  bool all_fin = eos >= 0;             // uniform over the workgroup
+  for (int k = 0; k < W; ++k) all_fin = all_fin && sel_lab[k] == eos;
+  if (tid == 0) {
+    a.step[b] = all_fin ? a.U : u + 1;
+    if (eos >= 0 && (all_fin || u + 1 == a.U)) atomicAdd(a.n_done, 1);
+  }
+  if (all_fin)                         // the rest of the history: every slot stays where it is and repeats eos
+    for (int i = tid; i < (a.U - u - 1) * W; i += 256) {
+      const size_t h = ((size_t)(u + 1) * W + i) * batch + b;
+      a.backptr[h] = i % W;
+      a.labels[h] = eos;
+    }
 
   // the survivors' decoder states, 16 bytes per thread and trip
   const int row4 = a.row >> 2;
@@ -169,10 +202,12 @@ beam_backtrack_kernel(const int* __restrict__ backptr, const int* __restrict__ l
 
 using namespace slu;
 
-extern "C" int slu_beam_select(const float* logits, float* scores, const float* state_next, float* state, int32_t* step,
-                               int32_t* backptr, int32_t* labels, float* y_prev, int64_t ld_y, const float* embed_w,
-                               int64_t ld_ew, const float* embed_b, float* inp, int64_t ld_inp, int64_t E, int64_t W,
-                               int64_t batch, int64_t V, int64_t L, int64_t Dd, int64_t U, void* stream) {
+// both entry points; eos < 0 (slu_beam_select) has no finished hypotheses
+static int beam_select_launch(const float* logits, float* scores, const float* state_next, float* state, int32_t* step,
+                              int32_t* backptr, int32_t* labels, float* y_prev, int64_t ld_y, const float* embed_w,
+                              int64_t ld_ew, const float* embed_b, float* inp, int64_t ld_inp, int64_t E, int64_t W,
+                              int64_t batch, int64_t V, int64_t L, int64_t Dd, int64_t U, int64_t eos, int32_t* lengths,
+                              int32_t* n_done, void* stream) {
   SLU_REQUIRE(logits && scores && state_next && state && step && backptr && labels, "slu_beam_select: null pointer");
   SLU_REQUIRE(y_prev || inp, "slu_beam_select: null pointer (neither y_prev nor inp: nothing to feed the next step)");
   SLU_REQUIRE(!inp || (embed_w && embed_b && E > 0 && ld_inp >= E && ld_ew >= V),
@@ -191,10 +226,29 @@ extern "C" int slu_beam_select(const float* logits, float* scores, const float* 
   a.logits = logits; a.scores = scores; a.state_next = state_next; a.state = state; a.step = step; a.backptr = backptr;
   a.labels = labels; a.y_prev = y_prev; a.ld_y = ld_y; a.embed_w = embed_w; a.ld_ew = ld_ew; a.embed_b = embed_b;
   a.inp = inp; a.ld_inp = ld_inp; a.E = (int)E; a.W = (int)W; a.batch = (int)batch; a.V = (int)V; a.row = (int)(L * Dd);
-  a.U = (int)U;
+  a.U = (int)U; a.eos = (int)eos; a.lengths = lengths; a.n_done = n_done;
   hipLaunchKernelGGL(beam_select_kernel, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, a);
   SLU_CHECK_LAUNCH("beam_select_kernel");
   return SLU_OK;
+}
+
+extern "C" int slu_beam_select(const float* logits, float* scores, const float* state_next, float* state, int32_t* step,
+                               int32_t* backptr, int32_t* labels, float* y_prev, int64_t ld_y, const float* embed_w,
+                               int64_t ld_ew, const float* embed_b, float* inp, int64_t ld_inp, int64_t E, int64_t W,
+                               int64_t batch, int64_t V, int64_t L, int64_t Dd, int64_t U, void* stream) {
+  return beam_select_launch(logits, scores, state_next, state, step, backptr, labels, y_prev, ld_y, embed_w, ld_ew, embed_b,
+                            inp, ld_inp, E, W, batch, V, L, Dd, U, -1, nullptr, nullptr, stream);
+}
+
+extern "C" int slu_beam_select_eos(const float* logits, float* scores, const float* state_next, float* state,
+                                   int32_t* step, int32_t* backptr, int32_t* labels, float* y_prev, int64_t ld_y,
+                                   const float* embed_w, int64_t ld_ew, const float* embed_b, float* inp, int64_t ld_inp,
+                                   int64_t E, int64_t W, int64_t batch, int64_t V, int64_t L, int64_t Dd, int64_t U,
+                                   int64_t eos, int32_t* lengths, int32_t* n_done, void* stream) {
+  SLU_REQUIRE(lengths && n_done, "slu_beam_select_eos: null pointer (lengths, n_done)");
+  SLU_REQUIRE(eos >= 0 && eos < V, "slu_beam_select_eos: eos outside [0, V)");
+  return beam_select_launch(logits, scores, state_next, state, step, backptr, labels, y_prev, ld_y, embed_w, ld_ew, embed_b,
+                            inp, ld_inp, E, W, batch, V, L, Dd, U, eos, lengths, n_done, stream);
 }
 
 extern "C" int slu_beam_backtrack(const int32_t* backptr, const int32_t* labels, int64_t* out, float* one_hot, int64_t W,

@@ -208,6 +208,17 @@ def beam_search_mode():
     return mode
 
 
+def beam_eos_enabled():
+    """SLU_BEAM_EOS: "0" (default) — the reference's search: no notion of a finished hypothesis, every hypothesis is
+    expanded for all U steps and the log-probabilities of what follows <eos> count; "1" — hypotheses that have emitted
+    <eos> are finished (the rule in Seq2SeqDecoder.infer): Model.predict_intents / decode_intents / decode_nbest pass
+    eos = Sy_intent.index("<eos>") to the search SLU_BEAM_SEARCH selects, which stops once every utterance is done."""
+    v = os.environ.get("SLU_BEAM_EOS", "0")
+    if v not in ("0", "1"):
+        raise ValueError("SLU_BEAM_EOS=%r: expected 0 or 1" % (v,))
+    return v == "1"
+
+
 def _require_device(t):
     if not t.is_cuda:
         raise _lib.SluHipError("the HIP kernels are the only compute path of this package: move the "
@@ -630,7 +641,7 @@ class Seq2SeqDecoder(torch.nn.Module):
         _, log_p = self.teacher_forced(encoder_outputs.transpose(0, 1), y)
         return log_p
 
-    def infer(self, encoder_outputs, Sy, B=4, debug=False, y_lengths=None):
+    def infer(self, encoder_outputs, Sy, B=4, debug=False, y_lengths=None, eos=None, want_lengths=False):
         """Beam search of width B for argmax_y log p(y|x) (reference models.py:559-651; B = 1 is greedy search).
         -> (beam_scores (B, batch), beam (B, batch, U, |Sy|) one-hot), U = 200 or max(y_lengths).
         All B hypotheses of all utterances advance in ONE batched decoder step on the HIP kernels (rows w * batch +
@@ -642,10 +653,24 @@ class Seq2SeqDecoder(torch.nn.Module):
         evaluations (1e-6 on log-probabilities of ~-10: the search continues for U = 200 steps past <eos>, where many
         continuations are nearly equally (im)probable) — that is a property of comparing two fp32 implementations, not of
         the tie rule (tests/test_hip_seq2seq.py::test_tiny_seq2seq_beam_search_vs_reference: best hypothesis identical,
-        >= 95 % of all hypothesis labels, scores to 1e-4 relative)."""
+        >= 95 % of all hypothesis labels, scores to 1e-4 relative).
+
+        eos (a label index; None: the search above) gives the search FINISHED hypotheses — this project's own definition,
+        the reference has none.  Slot k of an utterance is finished at step u iff u > 0 and its label of step u - 1 is eos.
+        A finished source hypothesis has exactly one candidate, index src * W + 0, with label eos and the source's score
+        unchanged, bit for bit; its other W - 1 candidates are -inf.  Unfinished sources, the first step and the selection
+        are as above (every source has a finite candidate, so the W best are finite).  lengths (W, batch) int32 travel
+        with the hypotheses: the source's length if it was finished, else u + 1 (the <eos> counts; U if it never came).
+        An utterance whose W survivors are all finished is done — further steps would select the same W, in the same
+        order; the loop ends when every utterance is, and the remaining steps are filled with eos.
+        -> (beam_scores, beam[, lengths when want_lengths])."""
         _require_device(encoder_outputs)
+        if want_lengths and eos is None:
+            raise ValueError("want_lengths needs eos: without it every hypothesis has U labels")
         dev = encoder_outputs.device
         W, bsz, V = B, encoder_outputs.shape[0], len(Sy)
+        if eos is not None and not 0 <= eos < V:
+            raise ValueError("eos = %r outside [0, %d)" % (eos, V))
         U = 200 if y_lengths is None else max(y_lengths)
         names, tensors = self._params()
         P = {n: t.detach() for n, t in zip(names, tensors)}
@@ -672,6 +697,7 @@ class Seq2SeqDecoder(torch.nn.Module):
             scores = torch.zeros(W, bsz, dtype=torch.float32, device=dev)
             cols = torch.arange(bsz, device=dev)
             zeros_y = torch.zeros(R, V, dtype=torch.float32, device=dev)
+            lengths = torch.zeros(W, bsz, dtype=torch.int32, device=dev)
             for u in range(U):
                 _ops.decoder_step(P, keys, values, state, state_next, y_prev, q, inp0, att_w, gi, gh, None, drop, logits, u,
                                   (0.0, None, 0, 0, None, R * Dd))
@@ -680,14 +706,27 @@ class Seq2SeqDecoder(torch.nn.Module):
                 cand = (top_s - lse.unsqueeze(1)).view(W, bsz, W) + scores.unsqueeze(2)  # [src hypothesis, b, extension]
                 if u == 0:
                     cand[1:] = float("-inf")
+                top_i = top_i.view(W, bsz, W)
+                if eos is not None and u > 0:
+                    fin = hyp[:, :, u - 1] == eos                                       # (W, bsz) finished sources
+                    frozen = torch.full_like(cand, float("-inf"))
+                    frozen[:, :, 0] = scores                                            # the score itself, nothing added
+                    cand = torch.where(fin.unsqueeze(2), frozen, cand)
+                    top_i = torch.where(fin.unsqueeze(2), torch.full_like(top_i, eos), top_i)
                 flat = cand.permute(1, 0, 2).reshape(bsz, W * W)                        # candidate order: src major
                 best, pick = flat.sort(dim=1, descending=True, stable=True)
                 best, pick = best[:, :W].t().contiguous(), pick[:, :W].t()              # (W, bsz)
                 src, ext = pick // W, pick % W
-                label = top_i.view(W, bsz, W)[src, cols.unsqueeze(0), ext]              # (W, bsz)
+                label = top_i[src, cols.unsqueeze(0), ext]                              # (W, bsz)
                 hyp = hyp[src, cols.unsqueeze(0)]
                 hyp[:, :, u] = label
                 scores = best
+                if eos is not None:
+                    grown = torch.full_like(lengths, u + 1)
+                    lengths = torch.where(fin[src, cols.unsqueeze(0)], lengths[src, cols.unsqueeze(0)], grown) if u else grown
+                    if bool((label == eos).all()):                                      # every utterance is done
+                        hyp[:, :, u + 1:] = eos
+                        break
                 state = state_next.view(W, bsz, Lc, Dd)[src, cols.unsqueeze(0)].reshape(R, Lc, Dd)
                 y_prev = torch.zeros(R, V, dtype=torch.float32, device=dev)
                 y_prev.scatter_(1, label.reshape(R, 1), 1.0)
@@ -695,7 +734,7 @@ class Seq2SeqDecoder(torch.nn.Module):
                     print("step %d | best score of utterance 0: %1.2f" % (u, scores[0, 0].item()))
             beam = torch.zeros(W, bsz, U, V, dtype=torch.float32, device=dev)
             beam.scatter_(3, hyp.unsqueeze(3), 1.0)
-        return scores, beam
+        return (scores, beam, lengths) if want_lengths else (scores, beam)
 
 
     # steps per captured chunk of the device search: U = 200 is 25 replays; a U that is no multiple runs its last chunk to
@@ -704,22 +743,22 @@ class Seq2SeqDecoder(torch.nn.Module):
     SEARCH_CHUNK = 8
     SEARCH_PLANS = 4            # captured shapes kept (ragged evaluation batches differ in T), least recently used out
 
-    def _search_plan(self, P, dev, bsz, T, W, U, V):
-        """Static buffers (+ the captured chunk of SEARCH_CHUNK steps) of one search shape."""
+    def _search_plan(self, P, dev, bsz, T, W, U, V, eos=None):
+        """Static buffers (+ the captured chunk of SEARCH_CHUNK steps) of one search shape and eos label."""
         from slu_hip import pipeline as _pipeline
         use_graph = _pipeline.graphs_enabled()
-        key = (bsz, T, W, U, V, str(dev), use_graph, tuple((n, t.data_ptr(), tuple(t.shape)) for n, t in P.items()
+        key = (bsz, T, W, U, V, eos, str(dev), use_graph, tuple((n, t.data_ptr(), tuple(t.shape)) for n, t in P.items()
                                                           if torch.is_tensor(t)))
         plans = self.__dict__.setdefault("_search_plans", {})
         plan = plans.pop(key, None)
         if plan is None:
-            plan = self._build_search_plan(P, dev, bsz, T, W, U, V, use_graph)
+            plan = self._build_search_plan(P, dev, bsz, T, W, U, V, use_graph, eos)
             while len(plans) >= self.SEARCH_PLANS:
                 plans.pop(next(iter(plans)))
         plans[key] = plan                                   # most recently used last
         return plan
 
-    def _build_search_plan(self, P, dev, bsz, T, W, U, V, use_graph):
+    def _build_search_plan(self, P, dev, bsz, T, W, U, V, use_graph, eos=None):
         from slu_hip import pipeline as _pipeline
         Kd, Vd = P["key.weight"].shape[0], P["value.weight"].shape[0]
         Lc, Dd = P["initial_state"].shape
@@ -730,10 +769,16 @@ class Seq2SeqDecoder(torch.nn.Module):
         b = {"keys": f(T, R, Kd), "values": f(T, R, Vd), "state": f(R, Lc, Dd), "state_next": f(R, Lc, Dd),
              "q": f(R, Kd), "inp0": f(R, E + Vd), "att_w": f(R, T), "logits": f(R, V), "gi": f(R, 3 * Dd),
              "gh": f(Lc, R, 3 * Dd), "drop": [f(R, Dd) for _ in range(Lc - 1)],
-             # step counters (bsz int32) and running scores (W * bsz fp32) share one buffer: ONE fill re-arms a search
-             "ctl": i32(bsz + R), "backptr": i32(U, W, bsz), "labels": i32(U, W, bsz), "graph": None}
+             # step counters (bsz int32), running scores (W * bsz fp32), hypothesis lengths (W * bsz int32) and the
+             # count of finished utterances (1 int32) share one buffer: ONE fill re-arms a search
+             "ctl": i32(bsz + 2 * R + 1), "backptr": i32(U, W, bsz), "labels": i32(U, W, bsz), "graph": None}
         b["ctl"].zero_()
-        b["step"], b["scores"] = b["ctl"][:bsz], b["ctl"][bsz:].view(torch.float32).view(W, bsz)
+        b["step"], b["scores"] = b["ctl"][:bsz], b["ctl"][bsz:bsz + R].view(torch.float32).view(W, bsz)
+        b["lengths"], b["n_done"] = b["ctl"][bsz + R:bsz + 2 * R].view(W, bsz), b["ctl"][bsz + 2 * R:]
+        if eos is not None:
+            # n_done after every chunk, read behind the next chunk's launches (search)
+            b["n_done_host"] = torch.empty(-(-U // self.SEARCH_CHUNK), dtype=torch.int32, pin_memory=True)
+        fin = {} if eos is None else {"eos": eos, "lengths": b["lengths"], "n_done": b["n_done"]}
         embed = (P["embed.weight"], P["embed.bias"], b["inp0"])
 
         def chunk():
@@ -743,7 +788,7 @@ class Seq2SeqDecoder(torch.nn.Module):
                                   b["att_w"], b["gi"], b["gh"], None, b["drop"], b["logits"], 0,
                                   (0.0, None, 0, 0, None, R * Dd))
                 _ops.beam_select(b["logits"], b["scores"], b["state_next"], b["state"], b["step"], b["backptr"],
-                                 b["labels"], None, embed)
+                                 b["labels"], None, embed, **fin)
         b["chunk"] = chunk
         if use_graph:
             # warm-up on the capture stream (lazy initialisation happens outside the capture), on zeroed operands
@@ -761,17 +806,30 @@ class Seq2SeqDecoder(torch.nn.Module):
             b["graph"] = graph
         return b
 
-    def search(self, encoder_outputs, Sy, B=4, y_lengths=None, want_beam=False):
+    def search(self, encoder_outputs, Sy, B=4, y_lengths=None, want_beam=False, eos=None, want_lengths=False):
         """infer's beam search with the books kept on the device -> (scores (B, batch) float32, labels (B, batch, U) int64)
         [, beam (B, batch, U, |Sy|) one-hot float32 when want_beam], U = 200 or max(y_lengths): the hypotheses, bit-equal
         scores and tie rule of infer (tests/test_hip_beam.py).  Per step: ops.decoder_step (its embedding GEMM left out:
         slu_beam_select writes embed.weight[:, label] + embed.bias, what that GEMM gives for a one-hot row) and ONE
         slu_beam_select; after the last step ONE slu_beam_backtrack.  No torch op and no host read in between; with
         SLU_GRAPHS=1 the steps are a hipGraph of SEARCH_CHUNK steps replayed ceil(U / SEARCH_CHUNK) times, captured once
-        per shape and parameter storage (the graph reads the parameters in place: optimiser updates are seen)."""
+        per shape and parameter storage (the graph reads the parameters in place: optimiser updates are seen).
+
+        eos (a label index; None: the search above): infer's finished hypotheses, kept by slu_beam_select_eos — the same
+        scores, labels and lengths as infer(eos=...), bit for bit.  The kernel counts the utterances that are done; the
+        host reads that count (4 bytes, through pinned memory) once per chunk, behind the NEXT chunk's launches, and
+        stops when it equals the batch: at most one chunk more than needed is launched, and its steps change nothing
+        (a done utterance's slu_beam_select_eos returns at once; the decoder steps touch scratch).  labels / beam keep
+        their (..., U[, V]) shapes, filled with eos.  -> (scores, labels[, beam][, lengths (B, batch) int32 when
+        want_lengths]).  self.last_search_steps = the decoder steps this call launched (without eos: SEARCH_CHUNK *
+        ceil(U / SEARCH_CHUNK))."""
         _require_device(encoder_outputs)
+        if want_lengths and eos is None:
+            raise ValueError("want_lengths needs eos: without it every hypothesis has U labels")
         dev = encoder_outputs.device
         W, bsz, V = B, encoder_outputs.shape[0], len(Sy)
+        if eos is not None and not 0 <= eos < V:
+            raise ValueError("eos = %r outside [0, %d)" % (eos, V))
         U = 200 if y_lengths is None else max(y_lengths)
         names, tensors = self._params()
         P = {n: t.detach() for n, t in zip(names, tensors)}
@@ -782,24 +840,36 @@ class Seq2SeqDecoder(torch.nn.Module):
             enc = encoder_outputs.detach().float().transpose(0, 1).contiguous()          # (T, bsz, C)
             T = enc.shape[0]
             enc2 = enc.view(T * bsz, -1)
-            p = self._search_plan(P, dev, bsz, T, W, U, V)
+            p = self._search_plan(P, dev, bsz, T, W, U, V, eos)
             R = W * bsz
             # set-up as in infer: keys / values once, replicated per hypothesis; initial state; all-zero first input
             p["keys"].view(T, W, bsz, Kd).copy_(_ops.gemm(enc2, P["key.weight"].t(), P["key.bias"]).view(T, 1, bsz, Kd).expand(T, W, bsz, Kd))
             p["values"].view(T, W, bsz, Vd).copy_(_ops.gemm(enc2, P["value.weight"].t(), P["value.bias"]).view(T, 1, bsz, Vd).expand(T, W, bsz, Vd))
             _ops.broadcast_rows(P["initial_state"].contiguous().view(-1), p["state"].view(R, -1))
             _ops.broadcast_rows(P["embed.bias"], p["inp0"][:, :E])                        # embed(0) = bias
-            p["ctl"].zero_()                                                            # step counters and scores
+            p["ctl"].zero_()                                            # step counters, scores, lengths, n_done
             labels = torch.empty(W, bsz, U, dtype=torch.int64, device=dev)
             beam = torch.empty(W, bsz, U, V, dtype=torch.float32, device=dev) if want_beam else None
-            for _ in range(-(-U // self.SEARCH_CHUNK)):
+            chunks, read = -(-U // self.SEARCH_CHUNK), None
+            for i in range(chunks):
                 if p["graph"] is not None:
                     p["graph"].replay()
                 else:
                     p["chunk"]()
+                self.last_search_steps = (i + 1) * self.SEARCH_CHUNK
+                if eos is None or i + 1 == chunks:
+                    continue
+                if read is not None:                                    # chunk i - 1's count, while chunk i runs
+                    read.synchronize()
+                    if int(p["n_done_host"][i - 1]) == bsz:
+                        break
+                p["n_done_host"][i:i + 1].copy_(p["n_done"], non_blocking=True)
+                read = torch.cuda.Event()
+                read.record()
             _ops.beam_backtrack(p["backptr"], p["labels"], labels, beam)
             scores = p["scores"].clone()
-        return (scores, labels, beam) if want_beam else (scores, labels)
+            out = (scores, labels) + ((beam,) if want_beam else ())
+        return out + (p["lengths"].clone(),) if want_lengths else out
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1405,13 +1475,48 @@ class Model(torch.nn.Module):
         h = self._intent_features_tm(x).contiguous()
         if self.seq2seq:                                         # beam search, width 4 (models.py:848-851)
             if beam_search_mode() == "host":
-                return self.decoder.infer(h.transpose(0, 1), self.Sy_intent, B=4)
-            scores, _, beam = self.decoder.search(h.transpose(0, 1), self.Sy_intent, B=4, want_beam=True)
+                return self.decoder.infer(h.transpose(0, 1), self.Sy_intent, B=4, **self._beam_eos())
+            scores, _, beam = self.decoder.search(h.transpose(0, 1), self.Sy_intent, B=4, want_beam=True, **self._beam_eos())
             return scores, beam
         cls = self.intent_layers[-2]
         _, logits, pred, _, _ = _ops.cls_maxpool_ce_fwd(h.detach(), cls.weight.detach(), cls.bias.detach(), None,
                                                         tuple(self.values_per_slot), False)
         return logits, pred
+
+    def _beam_eos(self):
+        """The search's eos argument under SLU_BEAM_EOS (nothing when the knob is off: the calls are today's)."""
+        return {"eos": self.Sy_intent.index("<eos>")} if beam_eos_enabled() else {}
+
+    def decode_nbest(self, x, n=4):
+        """seq2seq: -> list (batch) of lists of (string, score): the n <= 4 best hypotheses of the width-4 device search
+        (Seq2SeqDecoder.search), best first; score = the hypothesis' log-probability as the search ranks it.  With
+        SLU_BEAM_EOS=1 a hypothesis is cut at its length before the cleaning decode_intents applies (so entry 0 is
+        decode_intents' string); without, the whole row is cleaned.  Labels, scores and lengths cross to the host in one
+        copy."""
+        if not self.seq2seq:
+            raise ValueError("decode_nbest: the n-best list comes from the seq2seq decoder's beam search")
+        W = 4
+        if not 1 <= n <= W:
+            raise ValueError("decode_nbest: n = %r outside [1, %d]" % (n, W))
+        fin = self._beam_eos()
+        h = self._intent_features_tm(x).contiguous()
+        out = self.decoder.search(h.transpose(0, 1), self.Sy_intent, B=W, want_lengths=bool(fin), **fin)
+        scores, labels = out[0], out[1]
+        U = labels.shape[2]
+        lengths = out[2] if fin else torch.full_like(scores, U, dtype=torch.int32)
+        # float64 holds all three exactly
+        packed = torch.cat([labels[:n].double(), lengths[:n].double().unsqueeze(2), scores[:n].double().unsqueeze(2)],
+                           dim=2).cpu()
+        S = self.Sy_intent
+        res = []
+        for b in range(packed.shape[1]):
+            rows = []
+            for w in range(n):
+                row = packed[w, b].tolist()
+                text = "".join(S[int(c)] for c in row[:int(row[U])]).lstrip("<sos>").rstrip("<eos>")
+                rows.append((text, row[U + 1]))
+            res.append(rows)
+        return res
 
     def decode_intents(self, x):
         """-> list (batch) of lists (slots) of slot-value strings (reference models.py:853-865)."""
@@ -1419,7 +1524,7 @@ class Model(torch.nn.Module):
             # best hypothesis of every utterance (models.py:866-874) from its labels (batch, U): the string
             # one_hot_to_string builds, without the one-hot beam crossing to the host
             h = self._intent_features_tm(x).contiguous()
-            _, labels = self.decoder.search(h.transpose(0, 1), self.Sy_intent, B=4)
+            _, labels = self.decoder.search(h.transpose(0, 1), self.Sy_intent, B=4, **self._beam_eos())
             S = self.Sy_intent
             return ["".join([S[c] for c in row]).lstrip("<sos>").rstrip("<eos>") for row in labels[0].cpu().tolist()]
         _, pred = self.predict_intents(x)

@@ -48,6 +48,8 @@ SIGNATURES = {
     "slu_broadcast_rows_f32": (c_int, [vp, vp, c_i64, c_i64, c_i64, vp]),
     "slu_beam_select": (c_int, [vp, vp, vp, vp, vp, vp, vp, vp, c_i64, vp, c_i64, vp, vp, c_i64, c_i64, c_i64, c_i64, c_i64,
                                 c_i64, c_i64, c_i64, vp]),
+    "slu_beam_select_eos": (c_int, [vp, vp, vp, vp, vp, vp, vp, vp, c_i64, vp, c_i64, vp, vp, c_i64, c_i64, c_i64, c_i64,
+                                    c_i64, c_i64, c_i64, c_i64, c_i64, vp, vp, vp]),
     "slu_beam_backtrack": (c_int, [vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, vp]),
     "slu_sinc_filters_fwd": (c_int, [vp, vp, vp, c_i64, c_i64, c_f64, vp]),
     "slu_sinc_filters_bwd": (c_int, [vp, vp, vp, vp, vp, c_i64, c_i64, c_f64, vp]),

@@ -1691,12 +1691,15 @@ def broadcast_rows(src, dst2d):
                "slu_broadcast_rows_f32")
 
 
-def beam_select(logits, scores, state_next, state, step, backptr, labels, y_prev=None, embed=None):
+def beam_select(logits, scores, state_next, state, step, backptr, labels, y_prev=None, embed=None, eos=None, lengths=None,
+                n_done=None):
     """The beam bookkeeping of one decoding step in one launch (csrc/slu_beam.hip; include/slu_hip.h has the rule).
     logits (W * batch, V); scores (W, batch) fp32, in place; state_next -> state (W * batch, L, Dd), two buffers; step
     (batch) int32 device counters (read, then advanced); backptr / labels (U, W, batch) int32 history planes.
     Next input: y_prev (W * batch, V) gets the one-hot rows, and / or embed = (weight (E, V), bias (E), inp (W * batch,
-    >= E)) gets the embedded label directly."""
+    >= E)) gets the embedded label directly.
+    eos (a label index) turns on finished hypotheses (slu_beam_select_eos): lengths (W, batch) int32 hypothesis lengths, in
+    place; n_done (1) int32 counts the utterances whose search has ended.  eos=None is slu_beam_select."""
     L = _lib.load()
     W, batch = scores.shape
     R, V = logits.shape
@@ -1717,6 +1720,17 @@ def beam_select(logits, scores, state_next, state, step, backptr, labels, y_prev
         assert inp.shape[0] == R and inp.shape[1] >= E and inp.stride(1) == 1
     if y_prev is not None:
         assert tuple(y_prev.shape) == (R, V) and y_prev.stride(1) == 1
+    if eos is not None:
+        assert tuple(lengths.shape) == (W, batch) and lengths.dtype == n_done.dtype == torch.int32
+        assert lengths.is_contiguous() and n_done.numel() == 1
+        _lib.check(L.slu_beam_select_eos(logits.data_ptr(), scores.data_ptr(), state_next.data_ptr(), state.data_ptr(),
+                                         step.data_ptr(), backptr.data_ptr(), labels.data_ptr(), _ptr(y_prev),
+                                         0 if y_prev is None else y_prev.stride(0), _ptr(ew),
+                                         0 if ew is None else ew.stride(0), _ptr(eb), _ptr(inp),
+                                         0 if inp is None else inp.stride(0), E, W, batch, V, Lc, Dd, U, int(eos),
+                                         lengths.data_ptr(), n_done.data_ptr(), _stream()), "slu_beam_select_eos")
+        return
+    assert lengths is None and n_done is None, "lengths / n_done go with eos"
     _lib.check(L.slu_beam_select(logits.data_ptr(), scores.data_ptr(), state_next.data_ptr(), state.data_ptr(),
                                  step.data_ptr(), backptr.data_ptr(), labels.data_ptr(), _ptr(y_prev),
                                  0 if y_prev is None else y_prev.stride(0), _ptr(ew), 0 if ew is None else ew.stride(0),

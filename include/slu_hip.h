@@ -539,11 +539,29 @@ int slu_broadcast_rows_f32(const float* src, float* dst, int64_t ld_dst, int64_t
  *                      (the embedding Linear applied to that one-hot row, bit for bit).
  *                      SLU_ERR_UNSUPPORTED unless 1 <= W <= 8, V >= W, Dd % 4 == 0 and 16-byte aligned state buffers.
  *   slu_beam_backtrack after the last step: out (W, batch, U) int64 label sequences, final rank w first; one_hot (NULL or
- *                      (W, batch, U, V) float32) is written whole (zeros and ones).  3 * U * W * 4 bytes of LDS (<= 60 KiB). */
+ *                      (W, batch, U, V) float32) is written whole (zeros and ones).  3 * U * W * 4 bytes of LDS (<= 60 KiB).
+ *   slu_beam_select_eos (ABI 10 as well: one more entry point, nothing existing changed) slu_beam_select with FINISHED
+ *                      hypotheses — this project's own rule; the reference's search has none and expands past <eos>.
+ *                      eos in [0, V) is the label that ends a hypothesis.  Slot k of utterance b is finished at step u iff
+ *                      u > 0 and labels[u - 1, k, b] == eos.  A finished source src has ONE candidate: index src * W + 0,
+ *                      label eos, score = scores[src] copied bit for bit (no lse arithmetic, nothing added); its other
+ *                      W - 1 candidates are -inf.  Unfinished sources, the first step and the selection are as above (every
+ *                      source contributes at least one finite candidate, so the W best are finite).
+ *                      lengths (W, batch) int32 travels with the hypotheses: lengths[k] = the old lengths[src] if src was
+ *                      finished, else u + 1 (the <eos> counts; a hypothesis that never emits it ends with U).  Zero it
+ *                      with step.  When all W survivors are finished, the same launch fills planes u + 1 .. U - 1 of
+ *                      backptr / labels with k / eos, writes step[b] = U (later calls do nothing for b) and adds 1 to
+ *                      *n_done (int32, zero it with step); an utterance that reaches u + 1 == U unfinished adds 1 too:
+ *                      the search is over when *n_done == batch.  slu_beam_backtrack reads the planes unchanged.
+ *                      SLU_ERR_INVALID_ARG for eos outside [0, V) and NULL lengths / n_done; else as slu_beam_select. */
 int slu_beam_select(const float* logits, float* scores, const float* state_next, float* state, int32_t* step,
                     int32_t* backptr, int32_t* labels, float* y_prev, int64_t ld_y, const float* embed_w, int64_t ld_ew,
                     const float* embed_b, float* inp, int64_t ld_inp, int64_t E, int64_t W, int64_t batch, int64_t V,
                     int64_t L, int64_t Dd, int64_t U, void* stream);
+int slu_beam_select_eos(const float* logits, float* scores, const float* state_next, float* state, int32_t* step,
+                        int32_t* backptr, int32_t* labels, float* y_prev, int64_t ld_y, const float* embed_w, int64_t ld_ew,
+                        const float* embed_b, float* inp, int64_t ld_inp, int64_t E, int64_t W, int64_t batch, int64_t V,
+                        int64_t L, int64_t Dd, int64_t U, int64_t eos, int32_t* lengths, int32_t* n_done, void* stream);
 int slu_beam_backtrack(const int32_t* backptr, const int32_t* labels, int64_t* out, float* one_hot, int64_t W,
                        int64_t batch, int64_t U, int64_t V, void* stream);
 
