@@ -38,9 +38,15 @@ struct GruFwdParams {
   float* out;             // (T, B, D*H)
   float* reserve;         // [D][T][NBT][NW][5][64][4] or null
   int T, B, D;
+  const int* lengths;     // (B) valid steps per sequence: read by the LEN instantiations only
 };
 
-template <int H>
+// LEN (slu_gru_seq_fwd_len): `lengths` (B) gives every sequence its own number of valid steps n_b (clamped to [1, T]).
+// The whole change is one predicate per owned element: h_t = 0 where t >= n_b.  Direction 0 therefore writes zeros from
+// step n_b on; direction 1 keeps h = 0 (in registers and in LDS) while it walks through the padding and starts the
+// sequence at t = n_b - 1 from h = 0.  What was computed from gx rows at t >= n_b (NaN included) is dropped by that
+// select, and rows of the MFMA tile do not mix, so no padded value reaches a result.  LEN = false is the kernel as it was.
+template <int H, bool LEN = false>
 __global__ void __launch_bounds__(H * 4)
 gru_seq_fwd_kernel(const GruFwdParams p) {
   constexpr int NW = H / 16;      // waves
@@ -77,6 +83,11 @@ gru_seq_fwd_kernel(const GruFwdParams p) {
     const int b = b0 + 4 * kg + r;
     rowok[r] = b < B;
     grow[r] = (size_t)(rowok[r] ? b : 0);
+  }
+  int nlen[4] = {0, 0, 0, 0};   // LEN: valid steps of the lane's four sequences (0 for rows past B)
+  if constexpr (LEN) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) nlen[r] = rowok[r] ? min(max(p.lengths[grow[r]], 1), T) : 0;
   }
   const size_t gx_ts = (size_t)B * D * 3 * H;      // stride of t in gx
   const size_t out_ts = (size_t)B * D * H;
@@ -136,6 +147,7 @@ gru_seq_fwd_kernel(const GruFwdParams p) {
       qq[r] = an[r] + bhn;
       nn[r] = act_tanh(gn[r] + rr[r] * qq[r]);
       hn[r] = (1.0f - zz[r]) * nn[r] + zz[r] * hprev[r];
+      if constexpr (LEN) hn[r] = (t < nlen[r]) ? hn[r] : 0.0f;
     }
     float* __restrict__ hnext = &hbuf[cur ^ 1][0];
 #pragma unroll
@@ -172,7 +184,7 @@ gru_seq_fwd_kernel(const GruFwdParams p) {
 // v_permlane32_swap folds the two k-halves; the lower half-wave then finishes sequences 0, 1 and the
 // upper one sequences 2, 3 (gates, blend, stores).  Reserve layout and results interoperate with the
 // 16-sequence kernels (summation order differs: not bit-identical between the variants).
-template <int H>
+template <int H, bool LEN = false>
 __global__ void __launch_bounds__(H * 2)
 gru_seq_fwd4_kernel(const GruFwdParams p, const int NBT16) {
   constexpr int NW16 = H / 16;   // waves of the 16-sequence layout (reserve indexing)
@@ -212,6 +224,11 @@ gru_seq_fwd4_kernel(const GruFwdParams p, const int NBT16) {
     const int b = b0 + 2 * half + e;
     rowok[e] = b < B;
     grow[e] = (size_t)(rowok[e] ? b : 0);
+  }
+  int nlen[2] = {0, 0};         // LEN: as in gru_seq_fwd_kernel
+  if constexpr (LEN) {
+#pragma unroll
+    for (int e = 0; e < 2; ++e) nlen[e] = rowok[e] ? min(max(p.lengths[grow[e]], 1), T) : 0;
   }
   const size_t gx_ts = (size_t)B * D * 3 * H;
   const size_t out_ts = (size_t)B * D * H;
@@ -289,6 +306,7 @@ gru_seq_fwd4_kernel(const GruFwdParams p, const int NBT16) {
       qq[e] = hq[e] + bhn;
       nn[e] = act_tanh(gn[e] + rr[e] * qq[e]);
       hn[e] = (1.0f - zz[e]) * nn[e] + zz[e] * hprev[e];
+      if constexpr (LEN) hn[e] = (t < nlen[e]) ? hn[e] : 0.0f;
     }
     float* __restrict__ hnext = &hbuf[cur ^ 1][0];
 #pragma unroll
@@ -713,7 +731,7 @@ extern "C" int slu_gru_seq_fwd(const float* gx, const float* w_hh_fwd, const flo
   if (rc) return rc;
   GruFwdParams p;
   p.gx = gx; p.w_hh[0] = w_hh_fwd; p.w_hh[1] = w_hh_rev; p.b_hh[0] = b_hh_fwd; p.b_hh[1] = b_hh_rev;
-  p.out = out; p.reserve = reserve; p.T = (int)T; p.B = (int)B; p.D = (int)D;
+  p.out = out; p.reserve = reserve; p.T = (int)T; p.B = (int)B; p.D = (int)D; p.lengths = nullptr;
   hipStream_t st = (hipStream_t)stream;
   if (!gru_persistent(H)) return gru_step_fwd(gx, p.w_hh, p.b_hh, out, reserve, T, B, H, D, st);
   if (gru_use_seq4(B, H, D)) {
@@ -732,6 +750,41 @@ extern "C" int slu_gru_seq_fwd(const float* gx, const float* w_hh_fwd, const flo
     default: hipLaunchKernelGGL(gru_seq_fwd_kernel<128>, grid, dim3(512), 0, st, p); break;
   }
   SLU_CHECK_LAUNCH("gru_seq_fwd_kernel");
+  return SLU_OK;
+}
+
+extern "C" int slu_gru_seq_fwd_len(const float* gx, const float* w_hh_fwd, const float* w_hh_rev,
+                                   const float* b_hh_fwd, const float* b_hh_rev, float* out,
+                                   const int32_t* lengths, int64_t T, int64_t B, int64_t H, int64_t D,
+                                   void* stream) {
+  SLU_REQUIRE(gx && w_hh_fwd && b_hh_fwd && out, "slu_gru_seq_fwd_len: null pointer");
+  SLU_REQUIRE(lengths, "slu_gru_seq_fwd_len: null lengths");
+  SLU_REQUIRE(D == 1 || (w_hh_rev && b_hh_rev), "slu_gru_seq_fwd_len: reverse weights missing");
+  int rc = gru_check("slu_gru_seq_fwd_len", T, B, H, D);
+  if (rc) return rc;
+  if (!gru_persistent(H))
+    SLU_FAIL(SLU_ERR_UNSUPPORTED, "slu_gru_seq_fwd_len: hidden size %lld has no length-aware kernel (16, 32, 64 or 128)",
+             (long long)H);
+  GruFwdParams p;
+  p.gx = gx; p.w_hh[0] = w_hh_fwd; p.w_hh[1] = w_hh_rev; p.b_hh[0] = b_hh_fwd; p.b_hh[1] = b_hh_rev;
+  p.out = out; p.reserve = nullptr; p.T = (int)T; p.B = (int)B; p.D = (int)D; p.lengths = (const int*)lengths;
+  hipStream_t st = (hipStream_t)stream;
+  if (gru_use_seq4(B, H, D)) {
+    dim3 grid4((unsigned)cdiv(B, 4), (unsigned)D);
+    const int nbt16 = (int)cdiv(B, 16);
+    if (H == 64) hipLaunchKernelGGL((gru_seq_fwd4_kernel<64, true>), grid4, dim3(128), 0, st, p, nbt16);
+    else hipLaunchKernelGGL((gru_seq_fwd4_kernel<128, true>), grid4, dim3(256), 0, st, p, nbt16);
+    SLU_CHECK_LAUNCH("gru_seq_fwd4_kernel<LEN>");
+    return SLU_OK;
+  }
+  dim3 grid((unsigned)cdiv(B, 16), (unsigned)D);
+  switch (H) {
+    case 16: hipLaunchKernelGGL((gru_seq_fwd_kernel<16, true>), grid, dim3(64), 0, st, p); break;
+    case 32: hipLaunchKernelGGL((gru_seq_fwd_kernel<32, true>), grid, dim3(128), 0, st, p); break;
+    case 64: hipLaunchKernelGGL((gru_seq_fwd_kernel<64, true>), grid, dim3(256), 0, st, p); break;
+    default: hipLaunchKernelGGL((gru_seq_fwd_kernel<128, true>), grid, dim3(512), 0, st, p); break;
+  }
+  SLU_CHECK_LAUNCH("gru_seq_fwd_kernel<LEN>");
   return SLU_OK;
 }
 

@@ -227,6 +227,14 @@ def one_hot(letters, S):
     return out
 
 
+def mask_padding_enabled():
+    """SLU_MASK_PADDING: "0" (default) — batches are (x, y); "1" — CollateWavsSLU adds the per-utterance sample counts."""
+    v = os.environ.get("SLU_MASK_PADDING", "0")
+    if v not in ("0", "1"):
+        raise ValueError("SLU_MASK_PADDING=%r: expected 0 or 1" % (v,))
+    return v == "1"
+
+
 class CollateWavsSLU:
     """list of (waveform, [action, object, location]) -> (x (B, T_max) float32 zero-padded at the end,
     y_intent (B, 3) int64), as reference data.py:344-376.  seq2seq: the labels are <sos> ... <eos> index
@@ -235,7 +243,7 @@ class CollateWavsSLU:
     pins it (pin_memory=True, in the parent process — never in a forked worker) so that the H2D copy of the
     look-ahead slots is asynchronous."""
 
-    def __init__(self, Sy_intent, seq2seq, pad_multiple=None):
+    def __init__(self, Sy_intent, seq2seq, pad_multiple=None, mask_padding=None):
         self.Sy_intent = Sy_intent
         self.num_labels = len(self.Sy_intent)
         self.seq2seq = seq2seq
@@ -246,12 +254,23 @@ class CollateWavsSLU:
         # Off by default: the extra trailing zeros are seen by the recurrences, i.e. it is not the
         # reference's batch any more.
         self.pad_multiple = int(os.environ.get("SLU_PAD_TO_MULTIPLE", "0")) if pad_multiple is None else pad_multiple
+        # Opt-in (SLU_MASK_PADDING=1): also return the utterances' own sample counts, (x, y, lengths int32 (B)) — taken
+        # before the rounding above — so that evaluation can run padding-invariant (Model.eval_group(lengths=...):
+        # every utterance's logits are those of the utterance alone, whatever it was batched with).  The training loops
+        # drop them (training.Trainer).  Off: the batch is the reference's 2-tuple.
+        self.mask_padding = mask_padding_enabled() if mask_padding is None else bool(mask_padding)
 
     def __call__(self, batch):
         T = max(len(x) for x, _ in batch)
         if self.pad_multiple > 1:
             T = -(-T // self.pad_multiple) * self.pad_multiple
         x = _pad_waveforms([xi for xi, _ in batch], T)
+        if self.mask_padding:
+            x, y = self._labels(batch, x)
+            return x, y, torch.tensor([len(xi) for xi, _ in batch], dtype=torch.int32)
+        return self._labels(batch, x)
+
+    def _labels(self, batch, x):
         if self.seq2seq:
             U = max(len(yi) for _, yi in batch)
             idx = torch.full((len(batch), U), self.EOS, dtype=torch.int64)

@@ -873,6 +873,72 @@ class Seq2SeqDecoder(torch.nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------
+# per-utterance lengths (padding-invariant inference; the definition is in include/slu_hip.h and DESIGN.md section 7)
+# ------------------------------------------------------------------------------------------------
+def _host_lengths(lengths, B, T):
+    """lengths (list / tensor of B sample counts) -> list of B Python ints, each in [1, T]; ValueError otherwise.  Host
+    arithmetic only: a bad length never reaches a launch."""
+    if torch.is_tensor(lengths):
+        if lengths.is_floating_point() or lengths.dtype == torch.bool:
+            raise ValueError("lengths: expected integers, got %s" % lengths.dtype)
+        lengths = lengths.detach().cpu().reshape(-1).tolist() if lengths.dim() <= 1 else lengths
+    if torch.is_tensor(lengths) or not hasattr(lengths, "__len__"):
+        raise ValueError("lengths: expected a 1-D sequence of %d sample counts" % B)
+    vals = list(lengths)
+    if len(vals) != B:
+        raise ValueError("lengths: %d entries for a batch of %d" % (len(vals), B))
+    for v in vals:
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError("lengths: expected integers, got %r" % (v,))
+        if not 1 <= int(v) <= T:
+            raise ValueError("lengths: %d outside [1, %d] (the batch has %d samples per row)" % (int(v), T, T))
+    return [int(v) for v in vals]
+
+
+def _stage_lengths(stages, lengths):
+    """[valid lengths after stage 0, after stage 1, ...] for `lengths` valid frames at the first stage's input."""
+    out, cur = [], list(lengths)
+    for st in stages:
+        cur = [st.out_len(n) for n in cur]
+        out.append(cur)
+    return out
+
+
+def _check_len_stages(stages):
+    """The length-aware recurrence exists for the persistent hidden sizes only: refuse any other on the host."""
+    for st in stages:
+        if isinstance(st, _RnnStage) and st.gru.hidden_size not in _ops.LEN_HIDDEN_SIZES:
+            raise ValueError("lengths: hidden size %d of %s has no length-aware recurrence kernel (supported: %s)"
+                             % (st.gru.hidden_size, getattr(st.gru, "name", "a GRU layer"),
+                                ", ".join(map(str, _ops.LEN_HIDDEN_SIZES))))
+
+
+def _run_stages_len(stages, h, lengths):
+    """Length-aware evaluation of `stages` (no dropout, no autograd): h = the first stage's input, whose frames at or
+    beyond lengths[b] are zero; -> (output, its valid lengths).  The host computes every stage's valid lengths
+    (_stage_lengths) and sends them to the device in ONE int32 table.  Always the exact fp32 kernels — slu_wconv_fwd,
+    slu_gemm_f32, slu_gru_seq_fwd_len — whatever SLU_FROZEN_MATH says: both sides of the invariant (an utterance in a
+    padded batch / alone) then differ by summation order only.  A split-precision length-aware path does not exist."""
+    rows = [list(lengths)]
+    for st in stages:
+        if isinstance(st, _ConvStage):
+            rows.append([st.conv_len(n) for n in rows[-1]])      # valid frames of the raw convolution
+            rows.append([st.out_len(n) for n in rows[-2]])
+        else:
+            rows.append([st.out_len(n) for n in rows[-1]])
+    table = torch.tensor(rows, dtype=torch.int32).to(h.device, non_blocking=True)
+    k = 0
+    for st in stages:
+        if isinstance(st, _ConvStage):
+            h = st.run_len(h, table[k + 1])
+            k += 2
+        else:
+            h = st.run_len(h, table[k])
+            k += 1
+    return h, rows[-1], table[k]
+
+
+# ------------------------------------------------------------------------------------------------
 # fused stage plan
 # ------------------------------------------------------------------------------------------------
 class _ConvStage:
@@ -887,6 +953,32 @@ class _ConvStage:
 
     def parameters(self):
         return list(self.conv.parameters())
+
+    def conv_len(self, n):
+        """Valid frames of the raw convolution of a row of n valid frames (padding k // 2)."""
+        k = self.conv.Filt_dim if self.is_sinc else self.conv.kernel_size
+        return _ops.conv_out_len(n, k, self.conv.stride)
+
+    def out_len(self, n):
+        """Valid frames of the block's output: ceil(conv_len / pool)."""
+        return -(-self.conv_len(n) // self.pool)
+
+    def run_len(self, h, n_conv):
+        """Length-aware evaluation (exact fp32, no dropout): h = (B, T) waveform or channels-last (B, L, C) with a zero
+        tail, n_conv = int32 device lengths of the raw convolution's output.  The existing convolution call with pool 1,
+        slope 1 and no abs (convolution + bias), then slu_pool_act_len_fwd: abs / max-pool over the valid frames /
+        activation, zero beyond — channels-last, or time-major on the last CNN block."""
+        with torch.no_grad():
+            if h.dim() == 2:
+                h = h.unsqueeze(2)
+            h = h.contiguous()
+            B, l_in, c_in = h.shape
+            if self.is_sinc:
+                w, bias = self.conv.filters().view(self.conv.N_filt, 1, self.conv.Filt_dim), None
+            else:
+                w, bias = self.conv.weight.detach(), self.conv.bias.detach()
+            raw, _, _ = _ops.wconv_fwd(h, w, bias, B, l_in, c_in, self.conv.stride, False, 1, 1.0, False, False)
+            return _ops.pool_act_len_fwd(raw, n_conv, self.pool, self.do_abs, self.slope, self.time_major)
 
     def _frozen_cache(self, nsplit):
         """What a FROZEN block recomputed per call in round 2: the Sinc filterbank and the filters packed in MFMA
@@ -990,6 +1082,27 @@ class _RnnStage:
         """out_planes: the consumer is another frozen split-precision GRU layer: hand over bf16 planes."""
         p, mask, seed, offset = _dropout_args(self.drop_name, self.site, self.p, training)
         return self.gru.run_time_major(xt, p, mask, seed, offset, self.method, self.factor, out_planes)
+
+    def out_len(self, n):
+        """Valid frames behind the layer's Downsample: ceil(n / factor) for every method (the GRU keeps n)."""
+        return -(-n // self.factor)
+
+    def run_len(self, xt, n_in):
+        """Length-aware evaluation (exact fp32, no dropout): xt time-major (T, B, I) with zero rows at t >= n_in[b],
+        n_in int32 device lengths -> (ceil(T / factor), B, D*H), zero beyond ceil(n / factor).  slu_gemm_f32 (the padded
+        rows' projections are b_ih: never read), slu_gru_seq_fwd_len, slu_seq_pool_len_fwd."""
+        g = self.gru
+        with torch.no_grad():
+            xt = xt.contiguous()
+            T, B, I = xt.shape
+            H, D = g.hidden_size, 2 if g.bidirectional else 1
+            w_ih, b_ih = g._stacked_ih()
+            gx = _ops.gemm(xt.view(T * B, I), w_ih.detach().t(), b_ih.detach())
+            rev = (g.weight_hh_l0_reverse.detach(), g.bias_hh_l0_reverse.detach()) if g.bidirectional else (None, None)
+            out = _ops.gru_seq_fwd_len(gx, g.weight_hh_l0.detach(), rev[0], g.bias_hh_l0.detach(), rev[1], n_in, T, B, H, D)
+            if self.factor > 1:
+                out = _ops.seq_pool_len_fwd(out, n_in, self.method, self.factor)
+            return out
 
 
 def _build_rnn_stack(layers, stages, prefix, in_dim, hidden, bidirectional, drops, ds_types, ds_lens):
@@ -1252,11 +1365,51 @@ class PretrainedModel(torch.nn.Module):
             return out.view(T, B, -1).transpose(0, 1)
         return head(self.phoneme_linear, ph_tm), head(self.word_linear, wd_tm)
 
-    def compute_features(self, x):
-        """(B,T) waveform -> (B,T',C) encoder features (reference models.py:349-361)."""
+    def stage_lengths(self, lengths):
+        """Valid frames after every fused stage (CNN blocks, phoneme layers, word layers) for utterances of `lengths`
+        samples: a list with one list of B ints per stage (one int per stage for a single int).  Host integer arithmetic
+        by the rules of include/slu_hip.h: convolution (n + 2 (k // 2) - k) // stride + 1, max-pool and Downsample
+        ceil(n / width), GRU n."""
+        single = isinstance(lengths, int)
+        out = _stage_lengths(self._stages(), [lengths] if single else _as_int_list(lengths))
+        return [r[0] for r in out] if single else out
+
+    def _features_tm_len(self, x, lengths, more_stages=()):
+        """Length-aware evaluation of the encoder (+ more_stages): -> (time-major features, host lengths, device lengths).
+        Everything that can be refused is refused before the first launch, on the host."""
+        if x.dim() != 2:
+            raise ValueError("lengths: expected a (B, T) waveform batch")
+        if self.training:
+            raise ValueError("lengths: the length-aware path is inference only (dropout is not applied): call eval() first")
+        host = _host_lengths(lengths, x.shape[0], x.shape[1])
+        stages = self._stages() + list(more_stages)
+        _check_len_stages(stages)
+        (x,) = self._to_device(x)
+        self._cnn_stages[-1].time_major = True
+        with torch.no_grad():
+            x = _ops.pcm16_to_f32(x) if x.dtype == torch.int16 else x.float()
+            dev_len = torch.tensor(host, dtype=torch.int32).to(x.device, non_blocking=True)
+            x = _ops.mask_rows_len(x, dev_len)                       # the first stage's input tail
+            return _run_stages_len(stages, x, host)
+
+    def compute_features(self, x, lengths=None):
+        """(B,T) waveform -> (B,T',C) encoder features (reference models.py:349-361).
+        lengths (not in the reference; None: the call above): the utterances' sample counts -> the features of every
+        utterance as if it were run alone, zero at frames at or beyond stage_lengths(lengths)[-1] (eval mode only)."""
+        if lengths is not None:
+            return self._features_tm_len(x, lengths)[0].transpose(0, 1)
         (x,) = self._to_device(x)
         _DropoutState.current = next_rng_step()
         return self._features_tm(x).transpose(0, 1)
+
+
+def _as_int_list(lengths):
+    if torch.is_tensor(lengths):
+        lengths = lengths.detach().cpu().reshape(-1).tolist()
+    vals = [int(v) for v in lengths]
+    if any(v < 1 for v in vals):
+        raise ValueError("lengths: every utterance needs at least one sample")
+    return vals
 
 
 def freeze_layer(layer):
@@ -1447,13 +1600,49 @@ class Model(torch.nn.Module):
         character-set strips, as the reference applies them)."""
         return "".join([S[c] for c in input.max(dim=1)[1]]).lstrip("<sos>").rstrip("<eos>")
 
-    def eval_group(self, xs, ys):
+    def stage_lengths(self, lengths):
+        """PretrainedModel.stage_lengths continued through the intent layers: one entry per fused stage, the last one
+        being the frames the head's max over time ranges over."""
+        single = isinstance(lengths, int)
+        out = _stage_lengths(self.pretrained_model._stages() + list(self._intent_stages),
+                             [lengths] if single else _as_int_list(lengths))
+        return [r[0] for r in out] if single else out
+
+    def _intent_features_tm_len(self, x, lengths):
+        """Length-aware encoder + intent layers -> (h time-major, host lengths, device lengths of h)."""
+        if self.seq2seq:
+            raise ValueError("lengths: seq2seq models are not supported (the decoder's attention would have to mask the "
+                             "encoder frames as well)")
+        return self.pretrained_model._features_tm_len(x, lengths, self._intent_stages)
+
+    def eval_group(self, xs, ys, lengths=None):
         """Evaluation (no dropout, no autograd) of several equally-shaped batches in ONE pass through the
         encoder and the intent GRU (concatenated along the batch axis: 8 x more recurrence workgroups at
         the same latency), then the per-batch loss/accuracy.  Returns [(loss, acc), ...] — the values
-        forward() gives batch by batch."""
+        forward() gives batch by batch.
+        lengths (None: the evaluation above): one sequence of sample counts per batch -> the padding-invariant
+        evaluation: every utterance contributes the loss / correctness of the utterance run alone."""
         assert not self.training
         pm = self.pretrained_model
+        if lengths is not None:
+            if len(lengths) != len(xs):
+                raise ValueError("lengths: %d entries for %d batches" % (len(lengths), len(xs)))
+            B = xs[0].shape[0]
+            host = []
+            for x, l in zip(xs, lengths):
+                host += _host_lengths(l, x.shape[0], x.shape[1])
+            dev = next(self.parameters()).device if next(self.parameters()).is_cuda else None
+            x_cat = torch.cat([x.to(dev, non_blocking=True) if dev is not None else x for x in xs]) if len(xs) > 1 else xs[0]
+            h, _, n_dev = self._intent_features_tm_len(x_cat, host)
+            cls = self.intent_layers[-2]
+            out = []
+            for k, y in enumerate(ys):
+                hk = h[:, k * B:(k + 1) * B].contiguous() if len(xs) > 1 else h.contiguous()
+                la, _, _, _ = _ops.cls_maxpool_len_fwd(hk, cls.weight.detach(), cls.bias.detach(),
+                                                       n_dev[k * B:(k + 1) * B].contiguous(),
+                                                       y.to(h.device).contiguous(), tuple(self.values_per_slot))
+                out.append((la[0], la[1]))
+            return out
         with torch.no_grad():
             dev = next(self.parameters()).device
             B = xs[0].shape[0]
@@ -1470,8 +1659,18 @@ class Model(torch.nn.Module):
                 out.append((la[0], la[1]))
         return out
 
-    def predict_intents(self, x):
-        """-> (intent_logits (B, num_values_total), predicted_intent (B, num_slots)) (models.py:830-846)"""
+    def predict_intents(self, x, lengths=None):
+        """-> (intent_logits (B, num_values_total), predicted_intent (B, num_slots)) (models.py:830-846)
+        lengths (not in the reference; None: the call as it was): the utterances' sample counts, each in [1, T] ->
+        padding-invariant inference: row b's logits are those of x[b:b+1, :lengths[b]] run alone (eval mode, fixed-slot
+        models, GRU hidden sizes 16 / 32 / 64 / 128; exact fp32 kernels whatever SLU_FROZEN_MATH says)."""
+        if lengths is not None:
+            h, _, n_dev = self._intent_features_tm_len(x, lengths)
+            _DropoutState.current = next_rng_step()
+            cls = self.intent_layers[-2]
+            _, logits, pred, _ = _ops.cls_maxpool_len_fwd(h.contiguous(), cls.weight.detach(), cls.bias.detach(), n_dev,
+                                                          None, tuple(self.values_per_slot))
+            return logits, pred
         h = self._intent_features_tm(x).contiguous()
         if self.seq2seq:                                         # beam search, width 4 (models.py:848-851)
             if beam_search_mode() == "host":
@@ -1518,8 +1717,14 @@ class Model(torch.nn.Module):
             res.append(rows)
         return res
 
-    def decode_intents(self, x):
-        """-> list (batch) of lists (slots) of slot-value strings (reference models.py:853-865)."""
+    def decode_intents(self, x, lengths=None):
+        """-> list (batch) of lists (slots) of slot-value strings (reference models.py:853-865).
+        lengths: as predict_intents (fixed-slot models only)."""
+        if lengths is not None:
+            pred = self.predict_intents(x, lengths)[1].cpu()
+            inverse = [{idx: value for value, idx in self.Sy_intent[slot].items()} for slot in self.Sy_intent]
+            return [[inverse[s][int(row[s])] for s in range(len(inverse)) if int(row[s]) in inverse[s]]
+                    for row in pred]
         if self.seq2seq and beam_search_mode() == "device":
             # best hypothesis of every utterance (models.py:866-874) from its labels (batch, U): the string
             # one_hot_to_string builds, without the one-hot beam crossing to the host

@@ -1200,6 +1200,104 @@ def cls_maxpool_ce_fwd(h, weight, bias, y, values_per_slot, want_grad, epoch_sum
     return loss_acc, logits, pred, argmax_t, d_logits
 
 
+# ------------------------------------------------------------------------------------------------
+# per-utterance lengths: padding-invariant inference (include/slu_hip.h; csrc/slu_varlen.hip, slu_gru.hip)
+# ------------------------------------------------------------------------------------------------
+LEN_HIDDEN_SIZES = (16, 32, 64, 128)       # hidden sizes slu_gru_seq_fwd_len takes (the persistent recurrence kernels)
+
+
+def _len_check(lengths, B, *tensors):
+    """The length-aware calls are forward evaluations outside autograd: a tensor that requires a gradient is refused
+    instead of being silently detached.  lengths: int32 CUDA tensor of B entries (values are the caller's to validate —
+    models._host_lengths does, on the host; the kernels clamp)."""
+    for t in tensors:
+        if t is not None and t.requires_grad:
+            raise RuntimeError("the length-aware kernels are inference only (no backward): call them under torch.no_grad() "
+                               "with detached tensors")
+    if not torch.is_tensor(lengths) or lengths.dtype != torch.int32 or not lengths.is_cuda:
+        raise TypeError("lengths must be an int32 CUDA tensor")
+    if lengths.dim() != 1 or lengths.numel() != B or not lengths.is_contiguous():
+        raise ValueError("lengths: expected %d contiguous entries, got shape %s" % (B, tuple(lengths.shape)))
+
+
+def mask_rows_len(x, lengths):
+    """x (B, T) fp32 waveforms -> a copy with x[b, lengths[b]:] = 0."""
+    L = _lib.load()
+    _len_check(lengths, x.shape[0], x)
+    x = _f32c(x, "x")
+    out = torch.empty_like(x)
+    _lib.check(L.slu_mask_rows_len(x.data_ptr(), out.data_ptr(), lengths.data_ptr(), x.shape[0], x.shape[1], _stream()),
+               "slu_mask_rows_len")
+    return out
+
+
+def pool_act_len_fwd(x, lengths, pool, do_abs, slope, time_major):
+    """x channels-last (B, L, C), lengths = valid frames of x -> [abs ->] max-pool(pool, ceil) over the valid frames ->
+    LeakyReLU(slope), zero beyond ceil(n / pool): (B, L_out, C), or time-major (L_out, B, C)."""
+    L = _lib.load()
+    _len_check(lengths, x.shape[0], x)
+    x = _f32c(x, "x")
+    B, Lin, C = x.shape
+    l_out = -(-Lin // pool)
+    if time_major:
+        y = torch.empty(l_out, B, C, dtype=torch.float32, device=x.device)
+        sb, sl = C, B * C
+    else:
+        y = torch.empty(B, l_out, C, dtype=torch.float32, device=x.device)
+        sb, sl = l_out * C, C
+    _lib.check(L.slu_pool_act_len_fwd(x.data_ptr(), y.data_ptr(), lengths.data_ptr(), B, Lin, C, pool, int(do_abs),
+                                      float(slope), sb, sl, _stream()), "slu_pool_act_len_fwd")
+    return y
+
+
+def gru_seq_fwd_len(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lengths, T, B, H, D):
+    """gru_seq_fwd (no reserve) with per-sequence lengths -> out (T, B, D*H), zero at t >= lengths[b]."""
+    L = _lib.load()
+    _len_check(lengths, B, gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r)
+    if H not in LEN_HIDDEN_SIZES:
+        raise ValueError("lengths: hidden size %d has no length-aware recurrence kernel (supported: %s)"
+                         % (H, ", ".join(map(str, LEN_HIDDEN_SIZES))))
+    out = torch.empty(T, B, D * H, dtype=torch.float32, device=gx.device)
+    _lib.check(L.slu_gru_seq_fwd_len(gx.data_ptr(), w_hh_f.data_ptr(), _ptr(w_hh_r), b_hh_f.data_ptr(), _ptr(b_hh_r),
+                                     out.data_ptr(), lengths.data_ptr(), T, B, H, D, _stream()), "slu_gru_seq_fwd_len")
+    return out
+
+
+def seq_pool_len_fwd(x, lengths, method, factor):
+    """Downsample(method, factor) of a time-major (T, B, C) activation with per-sequence lengths."""
+    L = _lib.load()
+    _len_check(lengths, x.shape[1], x)
+    x = _f32c(x, "x")
+    T, B, C = x.shape
+    y = torch.empty(-(-T // factor), B, C, dtype=torch.float32, device=x.device)
+    _lib.check(L.slu_seq_pool_len_fwd(x.data_ptr(), y.data_ptr(), lengths.data_ptr(), METHODS[method], factor, T, B, C,
+                                      _stream()), "slu_seq_pool_len_fwd")
+    return y
+
+
+def cls_maxpool_len_fwd(h, weight, bias, lengths, y, values_per_slot):
+    """-> (loss_acc (2) or None, logits (B, V), pred (B, S), argmax_t (B, V) int32): cls_maxpool_ce_fwd with the max over
+    time taken over t < lengths[b]."""
+    import ctypes
+    L = _lib.load()
+    _len_check(lengths, h.shape[1], h, weight, bias)
+    h, weight, bias = _f32c(h, "h"), _f32c(weight, "weight"), _f32c(bias, "bias")
+    T, B, C = h.shape
+    S = len(values_per_slot)
+    V = int(sum(values_per_slot))
+    dev = h.device
+    logits = torch.empty(B, V, dtype=torch.float32, device=dev)
+    argmax_t = torch.empty(B, V, dtype=torch.int32, device=dev)
+    pred = torch.empty(B, S, dtype=torch.int64, device=dev)
+    row_stats = torch.empty(B, 2, dtype=torch.float32, device=dev) if y is not None else None
+    loss_acc = torch.empty(2, dtype=torch.float32, device=dev) if y is not None else None
+    vps = (ctypes.c_int64 * S)(*[int(v) for v in values_per_slot])
+    _lib.check(L.slu_cls_maxpool_len_fwd(h.data_ptr(), weight.data_ptr(), bias.data_ptr(), lengths.data_ptr(), _ptr(y), vps,
+                                         S, logits.data_ptr(), argmax_t.data_ptr(), pred.data_ptr(), _ptr(row_stats),
+                                         _ptr(loss_acc), T, B, C, _stream()), "slu_cls_maxpool_len_fwd")
+    return loss_acc, logits, pred, argmax_t
+
+
 def head_dropout_fusable(weight, p, mask, method, factor, h=None):
     """The Dropout between the last intent GRU layer and the classifier can be drawn inside the head kernels: Philox
     masks (no injected mask tensor), no Downsample, four-channel alignment OF WHAT THE HEAD READS — the classifier's

@@ -153,6 +153,23 @@ def _same_form(batch, first):
     return tuple(batch[0].shape) == tuple(first[0].shape) and batch[0].dtype == first[0].dtype
 
 
+class _drop_lengths:
+    """SLU batches of the training loops: (x, y) whatever the loader yields.  With SLU_MASK_PADDING=1 the collate function
+    adds the utterances' sample counts as a third element (data.CollateWavsSLU); only evaluation uses them
+    (Model.eval_group(lengths=...)) — training on masked padding is not implemented, its arithmetic stays as it is.
+    Keeps the loader's len() (the look-ahead pipeline sizes its first super-batches by the run's length)."""
+
+    def __init__(self, loader):
+        self.loader = loader
+
+    def __iter__(self):
+        for batch in self.loader:
+            yield tuple(batch[:2]) if len(batch) == 3 else batch
+
+    def __len__(self):
+        return len(self.loader)           # TypeError for a generator, as on the loader itself
+
+
 def _input_version(batch):
     return batch[0]._version if batch[0].is_cuda else None
 
@@ -354,6 +371,10 @@ class Trainer:
             if ptype == 2:
                 loss = phoneme_loss + word_loss
             return [phoneme_loss, word_loss, phoneme_acc, word_acc], loss
+        if len(batch) == 3:                    # (x, y, lengths): evaluation under SLU_MASK_PADDING=1 (_iterate)
+            x, y_intent, lengths = batch
+            (intent_loss, intent_acc), = self.model.eval_group([x], [y_intent], [lengths])
+            return [intent_loss, intent_acc], intent_loss
         x, y_intent = batch
         # through model.__call__ (forward hooks / wrappers keep working); rng_step is a keyword-only extra of this
         # package's Model.forward
@@ -567,7 +588,10 @@ class Trainer:
             outer.wait_stream(main)
 
     def _eval_group(self, group, sums):
-        res = self.model.eval_group([b[0] for b in group], [b[1] for b in group])
+        if len(group[0]) == 3:                 # (x, y, lengths): SLU_MASK_PADDING=1
+            res = self.model.eval_group([b[0] for b in group], [b[1] for b in group], [b[2] for b in group])
+        else:
+            res = self.model.eval_group([b[0] for b in group], [b[1] for b in group])
         out = [([l, a], len(b[0])) for (l, a), b in zip(res, group)]
         if sums is not None:
             for vals, bs in out:
@@ -706,6 +730,8 @@ class Trainer:
         if accumulate:
             sums = self._sums_buffer()
             sums.zero_()
+        if train and not asr:
+            loader = _drop_lengths(loader)
         depth, n_prefix = self.lookahead_depth(train, asr)
         group_eval = (not train and not asr and hasattr(self.model, "eval_group") and not models_masks_injected()
                       and not getattr(self.model, "seq2seq", False)
@@ -768,7 +794,7 @@ class Trainer:
                 if seq2seq and not train and self.epoch > 1:
                     # reference training.py:158-164: from the third epoch on the test accuracy is the fraction of
                     # utterances whose beam-search string equals the label string
-                    x, y = current
+                    x, y = current[:2]
                     guess = self.model.decode_intents(x)
                     truth = [self.model.one_hot_to_string(y[i], self.model.Sy_intent) for i in range(batch_size)]
                     hit = sum(g == t for g, t in zip(guess, truth)) / batch_size
@@ -802,7 +828,7 @@ class Trainer:
 
     def _say_seq2seq_sample(self, batch):
         """Reference training.py:103-112: decode the first utterance of the batch the step just consumed."""
-        x, y = batch
+        x, y = batch[:2]
         import models
         was_training = self.model.training
         step = models._DropoutState.step          # the sample must not shift the training run's dropout streams

@@ -565,6 +565,57 @@ int slu_beam_select_eos(const float* logits, float* scores, const float* state_n
 int slu_beam_backtrack(const int32_t* backptr, const int32_t* labels, int64_t* out, float* one_hot, int64_t W,
                        int64_t batch, int64_t U, int64_t V, void* stream);
 
+/* -------- per-utterance lengths: padding-invariant inference — added under ABI 10 (five new entry points; nothing
+ * existing changed, so the version number stays).  The definition is this library's own: the reference's collate functions
+ * zero-pad a batch to its longest row and pass no lengths (data.py:244), so its convolutions, ceil_mode windows, reverse
+ * GRU directions and FinalPool all see the padding.
+ *   lengths (B) int32: lengths[b] = number of valid frames of row b of the call's INPUT, 1 <= lengths[b] <= frames of the
+ *   buffer; frames at or beyond it are treated as zero, whatever the buffer holds.  The valid length follows every stage
+ *   by the rule the stage applies to an input of that length alone:
+ *     convolution           n_conv = (n + 2 * (k / 2) - k) / stride + 1
+ *     max-pool              ceil(n_conv / pool)
+ *     GRU                   n
+ *     Downsample none/avg/max   ceil(n / factor)
+ *   Every stage's output is exactly 0.0f at frames at or beyond its valid length and, at a valid frame, equals what the
+ *   stage computes on the row truncated to its valid length: a ceil_mode window that straddles the end uses its valid
+ *   frames only (the average divides by their count, as avg_pool1d(ceil_mode=True) does at the end of a tensor); GRU
+ *   direction 0 runs t = 0 .. n - 1, direction 1 starts at t = n - 1 from h = 0; the head's max over time and its
+ *   argmax_t range over t < n only.  So an utterance's logits in a padded batch are its logits when it is run alone.
+ * Forward / inference only: no route, no reserve, no dropout.  NULL lengths: SLU_ERR_INVALID_ARG.  A length outside
+ * [1, frames] is the HOST's to reject (slu_hip/ops.py raises ValueError before any launch); the kernels clamp it into
+ * that range, so a bad value cannot index out of bounds.  The convolution and the GRU input projection need no entry
+ * point of their own: on an input with a zero tail slu_wconv_fwd (pool = 1, slope = 1.0, do_abs = 0: convolution +
+ * bias) and slu_gemm_f32 give, at a valid frame, the truncated row's value; the calls below restore the zero tail.
+ *   slu_mask_rows_len        out[b][t] = t < lengths[b] ? in[b][t] : 0 for a (B, T) waveform batch (out may alias in): the
+ *                            first stage's input tail.
+ *   slu_pool_act_len_fwd     slu_pool_act_fwd over the valid frames: x channels-last (B, L, C) with lengths = valid frames
+ *                            of x (n_conv), [abs ->] max over the window clipped to the valid range -> LeakyReLU(slope),
+ *                            0 for lo >= ceil(n / pool); y[b, lo, c] at b * out_sb + lo * out_sl + c (channels-last or
+ *                            time-major); any pool in [1, 127] (pool = 1: activation + zero tail).
+ *   slu_gru_seq_fwd_len      slu_gru_seq_fwd with reserve = NULL and per-sequence lengths: out[t, b] = 0 for
+ *                            t >= lengths[b]; no gx value at t >= lengths[b] reaches any result (NaN there is harmless).
+ *                            Persistent hidden sizes H = 16 / 32 / 64 / 128 only, both workgroup geometries, D = 1 / 2;
+ *                            any other H (the step-wise path of slu_gru_seq_fwd): SLU_ERR_UNSUPPORTED — the host mirror
+ *                            raises ValueError("lengths: hidden size ...") before it gets here.
+ *   slu_seq_pool_len_fwd     Downsample on time-major x (T, B, C) -> y (ceil(T / factor), B, C): method 0 / 1 / 2 as
+ *                            slu_dropout_pool_fwd, windows clipped to t < lengths[b], 0 for to >= ceil(n / factor).
+ *   slu_cls_maxpool_len_fwd  slu_cls_maxpool_ce_fwd's logits (B, V) = max over t < lengths[b] of h_t W^T + b, argmax_t,
+ *                            pred (B, S); y (NULL, or (B, S) labels): loss_acc (2) by slu_cls_maxpool_ce_fwd's
+ *                            definitions (row_stats (B, 2) scratch and loss_acc then required).  No gradient, no dropout.
+ *                            values_per_slot is a HOST array, as there.                                              */
+int slu_mask_rows_len(const float* in, float* out, const int32_t* lengths, int64_t B, int64_t T, void* stream);
+int slu_pool_act_len_fwd(const float* x, float* y, const int32_t* lengths, int64_t B, int64_t L, int64_t C, int64_t pool,
+                         int do_abs, float slope, int64_t out_sb, int64_t out_sl, void* stream);
+int slu_gru_seq_fwd_len(const float* gx, const float* w_hh_fwd, const float* w_hh_rev, const float* b_hh_fwd,
+                        const float* b_hh_rev, float* out, const int32_t* lengths, int64_t T, int64_t B, int64_t H,
+                        int64_t D, void* stream);
+int slu_seq_pool_len_fwd(const float* x, float* y, const int32_t* lengths, int method, int64_t factor, int64_t T,
+                         int64_t B, int64_t C, void* stream);
+int slu_cls_maxpool_len_fwd(const float* h, const float* weight, const float* bias, const int32_t* lengths,
+                            const int64_t* y, const int64_t* values_per_slot, int64_t num_slots, float* logits,
+                            int32_t* argmax_t, int64_t* pred, float* row_stats, float* loss_acc, int64_t T, int64_t B,
+                            int64_t C, void* stream);
+
 /* -------- Adam: torch.optim.Adam(model.parameters(), lr) (training.py:19, default betas / eps) ------
  * One launch updates up to slu_adam_max_tensors() tensors of one dtype (elem_bytes 4 / 8); the pointer
  * arrays are HOST arrays of device pointers (they travel in the kernel arguments: hipGraph-safe).

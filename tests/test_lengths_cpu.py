@@ -1,0 +1,225 @@
+"""CPU: the host side of padding-invariant inference (per-utterance lengths; DESIGN.md section 7 "Lengths").
+
+  * models.*.stage_lengths against the frame counts the CPU oracle produces on a (1, n) waveform;
+  * data.CollateWavsSLU under SLU_MASK_PADDING;
+  * the new entry points of the built library;
+  * everything the host refuses before a launch (no GPU needed): bad lengths, seq2seq models, hidden sizes without a
+    length-aware recurrence kernel, and the Trainer's handling of 2- and 3-tuples.
+"""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import slu_oracle as O
+
+import data
+import models
+import training
+from slu_hip import lib
+
+
+def _sy(vps):
+    names = ["action", "object", "location"]
+    return {names[s]: {"%s%d" % (names[s][0], v): v for v in range(n)} for s, n in enumerate(vps)}
+
+
+def tiny_cfg(folder, **kw):
+    """The architecture of fixture g5 (tests/test_hip_model.py)."""
+    c = O.OracleConfig(cnn_N_filt=[8, 6, 6], cnn_len_filt=[41, 5, 3], cnn_stride=[10, 1, 1],
+                       phone_rnn_num_hidden=[16, 16], word_rnn_num_hidden=[16, 16],
+                       intent_rnn_num_hidden=[16], vocabulary_size=50, num_phonemes=11,
+                       values_per_slot=[3, 4, 2], pretraining_type=0)
+    c.folder = str(folder)
+    c.starting_unfreezing_index = 1
+    for k, v in kw.items():
+        setattr(c, k, v)
+    c.Sy_intent = _sy(c.values_per_slot)
+    return c
+
+
+def synthetic_cfg(folder, monkeypatch):
+    """experiments/no_unfreezing_synthetic.cfg's architecture, without its pre-trained checkpoint."""
+    # read_config creates the experiment's folders next to the cfg: read a copy under tmp_path
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "end-to-end-slu_amd", "experiments",
+                       "no_unfreezing_synthetic.cfg")
+    os.makedirs(os.path.join(str(folder), "experiments"), exist_ok=True)
+    with open(os.path.join(str(folder), "experiments", "no_unfreezing_synthetic.cfg"), "w") as f:
+        f.write(open(src).read())
+    monkeypatch.chdir(str(folder))
+    c = data.read_config("experiments/no_unfreezing_synthetic.cfg")
+    c.folder = str(folder)
+    c.pretraining_type = 0
+    c.num_phonemes, c.vocabulary_size = 42, 100        # set by the datasets in a real run; no stage length depends on them
+    c.values_per_slot = [6, 14, 4]
+    c.Sy_intent = _sy(c.values_per_slot)
+    c.seq2seq = False
+    return c
+
+
+def _oracle_frames(cfg, sd, n):
+    """Frame count behind every fused stage of the encoder, from the oracle's own tensors on a (1, n) waveform."""
+    st = O.encoder_stages(sd, torch.zeros(1, n), cfg, explicit_gru=False)
+    out = [st["cnn%d" % c].shape[2] for c in range(len(cfg.cnn_N_filt))]
+    out += [st["phone_down%d" % r].shape[1] for r in range(len(cfg.phone_rnn_num_hidden))]
+    out += [st["word_down%d" % r].shape[1] for r in range(len(cfg.word_rnn_num_hidden))]
+    return out
+
+
+# tiny: conv stride 10 and pool 2, then four Downsample(2): n = 1 (one frame everywhere); 10 / 11 give an even / odd n_conv
+# (2 / 2 -> the conv formula's floor) — 30, 50 give n_conv = 3, 5 (odd: a partial pooling window); 61, 101, 141, 301 make the
+# input of the first, second, third, fourth Downsample odd; 3000 is a workload-like length.
+TINY_N = [1, 10, 11, 30, 50, 61, 101, 141, 301, 1810, 2999, 3000]
+# full: conv stride 80 and pool 2: 81 -> n_conv 2, 161 -> 3 (odd), 321 -> phone input 3 (odd), 641, 1281, 2561 the deeper ones
+FULL_N = [1, 80, 81, 161, 321, 641, 1281, 2561, 8000, 16000]
+
+
+@pytest.mark.parametrize("arch", ["tiny", "synthetic"])
+def test_stage_lengths_match_the_oracles_frame_counts(arch, tmp_path, monkeypatch):
+    cfg = tiny_cfg(tmp_path) if arch == "tiny" else synthetic_cfg(tmp_path, monkeypatch)
+    torch.manual_seed(0)
+    model = models.Model(cfg).cpu()
+    sd = {"phoneme_layers." + k.split("phoneme_layers.")[1] if "phoneme_layers." in k else
+          "word_layers." + k.split("word_layers.")[1]: v.detach()
+          for k, v in model.pretrained_model.state_dict().items() if "phoneme_layers." in k or "word_layers." in k}
+    n_enc = len(model.pretrained_model._stages())
+    odd_conv = even_conv = False
+    for n in (TINY_N if arch == "tiny" else FULL_N):
+        want = _oracle_frames(cfg, sd, n)
+        got = model.pretrained_model.stage_lengths(n)
+        assert got == want, (arch, n, got, want)
+        full = model.stage_lengths(n)
+        assert full[:n_enc] == want
+        # the intent layers: the oracle's Downsample on a tensor of that many frames
+        frames = want[-1]
+        for r, (kind, width) in enumerate(zip(cfg.intent_downsample_type, cfg.intent_downsample_len)):
+            frames = O.downsample(torch.zeros(1, frames, 2), kind, width).shape[1]
+            assert full[n_enc + r] == frames
+        n_conv = model.pretrained_model._cnn_stages[0].conv_len(n)
+        odd_conv, even_conv = odd_conv or n_conv % 2 == 1, even_conv or n_conv % 2 == 0
+    assert odd_conv and even_conv
+    # a batch of lengths: one list per stage
+    both = model.stage_lengths([1, 3000])
+    assert [r[0] for r in both] == model.stage_lengths(1) and [r[1] for r in both] == model.stage_lengths(3000)
+
+
+def _batch(rs, lens):
+    return [(rs.randn(n).astype(np.float32), [int(rs.randint(3)), int(rs.randint(4)), int(rs.randint(2))]) for n in lens]
+
+
+def test_collate_returns_the_unrounded_lengths_only_when_asked(monkeypatch):
+    rs = np.random.RandomState(0)
+    lens = [900, 2399, 1, 1600]
+    batch = _batch(rs, lens)
+    monkeypatch.delenv("SLU_MASK_PADDING", raising=False)
+    monkeypatch.delenv("SLU_PAD_TO_MULTIPLE", raising=False)
+    plain = data.CollateWavsSLU(_sy([3, 4, 2]), False)(batch)
+    assert isinstance(plain, tuple) and len(plain) == 2 and tuple(plain[0].shape) == (4, 2399)
+    monkeypatch.setenv("SLU_MASK_PADDING", "1")
+    x, y, n = data.CollateWavsSLU(_sy([3, 4, 2]), False)(batch)
+    assert torch.equal(x, plain[0]) and torch.equal(y, plain[1])
+    assert n.dtype == torch.int32 and n.tolist() == lens
+    monkeypatch.setenv("SLU_PAD_TO_MULTIPLE", "1000")
+    x, y, n = data.CollateWavsSLU(_sy([3, 4, 2]), False)(batch)
+    assert tuple(x.shape) == (4, 3000) and n.tolist() == lens            # the lengths are not rounded
+    assert float(x[:, 2399:].abs().sum()) == 0.0
+    monkeypatch.setenv("SLU_MASK_PADDING", "0")
+    assert len(data.CollateWavsSLU(_sy([3, 4, 2]), False)(batch)) == 2
+    monkeypatch.setenv("SLU_MASK_PADDING", "yes")
+    with pytest.raises(ValueError):
+        data.CollateWavsSLU(_sy([3, 4, 2]), False)
+
+
+def test_library_has_the_length_entry_points():
+    L = lib.load()
+    assert L.slu_version() == 10 == lib.ABI_VERSION
+    raw = ctypes.CDLL(lib.LIB_PATH)
+    want = {"slu_mask_rows_len": 6, "slu_pool_act_len_fwd": 12, "slu_gru_seq_fwd_len": 12, "slu_seq_pool_len_fwd": 9,
+            "slu_cls_maxpool_len_fwd": 16}
+    for name, nargs in want.items():
+        assert hasattr(raw, name), name
+        assert len(lib.SIGNATURES[name][1]) == nargs, name
+    # argument checks that need no device: NULL lengths / NULL pointers are refused before any launch
+    assert L.slu_gru_seq_fwd_len(1, 1, 1, 1, 1, 1, None, 4, 2, 16, 2, None) == -1
+    assert b"lengths" in L.slu_last_error()
+    assert L.slu_pool_act_len_fwd(1, 1, None, 2, 4, 3, 2, 0, 0.2, 6, 3, None) == -1
+    assert L.slu_seq_pool_len_fwd(1, 1, None, 1, 2, 4, 2, 3, None) == -1
+    assert L.slu_mask_rows_len(1, 1, None, 2, 4, None) == -1
+    vps = (ctypes.c_int64 * 1)(3)
+    assert L.slu_cls_maxpool_len_fwd(1, 1, 1, None, None, vps, 1, 1, 1, 1, None, None, 4, 2, 8, None) == -1
+    # hidden sizes of the step-wise path: unsupported (-2)
+    one = ctypes.c_int32(1)
+    assert L.slu_gru_seq_fwd_len(1, 1, 1, 1, 1, 1, ctypes.addressof(one), 4, 1, 48, 2, None) == -2
+    assert b"hidden size 48" in L.slu_last_error()
+
+
+def test_bad_lengths_are_refused_on_the_host(tmp_path):
+    model = models.Model(tiny_cfg(tmp_path)).cpu().eval()
+    x = torch.zeros(3, 500)
+    for bad in ([0, 5, 5], [5, 501, 5], [5, 5], [5, 5, 5, 5], torch.tensor([5.0, 5.0, 5.0]), [5, 2.5, 5], 7,
+                torch.tensor([[5, 5, 5]]).t().repeat(1, 2)):
+        for call in (model.predict_intents, model.decode_intents, model.pretrained_model.compute_features):
+            with pytest.raises(ValueError, match="lengths"):
+                call(x, bad)
+    y = torch.zeros(3, 3, dtype=torch.int64)
+    with pytest.raises(ValueError, match="lengths"):
+        model.eval_group([x], [y], [[5, 5, 0]])
+    with pytest.raises(ValueError, match="lengths"):
+        model.eval_group([x, x], [y, y], [[5, 5, 5]])
+    model.train()
+    with pytest.raises(ValueError, match="inference only"):
+        model.predict_intents(x, [5, 5, 5])
+
+
+def test_seq2seq_models_and_stepwise_hidden_sizes_refuse_lengths(tmp_path):
+    labels = ["<sos>", "a", "b", "c", "<eos>"]
+    cfg = tiny_cfg(tmp_path, seq2seq=True, intent_encoder_dim=12, num_intent_encoder_layers=1, intent_decoder_dim=20,
+                   num_intent_decoder_layers=2, intent_decoder_key_dim=10, intent_decoder_value_dim=14)
+    cfg.Sy_intent = labels
+    s2s = models.Model(cfg).cpu().eval()
+    x = torch.zeros(2, 500)
+    for call in (s2s.predict_intents, s2s.decode_intents):
+        with pytest.raises(ValueError, match="seq2seq"):
+            call(x, [500, 100])
+    # a GRU layer on the step-wise recurrence path (hidden size 48): no length-aware kernel
+    wide = models.Model(tiny_cfg(tmp_path, word_rnn_num_hidden=[16, 48])).cpu().eval()
+    with pytest.raises(ValueError, match="lengths: hidden size 48"):
+        wide.predict_intents(x, [500, 100])
+    with pytest.raises(ValueError, match="lengths: hidden size 48"):
+        wide.pretrained_model.compute_features(x, [500, 100])
+    assert wide.stage_lengths(500)[-1] >= 1               # the host arithmetic does not depend on the kernels
+
+
+class _Recorder:
+    """Stands in for a Model: records what the Trainer hands to eval_group."""
+    training = False
+
+    def __init__(self):
+        self.calls = []
+
+    def eval_group(self, xs, ys, lengths=None):
+        self.calls.append((len(xs), None if lengths is None else [l.tolist() for l in lengths]))
+        return [(torch.tensor(1.0), torch.tensor(0.5)) for _ in xs]
+
+
+def test_trainer_tuple_arities():
+    x, y, n = torch.zeros(2, 8), torch.zeros(2, 3, dtype=torch.int64), torch.tensor([8, 3], dtype=torch.int32)
+    # training loops: the lengths are dropped, 2-tuples pass through untouched
+    assert [len(b) for b in training._drop_lengths([(x, y, n), (x, y)])] == [2, 2]
+    first = next(iter(training._drop_lengths([(x, y, n)])))
+    assert first[0] is x and first[1] is y
+    assert len(training._drop_lengths([(x, y)] * 7)) == 7              # the look-ahead pipeline asks for the run's length
+    with pytest.raises(TypeError):
+        len(training._drop_lengths(b for b in [(x, y)]))
+    # evaluation groups: a 3-tuple's lengths reach eval_group, a 2-tuple's call is today's
+    tr = training.Trainer.__new__(training.Trainer)
+    tr.model = _Recorder()
+    out = tr._eval_group([(x, y, n), (x, y, n)], None)
+    assert tr.model.calls == [(2, [[8, 3], [8, 3]])] and [bs for _, bs in out] == [2, 2]
+    tr._eval_group([(x, y)], None)
+    assert tr.model.calls[-1] == (1, None)
+    # the eager evaluation loop (SLU_LOOKAHEAD=0 / 1) takes the same route for a 3-tuple
+    vals, loss = tr._forward_losses((x, y, n), False)
+    assert tr.model.calls[-1] == (1, [[8, 3]]) and float(vals[0]) == 1.0 and float(vals[1]) == 0.5

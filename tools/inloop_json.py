@@ -24,7 +24,7 @@ def pick(prefix, n_shapes):
 
 
 spec = {  # bench.py table name -> (name prefix in the trace, launch shapes per look-ahead cycle)
-    "gru_seq_fwd4_kernel<128>": ("void slu::gru_seq_fwd4_kernel<128>", 1),
+    "gru_seq_fwd4_kernel<128>": ("void slu::gru_seq_fwd4_kernel<128, false>", 1),
     "gemm_f32_kernel<true,true,2>": ("void slu::gemm_f32_kernel<true, true, 2>", 1),
 }
 for ns in (2, 3):           # the split scheme of the frozen stages: f16x2 (default) / bf16x3
