@@ -336,9 +336,17 @@ struct GruBwdParams {
   float* d_gh;            // (T, B, D*3H)  gradient w.r.t. h_{t-1} W_hh^T + b_hh   = [dr_pre, dz_pre, dq]
   float* d_bias_part;     // [NBT][D][6H] or null: sums over t and the tile's sequences of d_gx | d_gh
   int T, B, D;
+  const int* lengths;     // (B) valid steps per sequence: read by the LEN instantiations only
 };
 
-template <int H>
+// LEN (slu_gru_seq_bwd_len): the BPTT of the LEN forward kernels.  A step with t >= n_b is no step of sequence b: its
+// dr_pre, dz_pre, dn_pre, dq and the dh it hands on are 0 — SELECTED, never multiplied (the reserve and d_out at such a step
+// may hold NaN) — so d_gx / d_gh rows are stored as 0 there, the bias sums see valid steps only and the row of gbuf that
+// feeds the MFMA is zero.  Rows of the MFMA A operand are sequences and do not mix: a zero row gives that sequence a zero
+// carry and touches no other.  Direction 0's backward walk meets the padding first (the carry stays 0 until t = n_b - 1,
+// where dh = d_out), direction 1's meets it last (the forward kernel saved h_{t-1} = 0 at t = n_b - 1).  LEN = false is
+// the kernel as it was.
+template <int H, bool LEN = false>
 __global__ void __launch_bounds__(H * 4)
 gru_seq_bwd_kernel(const GruBwdParams p) {
   constexpr int NW = H / 16;
@@ -372,6 +380,11 @@ gru_seq_bwd_kernel(const GruBwdParams p) {
     const int b = b0 + 4 * kg + r;
     rowok[r] = b < B;
     grow[r] = (size_t)(rowok[r] ? b : 0);
+  }
+  int nlen[4] = {0, 0, 0, 0};   // LEN: valid steps of the lane's four sequences (0 for rows past B)
+  if constexpr (LEN) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) nlen[r] = rowok[r] ? min(max(p.lengths[grow[r]], 1), T) : 0;
   }
   const size_t out_ts = (size_t)B * D * H;
   const size_t gx_ts = (size_t)B * D * 3 * H;
@@ -434,11 +447,17 @@ gru_seq_bwd_kernel(const GruBwdParams p) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const float dh = dcarry[r] + c_do[r];
-      const float dn_pre = dh * cN[r];
-      const float dz_pre = dh * cZ[r];
-      const float dq = dn_pre * cr[r];
-      const float dr_pre = dn_pre * cR[r];
+      float dn_pre = dh * cN[r];
+      float dz_pre = dh * cZ[r];
+      float dq = dn_pre * cr[r];
+      float dr_pre = dn_pre * cR[r];
       ddirect[r] = dh * cz[r];
+      if constexpr (LEN) {
+        const bool live = t < nlen[r];
+        dn_pre = live ? dn_pre : 0.0f; dz_pre = live ? dz_pre : 0.0f;
+        dq = live ? dq : 0.0f; dr_pre = live ? dr_pre : 0.0f;
+        ddirect[r] = live ? ddirect[r] : 0.0f;
+      }
       const int brow = 4 * kg + r;
       gcur[brow * LDB + 0 * H + j] = dr_pre;
       gcur[brow * LDB + 1 * H + j] = dz_pre;
@@ -515,7 +534,7 @@ gru_seq_bwd_kernel(const GruBwdParams p) {
 // accumulator chains (one per gate block) summed at the end.  Element ownership after the fold is the
 // forward kernel's: lane (half, u) handles sequences 2*half + {0, 1} of unit 32w+u.
 // d_bias_part rows are per 4-sequence tile here: [cdiv(B,4)][D][6H] (slu_gru_bias_tiles).
-template <int H>
+template <int H, bool LEN = false>
 __global__ void __launch_bounds__(H * 2)
 gru_seq_bwd4_kernel(const GruBwdParams p, const int NBT16) {
   constexpr int NW16 = H / 16;
@@ -549,6 +568,11 @@ gru_seq_bwd4_kernel(const GruBwdParams p, const int NBT16) {
     const int b = b0 + 2 * half + e;
     rowok[e] = b < B;
     grow[e] = (size_t)(rowok[e] ? b : 0);
+  }
+  int nlen[2] = {0, 0};         // LEN: as in gru_seq_bwd_kernel
+  if constexpr (LEN) {
+#pragma unroll
+    for (int e = 0; e < 2; ++e) nlen[e] = rowok[e] ? min(max(p.lengths[grow[e]], 1), T) : 0;
   }
   const size_t out_ts = (size_t)B * D * H;
   const size_t gx_ts = (size_t)B * D * 3 * H;
@@ -608,11 +632,17 @@ gru_seq_bwd4_kernel(const GruBwdParams p, const int NBT16) {
     for (int e = 0; e < 2; ++e) {
       const float dh = dcarry[e] + c_do[e];
       const float omz = 1.0f - zz[e];
-      const float dn_pre = dh * (omz * (1.0f - nn[e] * nn[e]));
-      const float dz_pre = dh * ((hp[e] - nn[e]) * (zz[e] * omz));
-      const float dq = dn_pre * rr[e];
-      const float dr_pre = dn_pre * (qq[e] * (rr[e] * (1.0f - rr[e])));
+      float dn_pre = dh * (omz * (1.0f - nn[e] * nn[e]));
+      float dz_pre = dh * ((hp[e] - nn[e]) * (zz[e] * omz));
+      float dq = dn_pre * rr[e];
+      float dr_pre = dn_pre * (qq[e] * (rr[e] * (1.0f - rr[e])));
       ddirect[e] = dh * zz[e];
+      if constexpr (LEN) {
+        const bool live = t < nlen[e];
+        dn_pre = live ? dn_pre : 0.0f; dz_pre = live ? dz_pre : 0.0f;
+        dq = live ? dq : 0.0f; dr_pre = live ? dr_pre : 0.0f;
+        ddirect[e] = live ? ddirect[e] : 0.0f;
+      }
       const int row = 2 * half + e;
       gcur[row * LDB + 0 * H + j] = dr_pre;
       gcur[row * LDB + 1 * H + j] = dz_pre;
@@ -753,21 +783,22 @@ extern "C" int slu_gru_seq_fwd(const float* gx, const float* w_hh_fwd, const flo
   return SLU_OK;
 }
 
-extern "C" int slu_gru_seq_fwd_len(const float* gx, const float* w_hh_fwd, const float* w_hh_rev,
-                                   const float* b_hh_fwd, const float* b_hh_rev, float* out,
-                                   const int32_t* lengths, int64_t T, int64_t B, int64_t H, int64_t D,
-                                   void* stream) {
-  SLU_REQUIRE(gx && w_hh_fwd && b_hh_fwd && out, "slu_gru_seq_fwd_len: null pointer");
-  SLU_REQUIRE(lengths, "slu_gru_seq_fwd_len: null lengths");
-  SLU_REQUIRE(D == 1 || (w_hh_rev && b_hh_rev), "slu_gru_seq_fwd_len: reverse weights missing");
-  int rc = gru_check("slu_gru_seq_fwd_len", T, B, H, D);
+// slu_gru_seq_fwd_len (reserve = null) and slu_gru_seq_fwd_len_rsv: the LEN instantiations write the reserve like the
+// plain ones — the gates a step computed and the h_{t-1} it blended with, which is the masked h of the step before: 0
+// for direction 1 at t = n_b - 1.  Reserve contents at t >= n_b are unspecified (NaN where gx is).
+static int gru_fwd_len_launch(const char* who, const float* gx, const float* w_hh_fwd, const float* w_hh_rev,
+                              const float* b_hh_fwd, const float* b_hh_rev, float* out, float* reserve,
+                              const int32_t* lengths, int64_t T, int64_t B, int64_t H, int64_t D, void* stream) {
+  SLU_REQUIRE(gx && w_hh_fwd && b_hh_fwd && out, "%s: null pointer", who);
+  SLU_REQUIRE(lengths, "%s: null lengths", who);
+  SLU_REQUIRE(D == 1 || (w_hh_rev && b_hh_rev), "%s: reverse weights missing", who);
+  int rc = gru_check(who, T, B, H, D);
   if (rc) return rc;
   if (!gru_persistent(H))
-    SLU_FAIL(SLU_ERR_UNSUPPORTED, "slu_gru_seq_fwd_len: hidden size %lld has no length-aware kernel (16, 32, 64 or 128)",
-             (long long)H);
+    SLU_FAIL(SLU_ERR_UNSUPPORTED, "%s: hidden size %lld has no length-aware kernel (16, 32, 64 or 128)", who, (long long)H);
   GruFwdParams p;
   p.gx = gx; p.w_hh[0] = w_hh_fwd; p.w_hh[1] = w_hh_rev; p.b_hh[0] = b_hh_fwd; p.b_hh[1] = b_hh_rev;
-  p.out = out; p.reserve = nullptr; p.T = (int)T; p.B = (int)B; p.D = (int)D; p.lengths = (const int*)lengths;
+  p.out = out; p.reserve = reserve; p.T = (int)T; p.B = (int)B; p.D = (int)D; p.lengths = (const int*)lengths;
   hipStream_t st = (hipStream_t)stream;
   if (gru_use_seq4(B, H, D)) {
     dim3 grid4((unsigned)cdiv(B, 4), (unsigned)D);
@@ -788,6 +819,22 @@ extern "C" int slu_gru_seq_fwd_len(const float* gx, const float* w_hh_fwd, const
   return SLU_OK;
 }
 
+extern "C" int slu_gru_seq_fwd_len(const float* gx, const float* w_hh_fwd, const float* w_hh_rev,
+                                   const float* b_hh_fwd, const float* b_hh_rev, float* out,
+                                   const int32_t* lengths, int64_t T, int64_t B, int64_t H, int64_t D,
+                                   void* stream) {
+  return gru_fwd_len_launch("slu_gru_seq_fwd_len", gx, w_hh_fwd, w_hh_rev, b_hh_fwd, b_hh_rev, out, nullptr, lengths, T, B, H,
+                            D, stream);
+}
+
+extern "C" int slu_gru_seq_fwd_len_rsv(const float* gx, const float* w_hh_fwd, const float* w_hh_rev,
+                                       const float* b_hh_fwd, const float* b_hh_rev, float* out, float* reserve,
+                                       const int32_t* lengths, int64_t T, int64_t B, int64_t H, int64_t D,
+                                       void* stream) {
+  return gru_fwd_len_launch("slu_gru_seq_fwd_len_rsv", gx, w_hh_fwd, w_hh_rev, b_hh_fwd, b_hh_rev, out, reserve, lengths, T,
+                            B, H, D, stream);
+}
+
 extern "C" int slu_gru_seq_bwd(const float* d_out, const float* reserve, const float* w_hh_fwd,
                                const float* w_hh_rev, float* d_gx, float* d_gh, float* d_bias_part,
                                int64_t T, int64_t B, int64_t H, int64_t D, void* stream) {
@@ -798,6 +845,7 @@ extern "C" int slu_gru_seq_bwd(const float* d_out, const float* reserve, const f
   GruBwdParams p;
   p.d_out = d_out; p.reserve = reserve; p.w_hh[0] = w_hh_fwd; p.w_hh[1] = w_hh_rev;
   p.d_gx = d_gx; p.d_gh = d_gh; p.d_bias_part = d_bias_part; p.T = (int)T; p.B = (int)B; p.D = (int)D;
+  p.lengths = nullptr;
   hipStream_t st = (hipStream_t)stream;
   if (!gru_persistent(H)) return gru_step_bwd(d_out, reserve, p.w_hh, d_gx, d_gh, d_bias_part, T, B, H, D, st);
   if (gru_use_seq4(B, H, D)) {
@@ -816,5 +864,40 @@ extern "C" int slu_gru_seq_bwd(const float* d_out, const float* reserve, const f
     default: hipLaunchKernelGGL(gru_seq_bwd_kernel<128>, grid, dim3(512), 0, st, p); break;
   }
   SLU_CHECK_LAUNCH("gru_seq_bwd_kernel");
+  return SLU_OK;
+}
+
+extern "C" int slu_gru_seq_bwd_len(const float* d_out, const float* reserve, const float* w_hh_fwd,
+                                   const float* w_hh_rev, float* d_gx, float* d_gh, float* d_bias_part,
+                                   const int32_t* lengths, int64_t T, int64_t B, int64_t H, int64_t D, void* stream) {
+  SLU_REQUIRE(d_out && reserve && w_hh_fwd && d_gx && d_gh, "slu_gru_seq_bwd_len: null pointer");
+  SLU_REQUIRE(lengths, "slu_gru_seq_bwd_len: null lengths");
+  SLU_REQUIRE(D == 1 || w_hh_rev, "slu_gru_seq_bwd_len: reverse weights missing");
+  int rc = gru_check("slu_gru_seq_bwd_len", T, B, H, D);
+  if (rc) return rc;
+  if (!gru_persistent(H))
+    SLU_FAIL(SLU_ERR_UNSUPPORTED, "slu_gru_seq_bwd_len: hidden size %lld has no length-aware kernel (16, 32, 64 or 128)",
+             (long long)H);
+  GruBwdParams p;
+  p.d_out = d_out; p.reserve = reserve; p.w_hh[0] = w_hh_fwd; p.w_hh[1] = w_hh_rev;
+  p.d_gx = d_gx; p.d_gh = d_gh; p.d_bias_part = d_bias_part; p.T = (int)T; p.B = (int)B; p.D = (int)D;
+  p.lengths = (const int*)lengths;
+  hipStream_t st = (hipStream_t)stream;
+  if (gru_use_seq4(B, H, D)) {
+    dim3 grid4((unsigned)cdiv(B, 4), (unsigned)D);
+    const int nbt16 = (int)cdiv(B, 16);
+    if (H == 64) hipLaunchKernelGGL((gru_seq_bwd4_kernel<64, true>), grid4, dim3(128), 0, st, p, nbt16);
+    else hipLaunchKernelGGL((gru_seq_bwd4_kernel<128, true>), grid4, dim3(256), 0, st, p, nbt16);
+    SLU_CHECK_LAUNCH("gru_seq_bwd4_kernel<LEN>");
+    return SLU_OK;
+  }
+  dim3 grid((unsigned)cdiv(B, 16), (unsigned)D);
+  switch (H) {
+    case 16: hipLaunchKernelGGL((gru_seq_bwd_kernel<16, true>), grid, dim3(64), 0, st, p); break;
+    case 32: hipLaunchKernelGGL((gru_seq_bwd_kernel<32, true>), grid, dim3(128), 0, st, p); break;
+    case 64: hipLaunchKernelGGL((gru_seq_bwd_kernel<64, true>), grid, dim3(256), 0, st, p); break;
+    default: hipLaunchKernelGGL((gru_seq_bwd_kernel<128, true>), grid, dim3(512), 0, st, p); break;
+  }
+  SLU_CHECK_LAUNCH("gru_seq_bwd_kernel<LEN>");
   return SLU_OK;
 }

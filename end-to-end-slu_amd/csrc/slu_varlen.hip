@@ -1,9 +1,12 @@
-// Length-aware inference stages (include/slu_hip.h, "per-utterance lengths"): every row b of a padded batch carries its
+// Length-aware stages (include/slu_hip.h, "per-utterance lengths"): every row b of a padded batch carries its
 // own number of valid frames n_b, a stage's output is exactly 0 at frames at or beyond its valid length, and a valid
 // frame equals what the stage computes on the row truncated to n_b — so an utterance's result does not depend on what
 // it was batched with.  The reference has no counterpart (its collate functions pad and pass no lengths, data.py:244).
 //
-// Forward / inference only: no route bytes, no reserve, no dropout.  The convolution itself and the GRU input projection
+// The first group is forward / inference only: no route bytes, no reserve, no dropout.  The second group (masked
+// training) adds Dropout + Downsample with windows clipped to the lengths, forward and backward, and the head's
+// cross-entropy gradient; the reserve and the BPTT are flags of the persistent kernels (slu_gru_seq_fwd_len_rsv,
+// slu_gru_seq_bwd_len).  The convolution itself and the GRU input projection
 // need no new kernel: on a zero tail the existing slu_wconv_fwd (pool 1, slope 1, no abs) and slu_gemm_f32 compute, at a
 // valid frame, what they compute on the truncated row; the kernels here put the zero tail back behind them.  The
 // length-aware recurrence is a flag of the persistent kernels in slu_gru.hip (slu_gru_seq_fwd_len).
@@ -11,6 +14,7 @@
 // All kernels clamp n_b to [1, frames of the buffer]: a bad length cannot index out of bounds (the host rejects it).
 // These are memory-bound passes over activations that are small next to the waveform: one thread per output element.
 #include "slu_common.h"
+#include "slu_philox.h"
 
 namespace slu {
 
@@ -104,6 +108,7 @@ struct HeadLenParams {
   int* argmax_t;           // (B, V)
   long long* pred;         // (B, S)
   float* row_stats;        // (B, 2) or null
+  float* d_logits;         // (B, V) or null: d loss / d logits (slu_cls_maxpool_len_ce_fwd; needs y)
   int T, B, C, V, S, VP;
   int slot_begin[HEADL_MAX_SLOTS + 1];
 };
@@ -164,6 +169,16 @@ head_len_fwd_kernel(const HeadLenParams p) {
       s_part[tid] = logf(den) - (sm[v0 + yv] - mx);                                   // -log softmax[y]
       s_ok[tid] = (am - v0 == yv) ? 1 : 0;
     }
+    if (p.y && p.d_logits) {
+      // d loss / d logits[b][tid] by head_fwd_kernel's definition (slu_head.hip): (softmax - one_hot(y)) / B, every lane
+      // summing its slot's denominator in the same order
+      float den = 0.0f;
+      for (int u = v0; u < v1; ++u) den += expf(sm[u] - mx);
+      int yv = (int)p.y[(size_t)b * p.S + sl_];
+      yv = min(max(yv, 0), v1 - v0 - 1);
+      const float inv = 1.0f / (den * (float)p.B);
+      p.d_logits[(size_t)b * V + tid] = expf(sm[tid] - mx) * inv - ((tid - v0 == yv) ? 1.0f / (float)p.B : 0.0f);
+    }
   }
   __syncthreads();
   if (tid == 0 && p.y) {
@@ -191,6 +206,209 @@ head_len_reduce_kernel(const float* __restrict__ row_stats, float* __restrict__ 
     __syncthreads();
   }
   if (threadIdx.x == 0) { loss_acc[0] = r0[0] / (float)B; loss_acc[1] = r1[0] / (float)B; }
+}
+
+
+// ---- Dropout -> Downsample over the valid frames, forward and backward (masked training) ----------------------------
+// slu_dropout_pool_fwd / _bwd (slu_pool.hip) with every window clipped to t < n_b: y is 0 at to >= ceil(n_b / factor), the
+// mean divides by the number of valid frames of its window, dx is 0 at t >= n_b whatever dy holds beyond the valid outputs
+// (it is not read there).  The dropout stream is the dense batch's: element (t, b, c) takes the keep factor it takes in
+// slu_dropout_pool_fwd — injected mask, or Philox (seed, offset [+ *offset_dev]) at index (t * B + b) * C + c — so a
+// stage keeps its masks when the lengths are switched on.  x and the mask are never read at t >= n_b.
+struct PoolLenParams {
+  const float* mask; long long m_st, m_sb;
+  float p, scale;
+  unsigned long long seed, offset;
+  const unsigned long long* offset_dev;
+  const int* lengths;
+  int method, factor;
+  int T, B, C, T_out;
+};
+
+__device__ __forceinline__ float keep_len(const PoolLenParams& q, unsigned long long off, int t, int b, int c) {
+  if (q.p <= 0.0f) return 1.0f;
+  if (q.mask) return q.mask[(long long)t * q.m_st + (long long)b * q.m_sb + c] * q.scale;
+  return philox_uniform(q.seed, off, ((unsigned long long)t * q.B + b) * q.C + c) < (1.0f - q.p) ? q.scale : 0.0f;
+}
+
+__device__ __forceinline__ float4 keep_len4(const PoolLenParams& q, unsigned long long off, int t, int b, int c) {
+  if (q.p <= 0.0f) return make_float4(1.f, 1.f, 1.f, 1.f);
+  if (q.mask) {
+    const float* m = q.mask + (long long)t * q.m_st + (long long)b * q.m_sb + c;
+    return make_float4(m[0] * q.scale, m[1] * q.scale, m[2] * q.scale, m[3] * q.scale);
+  }
+  return philox_keep4(q.seed, off, ((unsigned long long)t * q.B + b) * q.C + c, 1.0f - q.p, q.scale);
+}
+
+__device__ __forceinline__ float4 mul4_rn(float4 a, float4 b) {
+  return make_float4(__fmul_rn(a.x, b.x), __fmul_rn(a.y, b.y), __fmul_rn(a.z, b.z), __fmul_rn(a.w, b.w));
+}
+
+// scalar path: one thread per output element
+__global__ void __launch_bounds__(256)
+dropout_pool_len_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, const PoolLenParams q) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long long)q.T_out * q.B * q.C) return;
+  const int c = (int)(e % q.C);
+  const long long tb = e / q.C;
+  const int b = (int)(tb % q.B), to = (int)(tb / q.B);
+  const int n = clamp_len(q.lengths, b, q.T);
+  const long long t0 = (long long)to * q.factor;
+  float out = 0.0f;
+  if (t0 < n) {
+    const int t1 = (int)min((long long)n, t0 + q.factor);
+    const unsigned long long off = q.offset + (q.offset_dev ? *q.offset_dev : 0ull);
+    const size_t row = (size_t)q.B * q.C, col = (size_t)b * q.C + c;
+    if (q.method == 0) {
+      out = __fmul_rn(x[(size_t)t0 * row + col], keep_len(q, off, (int)t0, b, c));
+    } else {
+      float acc = q.method == 1 ? 0.0f : -INFINITY;
+      for (int t = (int)t0; t < t1; ++t) {
+        const float v = __fmul_rn(x[(size_t)t * row + col], keep_len(q, off, t, b, c));
+        acc = q.method == 1 ? __fadd_rn(acc, v) : fmaxf(acc, v);
+      }
+      out = q.method == 1 ? acc / (float)(t1 - (int)t0) : acc;
+    }
+  }
+  y[e] = out;
+}
+
+// scalar path: one thread per input element
+__global__ void __launch_bounds__(256)
+dropout_pool_len_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x, float* __restrict__ dx,
+                            const PoolLenParams q) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long long)q.T * q.B * q.C) return;
+  const int c = (int)(e % q.C);
+  const long long tb = e / q.C;
+  const int b = (int)(tb % q.B), t = (int)(tb / q.B);
+  const int n = clamp_len(q.lengths, b, q.T);
+  float out = 0.0f;
+  if (t < n) {
+    const int to = t / q.factor, t0 = to * q.factor, t1 = min(n, t0 + q.factor);
+    const unsigned long long off = q.offset + (q.offset_dev ? *q.offset_dev : 0ull);
+    const size_t row = (size_t)q.B * q.C, col = (size_t)b * q.C + c;
+    const float g = dy[(size_t)to * row + col];
+    const float ks = keep_len(q, off, t, b, c);
+    if (q.method == 0) {
+      out = (t == t0) ? g * ks : 0.0f;
+    } else if (q.method == 1) {
+      out = g * ks / (float)(t1 - t0);
+    } else {
+      int arg = t0;
+      float best = -INFINITY;
+      for (int tt = t0; tt < t1; ++tt) {
+        const float v = __fmul_rn(x[(size_t)tt * row + col], keep_len(q, off, tt, b, c));
+        if (v > best) { best = v; arg = tt; }
+      }
+      out = (arg == t) ? g * ks : 0.0f;
+    }
+  }
+  dx[e] = out;
+}
+
+// vector path (C % 4 == 0, 16-byte aligned rows): four channels per thread; grid x over the B * C / 4 quads, y over the
+// OUTPUT frames — the backward thread writes dx for every input frame of its dense window, zeros beyond n_b included
+__global__ void __launch_bounds__(256)
+dropout_pool_len_fwd4_kernel(const float* __restrict__ x, float* __restrict__ y, const PoolLenParams q) {
+  const int C4 = q.C >> 2;
+  const unsigned e = blockIdx.x * 256u + threadIdx.x;
+  if (e >= (unsigned)q.B * C4) return;
+  const int b = e / C4, c = (e - b * C4) * 4;
+  const int to = blockIdx.y;
+  const int n = clamp_len(q.lengths, b, q.T);
+  const long long t0 = (long long)to * q.factor;
+  const size_t row = (size_t)q.B * q.C, col = (size_t)b * q.C + c;
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (t0 < n) {
+    const int t1 = (int)min((long long)n, t0 + q.factor);
+    const unsigned long long off = q.offset + (q.offset_dev ? *q.offset_dev : 0ull);
+    if (q.method == 0) {
+      acc = mul4_rn(*reinterpret_cast<const float4*>(x + (size_t)t0 * row + col), keep_len4(q, off, (int)t0, b, c));
+    } else {
+      if (q.method == 2) acc = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+      for (int t = (int)t0; t < t1; ++t) {
+        const float4 v = mul4_rn(*reinterpret_cast<const float4*>(x + (size_t)t * row + col), keep_len4(q, off, t, b, c));
+        if (q.method == 1) { acc.x = __fadd_rn(acc.x, v.x); acc.y = __fadd_rn(acc.y, v.y); acc.z = __fadd_rn(acc.z, v.z); acc.w = __fadd_rn(acc.w, v.w); }
+        else { acc.x = fmaxf(acc.x, v.x); acc.y = fmaxf(acc.y, v.y); acc.z = fmaxf(acc.z, v.z); acc.w = fmaxf(acc.w, v.w); }
+      }
+      if (q.method == 1) {
+        const float cnt = (float)(t1 - (int)t0);
+        acc.x = acc.x / cnt; acc.y = acc.y / cnt; acc.z = acc.z / cnt; acc.w = acc.w / cnt;
+      }
+    }
+  }
+  *reinterpret_cast<float4*>(y + (size_t)to * row + col) = acc;
+}
+
+__global__ void __launch_bounds__(256)
+dropout_pool_len_bwd4_kernel(const float* __restrict__ dy, const float* __restrict__ x, float* __restrict__ dx,
+                             const PoolLenParams q) {
+  const int C4 = q.C >> 2;
+  const unsigned e = blockIdx.x * 256u + threadIdx.x;
+  if (e >= (unsigned)q.B * C4) return;
+  const int b = e / C4, c = (e - b * C4) * 4;
+  const int to = blockIdx.y;
+  const int n = clamp_len(q.lengths, b, q.T);
+  const long long t0l = (long long)to * q.factor;
+  const int t0 = (int)t0l;                                             // to < T_out: t0 < T
+  const int tend = (int)min((long long)q.T, t0l + q.factor);          // the dense window [t0, tend) is this thread's to write
+  const int t1 = min(n, tend);                                         // its valid part [t0, t1) (empty when t0 >= n)
+  const size_t row = (size_t)q.B * q.C, col = (size_t)b * q.C + c;
+  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (t0 < n) {
+    const unsigned long long off = q.offset + (q.offset_dev ? *q.offset_dev : 0ull);
+    const float4 g = *reinterpret_cast<const float4*>(dy + (size_t)to * row + col);
+    if (q.method == 0) {
+      *reinterpret_cast<float4*>(dx + (size_t)t0 * row + col) = mul4_rn(g, keep_len4(q, off, t0, b, c));
+      for (int t = t0 + 1; t < t1; ++t) *reinterpret_cast<float4*>(dx + (size_t)t * row + col) = zero;
+    } else if (q.method == 1) {
+      const float cnt = (float)(t1 - t0);
+      for (int t = t0; t < t1; ++t) {
+        const float4 k = keep_len4(q, off, t, b, c);
+        *reinterpret_cast<float4*>(dx + (size_t)t * row + col) =
+            make_float4(g.x * k.x / cnt, g.y * k.y / cnt, g.z * k.z / cnt, g.w * k.w / cnt);
+      }
+    } else {
+      int ax = t0, ay = t0, az = t0, aw = t0;                           // first maximum wins (ATen's max_pool1d)
+      float4 best = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+      for (int t = t0; t < t1; ++t) {
+        const float4 v = mul4_rn(*reinterpret_cast<const float4*>(x + (size_t)t * row + col), keep_len4(q, off, t, b, c));
+        if (v.x > best.x) { best.x = v.x; ax = t; }
+        if (v.y > best.y) { best.y = v.y; ay = t; }
+        if (v.z > best.z) { best.z = v.z; az = t; }
+        if (v.w > best.w) { best.w = v.w; aw = t; }
+      }
+      for (int t = t0; t < t1; ++t) {
+        const float4 k = keep_len4(q, off, t, b, c);
+        *reinterpret_cast<float4*>(dx + (size_t)t * row + col) =
+            make_float4(ax == t ? g.x * k.x : 0.f, ay == t ? g.y * k.y : 0.f, az == t ? g.z * k.z : 0.f, aw == t ? g.w * k.w : 0.f);
+      }
+    }
+  }
+  for (int t = max(t0, t1); t < tend; ++t) *reinterpret_cast<float4*>(dx + (size_t)t * row + col) = zero;
+}
+
+static int pool_len_fill(PoolLenParams& q, const char* who, const float* mask, int64_t m_st, int64_t m_sb, float p,
+                         uint64_t seed, uint64_t offset, const uint64_t* offset_dev, const int32_t* lengths, int method,
+                         int64_t factor, int64_t T, int64_t B, int64_t C) {
+  SLU_REQUIRE(lengths, "%s: null lengths", who);
+  SLU_REQUIRE(T > 0 && B > 0 && C > 0 && factor > 0, "%s: non-positive size", who);
+  SLU_REQUIRE(method >= 0 && method <= 2, "%s: downsampling method must be 0 (none), 1 (avg) or 2 (max)", who);
+  SLU_REQUIRE(p >= 0.0f && p < 1.0f, "%s: dropout p must be in [0,1)", who);
+  SLU_REQUIRE(T < (1ll << 31) && B < (1ll << 31) && C < (1ll << 31) && factor < (1ll << 31) &&
+              cdiv(T * B * C, 256) < (1ll << 31), "%s: tensor too large", who);
+  q.mask = mask; q.m_st = m_st; q.m_sb = m_sb; q.p = p; q.scale = 1.0f / (1.0f - p);
+  q.seed = seed; q.offset = offset; q.offset_dev = (const unsigned long long*)offset_dev; q.lengths = (const int*)lengths;
+  q.method = method; q.factor = (int)factor; q.T = (int)T; q.B = (int)B; q.C = (int)C; q.T_out = (int)cdiv(T, factor);
+  return SLU_OK;
+}
+
+// float4 path: channel count and every row start 16-byte aligned, grid within limits (explicit masks are read with
+// scalar loads: arbitrary strides)
+static bool pool_len_vec_ok(const PoolLenParams& q, const float* a, const float* b, const float* c) {
+  if (q.C % 4 != 0 || q.T_out > 65535 || (long long)q.B * q.C >= (1LL << 31)) return false;
+  return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
 }
 
 }  // namespace slu
@@ -237,28 +455,27 @@ extern "C" int slu_seq_pool_len_fwd(const float* x, float* y, const int32_t* len
   return SLU_OK;
 }
 
-extern "C" int slu_cls_maxpool_len_fwd(const float* h, const float* weight, const float* bias, const int32_t* lengths,
-                                       const int64_t* y, const int64_t* values_per_slot, int64_t num_slots, float* logits,
-                                       int32_t* argmax_t, int64_t* pred, float* row_stats, float* loss_acc, int64_t T,
-                                       int64_t B, int64_t C, void* stream) {
-  SLU_REQUIRE(h && weight && bias && logits && argmax_t && pred && values_per_slot, "slu_cls_maxpool_len_fwd: null pointer");
-  SLU_REQUIRE(lengths, "slu_cls_maxpool_len_fwd: null lengths");
-  SLU_REQUIRE(num_slots >= 1 && num_slots <= HEADL_MAX_SLOTS, "slu_cls_maxpool_len_fwd: 1..%d slots supported", HEADL_MAX_SLOTS);
-  SLU_REQUIRE(!y || (row_stats && loss_acc), "slu_cls_maxpool_len_fwd: row_stats / loss_acc required with labels");
-  SLU_REQUIRE(T > 0 && B > 0 && C > 0 && T < (1ll << 31) && B < (1ll << 31) && C < (1ll << 31),
-              "slu_cls_maxpool_len_fwd: bad size");
+static int head_len_launch(const char* who, const float* h, const float* weight, const float* bias, const int32_t* lengths,
+                           const int64_t* y, const int64_t* values_per_slot, int64_t num_slots, float* logits,
+                           int32_t* argmax_t, int64_t* pred, float* d_logits, float* row_stats, float* loss_acc, int64_t T,
+                           int64_t B, int64_t C, void* stream) {
+  SLU_REQUIRE(h && weight && bias && logits && argmax_t && pred && values_per_slot, "%s: null pointer", who);
+  SLU_REQUIRE(lengths, "%s: null lengths", who);
+  SLU_REQUIRE(num_slots >= 1 && num_slots <= HEADL_MAX_SLOTS, "%s: 1..%d slots supported", who, HEADL_MAX_SLOTS);
+  SLU_REQUIRE(!y || (row_stats && loss_acc), "%s: row_stats / loss_acc required with labels", who);
+  SLU_REQUIRE(T > 0 && B > 0 && C > 0 && T < (1ll << 31) && B < (1ll << 31) && C < (1ll << 31), "%s: bad size", who);
   HeadLenParams p;
   p.h = h; p.W = weight; p.bias = bias; p.lengths = (const int*)lengths; p.y = (const long long*)y;
-  p.logits = logits; p.argmax_t = argmax_t; p.pred = (long long*)pred; p.row_stats = row_stats;
+  p.logits = logits; p.argmax_t = argmax_t; p.pred = (long long*)pred; p.row_stats = row_stats; p.d_logits = d_logits;
   p.T = (int)T; p.B = (int)B; p.C = (int)C; p.S = (int)num_slots;
   int V = 0;
   for (int s = 0; s < num_slots; ++s) {
-    SLU_REQUIRE(values_per_slot[s] >= 1, "slu_cls_maxpool_len_fwd: empty slot %d", s);
+    SLU_REQUIRE(values_per_slot[s] >= 1, "%s: empty slot %d", who, s);
     p.slot_begin[s] = V; V += (int)values_per_slot[s];
   }
   p.slot_begin[num_slots] = V;
   p.V = V;
-  SLU_REQUIRE(V >= 1 && V <= HEADL_THREADS, "slu_cls_maxpool_len_fwd: 1..%d classifier outputs supported", HEADL_THREADS);
+  SLU_REQUIRE(V >= 1 && V <= HEADL_THREADS, "%s: 1..%d classifier outputs supported", who, HEADL_THREADS);
   int vp = 1;
   while (vp < V) vp <<= 1;
   p.VP = vp;
@@ -269,5 +486,64 @@ extern "C" int slu_cls_maxpool_len_fwd(const float* h, const float* weight, cons
     hipLaunchKernelGGL(head_len_reduce_kernel, dim3(1), dim3(256), 0, st, (const float*)row_stats, loss_acc, (int)B);
     SLU_CHECK_LAUNCH("head_len_reduce_kernel");
   }
+  return SLU_OK;
+}
+
+extern "C" int slu_cls_maxpool_len_fwd(const float* h, const float* weight, const float* bias, const int32_t* lengths,
+                                       const int64_t* y, const int64_t* values_per_slot, int64_t num_slots, float* logits,
+                                       int32_t* argmax_t, int64_t* pred, float* row_stats, float* loss_acc, int64_t T,
+                                       int64_t B, int64_t C, void* stream) {
+  return head_len_launch("slu_cls_maxpool_len_fwd", h, weight, bias, lengths, y, values_per_slot, num_slots, logits, argmax_t,
+                         pred, nullptr, row_stats, loss_acc, T, B, C, stream);
+}
+
+extern "C" int slu_cls_maxpool_len_ce_fwd(const float* h, const float* weight, const float* bias, const int32_t* lengths,
+                                          const int64_t* y, const int64_t* values_per_slot, int64_t num_slots, float* logits,
+                                          int32_t* argmax_t, int64_t* pred, float* d_logits, float* row_stats,
+                                          float* loss_acc, int64_t T, int64_t B, int64_t C, void* stream) {
+  SLU_REQUIRE(y && d_logits, "slu_cls_maxpool_len_ce_fwd: null pointer (labels and d_logits are required)");
+  return head_len_launch("slu_cls_maxpool_len_ce_fwd", h, weight, bias, lengths, y, values_per_slot, num_slots, logits,
+                         argmax_t, pred, d_logits, row_stats, loss_acc, T, B, C, stream);
+}
+
+extern "C" int slu_dropout_pool_len_fwd(const float* x, const int32_t* lengths, const float* mask, int64_t m_st, int64_t m_sb,
+                                        float p, uint64_t seed, uint64_t offset, const uint64_t* offset_dev, int method,
+                                        int64_t factor, float* y, int64_t T, int64_t B, int64_t C, void* stream) {
+  SLU_REQUIRE(x && y, "slu_dropout_pool_len_fwd: null pointer");
+  PoolLenParams q;
+  int rc = pool_len_fill(q, "slu_dropout_pool_len_fwd", mask, m_st, m_sb, p, seed, offset, offset_dev, lengths, method, factor,
+                         T, B, C);
+  if (rc) return rc;
+  if (pool_len_vec_ok(q, x, y, nullptr)) {
+    hipLaunchKernelGGL(dropout_pool_len_fwd4_kernel, dim3((unsigned)cdiv(B * (C / 4), 256), (unsigned)q.T_out), dim3(256), 0,
+                       (hipStream_t)stream, x, y, q);
+    SLU_CHECK_LAUNCH("dropout_pool_len_fwd4_kernel");
+    return SLU_OK;
+  }
+  hipLaunchKernelGGL(dropout_pool_len_fwd_kernel, dim3((unsigned)cdiv((int64_t)q.T_out * B * C, 256)), dim3(256), 0,
+                     (hipStream_t)stream, x, y, q);
+  SLU_CHECK_LAUNCH("dropout_pool_len_fwd_kernel");
+  return SLU_OK;
+}
+
+extern "C" int slu_dropout_pool_len_bwd(const float* dy, const float* x, const int32_t* lengths, const float* mask,
+                                        int64_t m_st, int64_t m_sb, float p, uint64_t seed, uint64_t offset,
+                                        const uint64_t* offset_dev, int method, int64_t factor, float* dx, int64_t T,
+                                        int64_t B, int64_t C, void* stream) {
+  SLU_REQUIRE(dy && dx, "slu_dropout_pool_len_bwd: null pointer");
+  SLU_REQUIRE(method != 2 || x, "slu_dropout_pool_len_bwd: x is required for max pooling");
+  PoolLenParams q;
+  int rc = pool_len_fill(q, "slu_dropout_pool_len_bwd", mask, m_st, m_sb, p, seed, offset, offset_dev, lengths, method, factor,
+                         T, B, C);
+  if (rc) return rc;
+  if (pool_len_vec_ok(q, dy, dx, method == 2 ? x : nullptr)) {
+    hipLaunchKernelGGL(dropout_pool_len_bwd4_kernel, dim3((unsigned)cdiv(B * (C / 4), 256), (unsigned)q.T_out), dim3(256), 0,
+                       (hipStream_t)stream, dy, x, dx, q);
+    SLU_CHECK_LAUNCH("dropout_pool_len_bwd4_kernel");
+    return SLU_OK;
+  }
+  hipLaunchKernelGGL(dropout_pool_len_bwd_kernel, dim3((unsigned)cdiv(T * B * C, 256)), dim3(256), 0, (hipStream_t)stream, dy,
+                     x, dx, q);
+  SLU_CHECK_LAUNCH("dropout_pool_len_bwd_kernel");
   return SLU_OK;
 }

@@ -873,7 +873,8 @@ class Seq2SeqDecoder(torch.nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------
-# per-utterance lengths (padding-invariant inference; the definition is in include/slu_hip.h and DESIGN.md section 7)
+# per-utterance lengths (padding-invariant inference and masked training; the definition is in include/slu_hip.h and
+# DESIGN.md section 7)
 # ------------------------------------------------------------------------------------------------
 def _host_lengths(lengths, B, T):
     """lengths (list / tensor of B sample counts) -> list of B Python ints, each in [1, T]; ValueError otherwise.  Host
@@ -913,12 +914,14 @@ def _check_len_stages(stages):
                                 ", ".join(map(str, _ops.LEN_HIDDEN_SIZES))))
 
 
-def _run_stages_len(stages, h, lengths):
+def _run_stages_len(stages, h, lengths, training=None):
     """Length-aware evaluation of `stages` (no dropout, no autograd): h = the first stage's input, whose frames at or
     beyond lengths[b] are zero; -> (output, its valid lengths).  The host computes every stage's valid lengths
     (_stage_lengths) and sends them to the device in ONE int32 table.  Always the exact fp32 kernels — slu_wconv_fwd,
     slu_gemm_f32, slu_gru_seq_fwd_len — whatever SLU_FROZEN_MATH says: both sides of the invariant (an utterance in a
-    padded batch / alone) then differ by summation order only.  A split-precision length-aware path does not exist."""
+    padded batch / alone) then differ by summation order only.  A split-precision length-aware path does not exist.
+    training (None: the evaluation above; else the module's training flag): the masked training step — every stage through
+    run_len_train, i.e. inside autograd where it has something to differentiate and with its dropout when `training`."""
     rows = [list(lengths)]
     for st in stages:
         if isinstance(st, _ConvStage):
@@ -929,12 +932,9 @@ def _run_stages_len(stages, h, lengths):
     table = torch.tensor(rows, dtype=torch.int32).to(h.device, non_blocking=True)
     k = 0
     for st in stages:
-        if isinstance(st, _ConvStage):
-            h = st.run_len(h, table[k + 1])
-            k += 2
-        else:
-            h = st.run_len(h, table[k])
-            k += 1
+        n_dev = table[k + 1] if isinstance(st, _ConvStage) else table[k]
+        h = st.run_len(h, n_dev) if training is None else st.run_len_train(h, n_dev, training)
+        k += 2 if isinstance(st, _ConvStage) else 1
     return h, rows[-1], table[k]
 
 
@@ -963,11 +963,12 @@ class _ConvStage:
         """Valid frames of the block's output: ceil(conv_len / pool)."""
         return -(-self.conv_len(n) // self.pool)
 
-    def run_len(self, h, n_conv):
+    def run_len(self, h, n_conv, time_major=None):
         """Length-aware evaluation (exact fp32, no dropout): h = (B, T) waveform or channels-last (B, L, C) with a zero
         tail, n_conv = int32 device lengths of the raw convolution's output.  The existing convolution call with pool 1,
         slope 1 and no abs (convolution + bias), then slu_pool_act_len_fwd: abs / max-pool over the valid frames /
-        activation, zero beyond — channels-last, or time-major on the last CNN block."""
+        activation, zero beyond — channels-last, or time-major on the last CNN block (time_major overrides that)."""
+        time_major = self.time_major if time_major is None else time_major
         with torch.no_grad():
             if h.dim() == 2:
                 h = h.unsqueeze(2)
@@ -978,7 +979,19 @@ class _ConvStage:
             else:
                 w, bias = self.conv.weight.detach(), self.conv.bias.detach()
             raw, _, _ = _ops.wconv_fwd(h, w, bias, B, l_in, c_in, self.conv.stride, False, 1, 1.0, False, False)
-            return _ops.pool_act_len_fwd(raw, n_conv, self.pool, self.do_abs, self.slope, self.time_major)
+            return _ops.pool_act_len_fwd(raw, n_conv, self.pool, self.do_abs, self.slope, time_major)
+
+    def run_len_train(self, h, n_conv, training):
+        """A FROZEN block inside a masked training step (Model.forward(lengths=...) refuses trainable ones): run_len, then
+        the block's nn.Dropout as run() applies it — on the channels-last tensor, the same stream and masks as without
+        lengths; a dropped padded frame is still zero."""
+        if not (self.drop > 0.0 and training):
+            return self.run_len(h, n_conv)
+        h = self.run_len(h, n_conv, time_major=False)
+        p, mask, seed, offset = _dropout_args(self.drop_name, self.site, self.drop, training, cnn=True)
+        with torch.no_grad():
+            h = _DropOnlyFn.apply(h.contiguous(), p, mask, seed, offset)
+        return h.transpose(0, 1).contiguous() if self.time_major else h
 
     def _frozen_cache(self, nsplit):
         """What a FROZEN block recomputed per call in round 2: the Sinc filterbank and the filters packed in MFMA
@@ -1102,6 +1115,35 @@ class _RnnStage:
             out = _ops.gru_seq_fwd_len(gx, g.weight_hh_l0.detach(), rev[0], g.bias_hh_l0.detach(), rev[1], n_in, T, B, H, D)
             if self.factor > 1:
                 out = _ops.seq_pool_len_fwd(out, n_in, self.method, self.factor)
+            return out
+
+    def run_len_train(self, xt, n_in, training):
+        """The layer inside a masked training step (exact fp32): xt and n_in as run_len, dropout when `training` (the dense
+        batch's masks: _dropout_args).  A layer with a trainable parameter, or behind one (xt requires a gradient), runs as
+        ops.GRULayerLenFn; a frozen one runs the same kernels outside autograd, without a reserve."""
+        g = self.gru
+        p, mask, seed, offset = _dropout_args(self.drop_name, self.site, self.p, training)
+        w_ih, b_ih = g._stacked_ih()
+        if any(q.requires_grad for q in g.parameters()) or xt.requires_grad:
+            if g.bidirectional:
+                ih = (g.weight_ih_l0, g.weight_ih_l0_reverse, g.bias_ih_l0, g.bias_ih_l0_reverse)
+                rev = (g.weight_hh_l0_reverse, g.bias_hh_l0_reverse)
+            else:
+                ih, rev = (g.weight_ih_l0, None, g.bias_ih_l0, None), (None, None)
+            return _ops.GRULayerLenFn.apply(xt, w_ih.detach(), b_ih.detach(), *ih, g.weight_hh_l0, g.bias_hh_l0, rev[0],
+                                            rev[1], n_in, p, mask, seed, offset, self.method, self.factor)
+        with torch.no_grad():
+            xt = xt.contiguous()
+            T, B, I = xt.shape
+            H, D = g.hidden_size, 2 if g.bidirectional else 1
+            gx = _ops.gemm(xt.view(T * B, I), w_ih.detach().t(), b_ih.detach())
+            rev = (g.weight_hh_l0_reverse.detach(), g.bias_hh_l0_reverse.detach()) if g.bidirectional else (None, None)
+            out, _ = _ops.gru_seq_fwd_len_rsv(gx, g.weight_hh_l0.detach(), rev[0], g.bias_hh_l0.detach(), rev[1], n_in, T, B,
+                                              H, D, False)
+            if p > 0.0 or self.factor > 1:
+                offset, offset_dev, sub_batch = offset if isinstance(offset, tuple) else (offset, None, 0)
+                assert sub_batch == 0
+                out = _ops.dropout_pool_len_fwd(out, n_in, mask, p, seed, offset, self.method, self.factor, offset_dev)
             return out
 
 
@@ -1584,16 +1626,61 @@ class Model(torch.nn.Module):
         self.last_loss_acc = _ops.IntentHeadFn.last_loss_acc
         return loss, acc
 
-    def forward(self, x, y_intent, *, rng_step=None, n_prefix=0):
+    def forward(self, x, y_intent, *, lengths=None, rng_step=None, n_prefix=0):
         """x (B,T), y_intent (B,num_slots) -> (loss = sum of per-slot CE, acc = all slots right)
         (reference models.py:797-823); classifier, max over time, CE and accuracy are one fused op.
         seq2seq: y_intent (B,U,num_labels) one-hot -> (-mean log p(y|x), host zero) (models.py:825-828).
         Keyword-only extras (not in the reference) for training.Trainer: rng_step = the dropout-stream index of this
         forward (None = the next one; or a 1-element int64 CUDA tensor holding step * 16 for captured steps),
-        n_prefix > 0: x is the output of the first n_prefix encoder stages (look-ahead pipeline)."""
+        n_prefix > 0: x is the output of the first n_prefix encoder stages (look-ahead pipeline).
+        lengths (None: the call as it was): the utterances' sample counts, each in [1, T] -> the masked step (_forward_len):
+        loss and gradients are the mean over the rows of what each x[b:b+1, :lengths[b]], y[b:b+1] gives run alone."""
+        if lengths is not None:
+            return self._forward_len(x, y_intent, lengths, rng_step, n_prefix)
         if n_prefix == 0:
             x = self.pretrained_model._to_device(x)[0]
         return self.forward_from(x, n_prefix, y_intent, next_rng_step() if rng_step is None else rng_step)
+
+    def _forward_len(self, x, y_intent, lengths, rng_step, n_prefix):
+        """Model.forward with per-utterance lengths (DESIGN.md section 7 "Lengths"): the waveform tail is zeroed, every
+        stage runs length-aware in exact fp32 (frozen ones outside autograd, trainable GRU layers as ops.GRULayerLenFn),
+        the head is ops.IntentHeadLenFn.  In train() mode every dropout site draws the masks it draws without lengths
+        (the dense batch's Philox stream or the injected masks), so with p = 0 or injected masks the gradients equal the
+        mean of the alone runs' exactly, with Philox masks in distribution.  Everything that can be refused is refused
+        here, on the host, before the first launch."""
+        if n_prefix > 0:
+            raise ValueError("lengths: the look-ahead pipeline (n_prefix > 0) has no masked steps")
+        if self.seq2seq:
+            raise ValueError("lengths: seq2seq models are not supported (the decoder's attention would have to mask the "
+                             "encoder frames as well)")
+        if torch.is_tensor(rng_step):
+            raise ValueError("lengths: captured steps (a device-resident rng_step) are not supported")
+        if x.dim() != 2:
+            raise ValueError("lengths: expected a (B, T) waveform batch")
+        pm = self.pretrained_model
+        host = _host_lengths(lengths, x.shape[0], x.shape[1])
+        stages = pm._stages() + list(self._intent_stages)
+        _check_len_stages(stages)
+        if self.augment and self.training:
+            raise ValueError("lengths: augment=True is not supported (the augmentation moves the utterances' ends)")
+        for st in pm._cnn_stages:
+            if any(q.requires_grad for q in st.parameters()):
+                raise ValueError("lengths: a trainable CNN block (the unfreezing has reached the convolutions) has no "
+                                 "length-aware backward pass yet — that is the next step; freeze the CNN blocks or train "
+                                 "without lengths")
+        (x,) = pm._to_device(x)
+        pm._cnn_stages[-1].time_major = True
+        _DropoutState.current = next_rng_step() if rng_step is None else rng_step
+        with torch.no_grad():
+            x = _ops.pcm16_to_f32(x) if x.dtype == torch.int16 else x.float()
+            dev_len = torch.tensor(host, dtype=torch.int32).to(x.device, non_blocking=True)
+            x = _ops.mask_rows_len(x, dev_len)
+        h, _, n_dev = _run_stages_len(stages, x, host, training=self.training)
+        cls = self.intent_layers[-2]
+        loss, acc, _, _ = _ops.IntentHeadLenFn.apply(h, n_dev.contiguous(), cls.weight, cls.bias, y_intent.to(h.device),
+                                                     tuple(self.values_per_slot))
+        self.last_loss_acc = _ops.IntentHeadFn.last_loss_acc
+        return loss, acc
 
     def one_hot_to_string(self, input, S):
         """input (T, |S|) one-hot rows, S list of labels -> the string (reference models.py:731-737; the strips are

@@ -89,6 +89,14 @@ SIGNATURES = {
     "slu_seq_pool_len_fwd": (c_int, [vp, vp, vp, c_int, c_i64, c_i64, c_i64, c_i64, vp]),
     "slu_cls_maxpool_len_fwd": (c_int, [vp, vp, vp, vp, vp, ctypes.POINTER(c_i64), c_i64, vp, vp, vp, vp, vp, c_i64, c_i64,
                                         c_i64, vp]),
+    "slu_gru_seq_fwd_len_rsv": (c_int, [vp, vp, vp, vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, vp]),
+    "slu_gru_seq_bwd_len": (c_int, [vp, vp, vp, vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, vp]),
+    "slu_dropout_pool_len_fwd": (c_int, [vp, vp, vp, c_i64, c_i64, c_f32, c_u64, c_u64, vp, c_int, c_i64, vp, c_i64, c_i64,
+                                         c_i64, vp]),
+    "slu_dropout_pool_len_bwd": (c_int, [vp, vp, vp, vp, c_i64, c_i64, c_f32, c_u64, c_u64, vp, c_int, c_i64, vp, c_i64,
+                                         c_i64, c_i64, vp]),
+    "slu_cls_maxpool_len_ce_fwd": (c_int, [vp, vp, vp, vp, vp, ctypes.POINTER(c_i64), c_i64, vp, vp, vp, vp, vp, vp, c_i64,
+                                           c_i64, c_i64, vp]),
     "slu_comm_version": (c_int, []),
     "slu_comm_unique_id": (c_int, [vp]),
     "slu_comm_init": (c_int, [vp, vp, c_i64, c_i64]),

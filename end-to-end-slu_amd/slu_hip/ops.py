@@ -1201,7 +1201,7 @@ def cls_maxpool_ce_fwd(h, weight, bias, y, values_per_slot, want_grad, epoch_sum
 
 
 # ------------------------------------------------------------------------------------------------
-# per-utterance lengths: padding-invariant inference (include/slu_hip.h; csrc/slu_varlen.hip, slu_gru.hip)
+# per-utterance lengths: padding-invariant inference and masked training (include/slu_hip.h; csrc/slu_varlen.hip, slu_gru.hip)
 # ------------------------------------------------------------------------------------------------
 LEN_HIDDEN_SIZES = (16, 32, 64, 128)       # hidden sizes slu_gru_seq_fwd_len takes (the persistent recurrence kernels)
 
@@ -1214,10 +1214,7 @@ def _len_check(lengths, B, *tensors):
         if t is not None and t.requires_grad:
             raise RuntimeError("the length-aware kernels are inference only (no backward): call them under torch.no_grad() "
                                "with detached tensors")
-    if not torch.is_tensor(lengths) or lengths.dtype != torch.int32 or not lengths.is_cuda:
-        raise TypeError("lengths must be an int32 CUDA tensor")
-    if lengths.dim() != 1 or lengths.numel() != B or not lengths.is_contiguous():
-        raise ValueError("lengths: expected %d contiguous entries, got shape %s" % (B, tuple(lengths.shape)))
+    _len_ok(lengths, B)
 
 
 def mask_rows_len(x, lengths):
@@ -1298,6 +1295,108 @@ def cls_maxpool_len_fwd(h, weight, bias, lengths, y, values_per_slot):
     return loss_acc, logits, pred, argmax_t
 
 
+# ---- masked training (include/slu_hip.h "masked training"): the same stages with a reserve, a BPTT and dropout ----------
+def _len_ok(lengths, B):
+    if not torch.is_tensor(lengths) or lengths.dtype != torch.int32 or not lengths.is_cuda:
+        raise TypeError("lengths must be an int32 CUDA tensor")
+    if lengths.dim() != 1 or lengths.numel() != B or not lengths.is_contiguous():
+        raise ValueError("lengths: expected %d contiguous entries, got shape %s" % (B, tuple(lengths.shape)))
+    return lengths
+
+
+def _len_hidden_ok(H):
+    if H not in LEN_HIDDEN_SIZES:
+        raise ValueError("lengths: hidden size %d has no length-aware recurrence kernel (supported: %s)"
+                         % (H, ", ".join(map(str, LEN_HIDDEN_SIZES))))
+
+
+def gru_seq_fwd_len_rsv(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lengths, T, B, H, D, want_reserve):
+    """gru_seq_fwd with per-sequence lengths -> (out (T, B, D*H), zero at t >= lengths[b]; reserve or None).  The reserve
+    has gru_seq_fwd's layout; at t >= lengths[b] its contents are unspecified (gru_seq_bwd_len does not use them)."""
+    L = _lib.load()
+    _len_ok(lengths, B)
+    _len_hidden_ok(H)
+    out = torch.empty(T, B, D * H, dtype=torch.float32, device=gx.device)
+    reserve = None
+    if want_reserve:
+        reserve = torch.empty(L.slu_gru_reserve_bytes(T, B, H, D) // 4, dtype=torch.float32, device=gx.device)
+    _lib.check(L.slu_gru_seq_fwd_len_rsv(gx.data_ptr(), w_hh_f.data_ptr(), _ptr(w_hh_r), b_hh_f.data_ptr(), _ptr(b_hh_r),
+                                         out.data_ptr(), _ptr(reserve), lengths.data_ptr(), T, B, H, D, _stream()),
+               "slu_gru_seq_fwd_len_rsv")
+    return out, reserve
+
+
+def gru_seq_bwd_len(d_out, reserve, w_hh_f, w_hh_r, lengths, T, B, H, D):
+    """gru_seq_bwd for a reserve of gru_seq_fwd_len_rsv -> (d_gx, d_gh, d_bias_part): rows t >= lengths[b] are exactly zero
+    whatever d_out holds there."""
+    L = _lib.load()
+    _len_ok(lengths, B)
+    _len_hidden_ok(H)
+    d_out = _f32c(d_out, "d_out")
+    dev = d_out.device
+    d_gx = torch.empty(T, B, D * 3 * H, dtype=torch.float32, device=dev)
+    d_gh = torch.empty(T, B, D * 3 * H, dtype=torch.float32, device=dev)
+    nbt = int(L.slu_gru_bias_tiles(T, B, H, D))
+    d_bias_part = torch.empty(nbt, D, 6 * H, dtype=torch.float32, device=dev)
+    _lib.check(L.slu_gru_seq_bwd_len(d_out.data_ptr(), reserve.data_ptr(), w_hh_f.data_ptr(), _ptr(w_hh_r), d_gx.data_ptr(),
+                                     d_gh.data_ptr(), d_bias_part.data_ptr(), lengths.data_ptr(), T, B, H, D, _stream()),
+               "slu_gru_seq_bwd_len")
+    return d_gx, d_gh, d_bias_part
+
+
+def dropout_pool_len_fwd(x, lengths, mask, p, seed, offset, method, factor, offset_dev=None):
+    """dropout_pool_fwd with windows clipped to t < lengths[b]: zero at to >= ceil(lengths[b] / factor).  The keep factor of
+    element (t, b, c) is dropout_pool_fwd's (the dense batch's stream)."""
+    L = _lib.load()
+    x = _f32c(x, "x")
+    T, B, C = x.shape
+    _len_ok(lengths, B)
+    y = torch.empty(-(-T // factor), B, C, dtype=torch.float32, device=x.device)
+    mp, mst, msb = _mask_args(mask, T, B, C)
+    _lib.check(L.slu_dropout_pool_len_fwd(x.data_ptr(), lengths.data_ptr(), mp, mst, msb, float(p), int(seed), int(offset),
+                                          _ptr(offset_dev), METHODS[method], factor, y.data_ptr(), T, B, C, _stream()),
+               "slu_dropout_pool_len_fwd")
+    return y
+
+
+def dropout_pool_len_bwd(dy, x, lengths, mask, p, seed, offset, method, factor, offset_dev=None):
+    """-> dx (T, B, C), exactly zero at t >= lengths[b] whatever dy holds beyond the valid outputs."""
+    L = _lib.load()
+    T, B, C = x.shape
+    _len_ok(lengths, B)
+    dy = _f32c(dy, "dy")
+    dx = torch.empty(T, B, C, dtype=torch.float32, device=x.device)
+    mp, mst, msb = _mask_args(mask, T, B, C)
+    _lib.check(L.slu_dropout_pool_len_bwd(dy.data_ptr(), x.data_ptr(), lengths.data_ptr(), mp, mst, msb, float(p), int(seed),
+                                          int(offset), _ptr(offset_dev), METHODS[method], factor, dx.data_ptr(), T, B, C,
+                                          _stream()), "slu_dropout_pool_len_bwd")
+    return dx
+
+
+def cls_maxpool_len_ce_fwd(h, weight, bias, lengths, y, values_per_slot):
+    """cls_maxpool_len_fwd with labels -> (loss_acc (2), logits (B, V), pred (B, S), argmax_t (B, V) int32, d_logits (B, V))"""
+    import ctypes
+    L = _lib.load()
+    h, weight, bias = _f32c(h, "h"), _f32c(weight, "weight"), _f32c(bias, "bias")
+    T, B, C = h.shape
+    _len_ok(lengths, B)
+    S = len(values_per_slot)
+    V = int(sum(values_per_slot))
+    dev = h.device
+    logits = torch.empty(B, V, dtype=torch.float32, device=dev)
+    argmax_t = torch.empty(B, V, dtype=torch.int32, device=dev)
+    pred = torch.empty(B, S, dtype=torch.int64, device=dev)
+    d_logits = torch.empty(B, V, dtype=torch.float32, device=dev)
+    row_stats = torch.empty(B, 2, dtype=torch.float32, device=dev)
+    loss_acc = torch.empty(2, dtype=torch.float32, device=dev)
+    vps = (ctypes.c_int64 * S)(*[int(v) for v in values_per_slot])
+    _lib.check(L.slu_cls_maxpool_len_ce_fwd(h.data_ptr(), weight.data_ptr(), bias.data_ptr(), lengths.data_ptr(),
+                                            y.data_ptr(), vps, S, logits.data_ptr(), argmax_t.data_ptr(), pred.data_ptr(),
+                                            d_logits.data_ptr(), row_stats.data_ptr(), loss_acc.data_ptr(), T, B, C,
+                                            _stream()), "slu_cls_maxpool_len_ce_fwd")
+    return loss_acc, logits, pred, argmax_t, d_logits
+
+
 def head_dropout_fusable(weight, p, mask, method, factor, h=None):
     """The Dropout between the last intent GRU layer and the classifier can be drawn inside the head kernels: Philox
     masks (no injected mask tensor), no Downsample, four-channel alignment OF WHAT THE HEAD READS — the classifier's
@@ -1364,6 +1463,43 @@ class IntentHeadFn(torch.autograd.Function):
                                             T, B, C, V, _stream()), "slu_cls_maxpool_ce_bwd")
         return dh, dW, db, None, None, None
 
+
+class IntentHeadLenFn(torch.autograd.Function):
+    """IntentHeadFn with the max over time taken over t < lengths[b] (masked training; no fused dropout: the stage in front
+    applies it).  h time-major (T, B, C), zero at t >= lengths[b].  Returns (loss, acc, logits, pred); the backward pass is
+    IntentHeadFn's kernel: argmax_t < lengths[b], so d_h is zero-filled and non-zero at valid frames only."""
+
+    @staticmethod
+    def forward(ctx, h, lengths, weight, bias, y, values_per_slot):
+        h = h.contiguous()
+        y = y.contiguous()
+        loss_acc, logits, pred, argmax_t, d_logits = cls_maxpool_len_ce_fwd(h, weight, bias, lengths, y, values_per_slot)
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            ctx.save_for_backward(h, weight, argmax_t, d_logits)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(logits, pred)
+        acc = loss_acc[1]
+        ctx.mark_non_differentiable(acc)
+        IntentHeadFn.last_loss_acc = loss_acc
+        return loss_acc[0], acc, logits, pred
+
+    @staticmethod
+    def backward(ctx, d_loss, _d_acc, _d_logits, _d_pred):
+        L = _lib.load()
+        if d_loss is None:
+            return None, None, None, None, None, None
+        h, weight, argmax_t, d_logits = ctx.saved_tensors
+        T, B, C = h.shape
+        V = weight.shape[0]
+        g = d_loss.contiguous().float()
+        dh = torch.empty_like(h) if ctx.needs_input_grad[0] else None
+        need_w = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
+        dW = torch.empty_like(weight) if need_w else None
+        db = torch.empty(V, dtype=torch.float32, device=h.device) if need_w else None
+        _lib.check(L.slu_cls_maxpool_ce_bwd(d_logits.data_ptr(), argmax_t.data_ptr(), h.data_ptr(), weight.data_ptr(),
+                                            g.data_ptr(), _ptr(dh), _ptr(dW), _ptr(db), 0.0, 0, 0, 0, T, B, C, V, _stream()),
+                   "slu_cls_maxpool_ce_bwd")
+        return dh, None, dW, db, None, None
 
 
 class FrameHeadFn(torch.autograd.Function):
@@ -1696,32 +1832,77 @@ class GRULayerFn(torch.autograd.Function):
         else:
             d_raw = dropout_pool_bwd(dy, raw, mask, p, seed, offset, method, factor, ctx.offset_dev)
         d_gx, d_gh, dbp = gru_seq_bwd(d_raw, reserve, w_hh_f, w_hh_r, T, B, H, D)
-        ng = ctx.needs_input_grad
-        # positions: 0 x | 1 w_ih 2 b_ih (storage, no grad) | 3 w_ih_f 4 w_ih_r 5 b_ih_f 6 b_ih_r |
-        #            7 w_hh_f 8 b_hh_f 9 w_hh_r 10 b_hh_r
-        need_ih, need_hh = ng[3] or ng[4], [ng[7 + 2 * d] for d in range(D)]
-        bias_part = dbp if ng[5] or ng[6] or ng[8] or ng[10] else None
-        ih, hh = _gru_wgrad_operands(x, raw, d_gx, d_gh, T, B, I, H, D)
-        kind, budget, mode = gru_wgrad_plan(T, B, I, H, D, need_ih, need_hh, gemm_tn_splitk_ok([ih] + hh))
-        if kind == "batched":
-            dW_ih, dW_hh, db, join = _wgrad_batched(ih, hh, bias_part)
-        elif kind == "splitk":
-            dW_ih, dW_hh, db, join = _wgrad_splitk(ih, hh, bias_part, budget, mode)
+        return tuple(_gru_layer_grads(ctx.needs_input_grad[:11], x, raw, d_gx, d_gh, dbp, w_ih, T, B, I, H, D) + [None] * 8)
+
+
+def _gru_layer_grads(ng, x, raw, d_gx, d_gh, dbp, w_ih, T, B, I, H, D):
+    """The parameter and input gradients of a GRU layer from its BPTT outputs: the weight-gradient plan and dx.
+    ng / result positions: 0 x | 1 w_ih 2 b_ih (storage, no grad) | 3 w_ih_f 4 w_ih_r 5 b_ih_f 6 b_ih_r |
+                           7 w_hh_f 8 b_hh_f 9 w_hh_r 10 b_hh_r"""
+    need_ih, need_hh = ng[3] or ng[4], [ng[7 + 2 * d] for d in range(D)]
+    bias_part = dbp if ng[5] or ng[6] or ng[8] or ng[10] else None
+    ih, hh = _gru_wgrad_operands(x, raw, d_gx, d_gh, T, B, I, H, D)
+    kind, budget, mode = gru_wgrad_plan(T, B, I, H, D, need_ih, need_hh, gemm_tn_splitk_ok([ih] + hh))
+    if kind == "batched":
+        dW_ih, dW_hh, db, join = _wgrad_batched(ih, hh, bias_part)
+    elif kind == "splitk":
+        dW_ih, dW_hh, db, join = _wgrad_splitk(ih, hh, bias_part, budget, mode)
+    else:
+        dW_ih, dW_hh, db, join = _wgrad_forked(ih, hh, bias_part, need_ih, need_hh, T)
+    grads = [None] * 11
+    if ng[0]:                                          # dx = d_gx W_ih (both directions, K = D*3H)
+        grads[0] = _gru_dx(ih[0], w_ih, T, B, I, H, D)
+    for d in range(D):
+        grads[3 + d] = dW_ih[d] if dW_ih else None
+        grads[7 + 2 * d] = dW_hh[d]
+        if ng[5 + d]:
+            grads[5 + d] = db[d, :3 * H]
+        if ng[8 + 2 * d]:
+            grads[8 + 2 * d] = db[d, 3 * H:]
+    if join:
+        _Fork.join(x.device)
+    return grads
+
+
+class GRULayerLenFn(torch.autograd.Function):
+    """GRULayerFn with per-sequence lengths (masked training): x time-major (T, B, I), zero at t >= lengths[b] ->
+    (ceil(T / factor), B, D*H), zero at to >= ceil(lengths[b] / factor).  Always exact fp32, like the length-aware inference
+    stages: slu_gemm_f32 -> slu_gru_seq_fwd_len_rsv -> slu_dropout_pool_len_fwd; backward slu_dropout_pool_len_bwd ->
+    slu_gru_seq_bwd_len -> GRULayerFn's weight-gradient plan and dx, which are correct as they are on zeroed d_gx / d_gh
+    rows (the reverse scan's h_{t-1} is raw[t + 1], which is 0 at t = lengths[b] - 1)."""
+
+    @staticmethod
+    def forward(ctx, x, w_ih, b_ih, w_ih_f, w_ih_r, b_ih_f, b_ih_r, w_hh_f, b_hh_f, w_hh_r, b_hh_r,
+                lengths, p, mask, seed, offset, method, factor):
+        x = x.contiguous()
+        T, B, I = x.shape
+        H = w_hh_f.shape[1]
+        D = 1 if w_hh_r is None else 2
+        need = any(ctx.needs_input_grad[:11])
+        gx = gemm(x.view(T * B, I), w_ih.t(), b_ih)
+        raw, reserve = gru_seq_fwd_len_rsv(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lengths, T, B, H, D, need)
+        offset, offset_dev, sub_batch = offset if isinstance(offset, tuple) else (offset, None, 0)
+        assert sub_batch == 0, "sub-batched dropout streams are for the look-ahead pipeline, which has no masked steps"
+        if p == 0.0 and factor == 1:
+            y = raw                                      # already zero at t >= lengths[b]
         else:
-            dW_ih, dW_hh, db, join = _wgrad_forked(ih, hh, bias_part, need_ih, need_hh, T)
-        grads = [None] * 19
-        if ng[0]:                                          # dx = d_gx W_ih (both directions, K = D*3H)
-            grads[0] = _gru_dx(ih[0], w_ih, T, B, I, H, D)
-        for d in range(D):
-            grads[3 + d] = dW_ih[d] if dW_ih else None
-            grads[7 + 2 * d] = dW_hh[d]
-            if ng[5 + d]:
-                grads[5 + d] = db[d, :3 * H]
-            if ng[8 + 2 * d]:
-                grads[8 + 2 * d] = db[d, 3 * H:]
-        if join:
-            _Fork.join(x.device)
-        return tuple(grads)
+            y = dropout_pool_len_fwd(raw, lengths, mask, p, seed, offset, method, factor, offset_dev)
+        if need:
+            ctx.save_for_backward(x, raw, reserve, mask, w_ih, w_hh_f, w_hh_r, lengths)
+            ctx.offset_dev = offset_dev
+            ctx.cfg = (T, B, I, H, D, p, seed, offset, method, factor)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        T, B, I, H, D, p, seed, offset, method, factor = ctx.cfg
+        x, raw, reserve, mask, w_ih, w_hh_f, w_hh_r, lengths = ctx.saved_tensors
+        if p == 0.0 and factor == 1:
+            d_raw = dy                                   # the BPTT kernel does not use d_out at t >= lengths[b]
+        else:
+            d_raw = dropout_pool_len_bwd(dy, raw, lengths, mask, p, seed, offset, method, factor, ctx.offset_dev)
+        d_gx, d_gh, dbp = gru_seq_bwd_len(d_raw, reserve, w_hh_f, w_hh_r, lengths, T, B, H, D)
+        return tuple(_gru_layer_grads(ctx.needs_input_grad[:11], x, raw, d_gx, d_gh, dbp, w_ih, T, B, I, H, D) + [None] * 7)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -23,7 +23,7 @@ import pandas as pd
 import torch
 from tqdm import tqdm
 
-from data import SLUDataset, ASRDataset
+from data import SLUDataset, ASRDataset, mask_padding_enabled as data_mask_padding_enabled
 from models import PretrainedModel, Model, next_rng_step
 from slu_hip import dp, ops, pipeline
 
@@ -153,10 +153,22 @@ def _same_form(batch, first):
     return tuple(batch[0].shape) == tuple(first[0].shape) and batch[0].dtype == first[0].dtype
 
 
+def mask_train_enabled():
+    """SLU_MASK_TRAIN: "0" (default) — the training loops drop the lengths (_drop_lengths); "1" — they train on them
+    (Model.forward(lengths=...)): every step's loss and gradients are the mean of what its utterances give alone, whatever
+    the batch was padded to.  Needs SLU_MASK_PADDING=1 (the collate function supplies the lengths)."""
+    v = os.environ.get("SLU_MASK_TRAIN", "0")
+    if v not in ("0", "1"):
+        raise ValueError("SLU_MASK_TRAIN=%r: expected 0 or 1" % (v,))
+    if v == "1" and not data_mask_padding_enabled():
+        raise ValueError("SLU_MASK_TRAIN=1 needs SLU_MASK_PADDING=1: the lengths come from the collate function")
+    return v == "1"
+
+
 class _drop_lengths:
     """SLU batches of the training loops: (x, y) whatever the loader yields.  With SLU_MASK_PADDING=1 the collate function
-    adds the utterances' sample counts as a third element (data.CollateWavsSLU); only evaluation uses them
-    (Model.eval_group(lengths=...)) — training on masked padding is not implemented, its arithmetic stays as it is.
+    adds the utterances' sample counts as a third element (data.CollateWavsSLU); evaluation uses them
+    (Model.eval_group(lengths=...)) and, with SLU_MASK_TRAIN=1, so does training — then this wrapper is not applied.
     Keeps the loader's len() (the look-ahead pipeline sizes its first super-batches by the run's length)."""
 
     def __init__(self, loader):
@@ -262,6 +274,7 @@ class Trainer:
     def __init__(self, model, config):
         self.model = model
         self.config = config
+        mask_train_enabled()                     # SLU_MASK_TRAIN=1 without SLU_MASK_PADDING=1 fails here, not at the first step
         if isinstance(self.model, PretrainedModel):
             self.lr = config.pretraining_lr
             self.checkpoint_path = os.path.join(self.config.folder, "pretraining")
@@ -371,8 +384,11 @@ class Trainer:
             if ptype == 2:
                 loss = phoneme_loss + word_loss
             return [phoneme_loss, word_loss, phoneme_acc, word_acc], loss
-        if len(batch) == 3:                    # (x, y, lengths): evaluation under SLU_MASK_PADDING=1 (_iterate)
+        if len(batch) == 3:                    # (x, y, lengths): SLU_MASK_PADDING=1 (_iterate)
             x, y_intent, lengths = batch
+            if getattr(self.model, "training", False):          # a masked training step (SLU_MASK_TRAIN=1)
+                intent_loss, intent_acc = self.model(x, y_intent, lengths=lengths)
+                return [intent_loss, intent_acc], intent_loss
             (intent_loss, intent_acc), = self.model.eval_group([x], [y_intent], [lengths])
             return [intent_loss, intent_acc], intent_loss
         x, y_intent = batch
@@ -731,6 +747,11 @@ class Trainer:
             sums = self._sums_buffer()
             sums.zero_()
         if train and not asr:
+            if mask_train_enabled():
+                # masked steps are eager: no look-ahead super-batches, no captured steps (a step's lengths table and the
+                # zeroed waveform tail belong to its own batch)
+                yield from self._iterate_eager(loader, train, asr, sums)
+                return
             loader = _drop_lengths(loader)
         depth, n_prefix = self.lookahead_depth(train, asr)
         group_eval = (not train and not asr and hasattr(self.model, "eval_group") and not models_masks_injected()

@@ -581,7 +581,8 @@ int slu_beam_backtrack(const int32_t* backptr, const int32_t* labels, int64_t* o
  *   frames only (the average divides by their count, as avg_pool1d(ceil_mode=True) does at the end of a tensor); GRU
  *   direction 0 runs t = 0 .. n - 1, direction 1 starts at t = n - 1 from h = 0; the head's max over time and its
  *   argmax_t range over t < n only.  So an utterance's logits in a padded batch are its logits when it is run alone.
- * Forward / inference only: no route, no reserve, no dropout.  NULL lengths: SLU_ERR_INVALID_ARG.  A length outside
+ * These five are forward / inference only: no route, no reserve, no dropout (masked training: the next block).  NULL
+ * lengths: SLU_ERR_INVALID_ARG.  A length outside
  * [1, frames] is the HOST's to reject (slu_hip/ops.py raises ValueError before any launch); the kernels clamp it into
  * that range, so a bad value cannot index out of bounds.  The convolution and the GRU input projection need no entry
  * point of their own: on an input with a zero tail slu_wconv_fwd (pool = 1, slope = 1.0, do_abs = 0: convolution +
@@ -615,6 +616,51 @@ int slu_cls_maxpool_len_fwd(const float* h, const float* weight, const float* bi
                             const int64_t* y, const int64_t* values_per_slot, int64_t num_slots, float* logits,
                             int32_t* argmax_t, int64_t* pred, float* row_stats, float* loss_acc, int64_t T, int64_t B,
                             int64_t C, void* stream);
+
+/* -------- masked training: the lengths through BPTT and the intent head — added under ABI 10 (five new entry points;
+ * nothing existing changed, so the version number stays).  The definition is this library's own:
+ *   forward   exactly the length-aware definition above, now also with dropout: element (t, b, c) of a dropout site takes
+ *             the keep factor it takes WITHOUT lengths (injected mask, or the dense batch's Philox index (t * B + b) * C + c),
+ *             dropout comes before the Downsample, and a dropped padded frame is still zero;
+ *   loss      the head's mean over the B rows of each row's loss (slu_cls_maxpool_ce_fwd's definition);
+ *   hence     the gradient of every parameter for a padded batch with lengths = (1 / B) * sum over b of its gradient when
+ *             row b, truncated to lengths[b], is run alone through the kernels without lengths — exactly (up to summation
+ *             order) with p = 0 or injected masks, in distribution with Philox masks (the alone run indexes its own stream);
+ *   and       every activation gradient is exactly 0.0f at frames at or beyond the stage's valid length, whatever the
+ *             incoming gradient buffer holds there (NaN included): the kernels SELECT, they never multiply by zero.
+ * NULL lengths: SLU_ERR_INVALID_ARG.  Lengths are clamped into [1, frames]; the host rejects bad values before any launch.
+ *   slu_gru_seq_fwd_len_rsv  slu_gru_seq_fwd_len that also writes `reserve` (slu_gru_reserve_bytes, the layout of
+ *                            slu_gru_seq_fwd; NULL: none).  The saved h_{t-1} is the masked one: 0 for direction 1 at
+ *                            t = lengths[b] - 1.  Reserve contents at t >= lengths[b] are unspecified (NaN where gx is).
+ *   slu_gru_seq_bwd_len      slu_gru_seq_bwd with per-sequence lengths, for a reserve of slu_gru_seq_fwd_len_rsv: a step
+ *                            t >= lengths[b] contributes nothing — its d_gx / d_gh rows are stored as 0, the carried dh
+ *                            stays 0 through it, d_bias_part sums valid steps only; d_out and the reserve are not trusted
+ *                            there.  Same geometries (slu_gru_bias_tiles gives the rows of d_bias_part) and hidden sizes as
+ *                            slu_gru_seq_fwd_len; any other H: SLU_ERR_UNSUPPORTED.
+ *   slu_dropout_pool_len_fwd / _bwd   slu_dropout_pool_fwd / _bwd (float mask with strides m_st / m_sb, or Philox (seed,
+ *                            offset [+ *offset_dev]); no keep_bits, no sub-batches) with windows clipped to t < lengths[b]:
+ *                            y = 0 at to >= ceil(n / factor), the mean divides by the valid frames of its window; dx = 0
+ *                            at t >= n and dy is not read at to >= ceil(n / factor).  x (needed by _bwd for max only) and
+ *                            the mask are not read at t >= n.
+ *   slu_cls_maxpool_len_ce_fwd   slu_cls_maxpool_len_fwd with labels that also writes d_logits (B, V) = d loss / d logits
+ *                            by slu_cls_maxpool_ce_fwd's definition.  slu_cls_maxpool_ce_bwd (drop_p = 0) then gives d_h,
+ *                            d_weight, d_bias unchanged: it zero-fills d_h and scatters into argmax_t[b][v] < lengths[b].  */
+int slu_gru_seq_fwd_len_rsv(const float* gx, const float* w_hh_fwd, const float* w_hh_rev, const float* b_hh_fwd,
+                            const float* b_hh_rev, float* out, float* reserve, const int32_t* lengths, int64_t T,
+                            int64_t B, int64_t H, int64_t D, void* stream);
+int slu_gru_seq_bwd_len(const float* d_out, const float* reserve, const float* w_hh_fwd, const float* w_hh_rev,
+                        float* d_gx, float* d_gh, float* d_bias_part, const int32_t* lengths, int64_t T, int64_t B,
+                        int64_t H, int64_t D, void* stream);
+int slu_dropout_pool_len_fwd(const float* x, const int32_t* lengths, const float* mask, int64_t m_st, int64_t m_sb, float p,
+                             uint64_t seed, uint64_t offset, const uint64_t* offset_dev, int method, int64_t factor,
+                             float* y, int64_t T, int64_t B, int64_t C, void* stream);
+int slu_dropout_pool_len_bwd(const float* dy, const float* x, const int32_t* lengths, const float* mask, int64_t m_st,
+                             int64_t m_sb, float p, uint64_t seed, uint64_t offset, const uint64_t* offset_dev, int method,
+                             int64_t factor, float* dx, int64_t T, int64_t B, int64_t C, void* stream);
+int slu_cls_maxpool_len_ce_fwd(const float* h, const float* weight, const float* bias, const int32_t* lengths,
+                               const int64_t* y, const int64_t* values_per_slot, int64_t num_slots, float* logits,
+                               int32_t* argmax_t, int64_t* pred, float* d_logits, float* row_stats, float* loss_acc,
+                               int64_t T, int64_t B, int64_t C, void* stream);
 
 /* -------- Adam: torch.optim.Adam(model.parameters(), lr) (training.py:19, default betas / eps) ------
  * One launch updates up to slu_adam_max_tensors() tensors of one dtype (elem_bytes 4 / 8); the pointer
