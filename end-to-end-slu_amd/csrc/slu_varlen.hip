@@ -6,7 +6,8 @@
 // The first group is forward / inference only: no route bytes, no reserve, no dropout.  The second group (masked
 // training) adds Dropout + Downsample with windows clipped to the lengths, forward and backward, and the head's
 // cross-entropy gradient; the reserve and the BPTT are flags of the persistent kernels (slu_gru_seq_fwd_len_rsv,
-// slu_gru_seq_bwd_len).  The convolution itself and the GRU input projection
+// slu_gru_seq_bwd_len).  The third group is the masked pooling / activation pass of a TRAINABLE conv block with its route
+// bytes, and its backward (slu_pool_act_len_fwd_route, slu_pool_act_len_bwd).  The convolution itself and the GRU input projection
 // need no new kernel: on a zero tail the existing slu_wconv_fwd (pool 1, slope 1, no abs) and slu_gemm_f32 compute, at a
 // valid frame, what they compute on the truncated row; the kernels here put the zero tail back behind them.  The
 // length-aware recurrence is a flag of the persistent kernels in slu_gru.hip (slu_gru_seq_fwd_len).
@@ -389,6 +390,153 @@ dropout_pool_len_bwd4_kernel(const float* __restrict__ dy, const float* __restri
   for (int t = max(t0, t1); t < tend; ++t) *reinterpret_cast<float4*>(dx + (size_t)t * row + col) = zero;
 }
 
+// ---- [abs ->] MaxPool(ceil) over the valid frames -> LeakyReLU with route bytes, and its backward (masked training ----
+// through a trainable CNN block).  The forward is pool_act_len_fwd_kernel that also records, per output, the route byte of
+// pool_act_fwd_kernel (slu_pool.hip): arg-max offset inside the window | negative-before-abs << 7, 0 at a padded output.
+// The backward is pool_act_bwd_kernel with every window clipped to n_b: dx is exactly 0 at l >= n_b (selected, never a
+// product), dy / y are not read at lo >= ceil(n_b / pool), and the activation's derivative is that kernel's
+// (y > 0 ? 1 : slope).  x / dx channels-last (B, L, C); y / dy at b * out_sb + lo * out_sl + c.
+struct PoolActLenParams {
+  const int* lengths;
+  int B, L, C, L_out, pool, do_abs;
+  float slope;
+  long long out_sb, out_sl;
+};
+
+__device__ __forceinline__ void route_take(float v, int do_abs, int off, float& best, unsigned& r) {
+  const float u = do_abs ? fabsf(v) : v;
+  if (u > best) { best = u; r = (unsigned)off | ((do_abs && v < 0.0f) ? 0x80u : 0u); }      // first maximum wins
+}
+
+// scalar path: one thread per output element
+__global__ void __launch_bounds__(256)
+pool_act_len_fwd_route_kernel(const float* __restrict__ x, float* __restrict__ y, unsigned char* __restrict__ route,
+                              const PoolActLenParams q) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long long)q.B * q.L_out * q.C) return;
+  const int c = (int)(e % q.C);
+  const long long bl = e / q.C;
+  const int lo = (int)(bl % q.L_out), b = (int)(bl / q.L_out);
+  const int n = clamp_len(q.lengths, b, q.L);
+  const int l0 = lo * q.pool, l1 = min(n, l0 + q.pool);
+  float out = 0.0f;
+  unsigned r = 0;
+  if (l0 < n) {
+    float best = -INFINITY;
+    for (int l = l0; l < l1; ++l) route_take(x[((size_t)b * q.L + l) * q.C + c], q.do_abs, l - l0, best, r);
+    out = best > 0.0f ? best : best * q.slope;
+  }
+  y[(size_t)b * q.out_sb + (size_t)lo * q.out_sl + c] = out;
+  route[e] = (unsigned char)r;
+}
+
+// scalar path: one thread per input element
+__global__ void __launch_bounds__(256)
+pool_act_len_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y, const unsigned char* __restrict__ route,
+                        float* __restrict__ dx, const PoolActLenParams q) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long long)q.B * q.L * q.C) return;
+  const int c = (int)(e % q.C);
+  const long long bl = e / q.C;
+  const int l = (int)(bl % q.L), b = (int)(bl / q.L);
+  const int n = clamp_len(q.lengths, b, q.L);
+  float out = 0.0f;
+  if (l < n) {
+    const int lo = l / q.pool;
+    const unsigned char r = route[((size_t)b * q.L_out + lo) * q.C + c];
+    if (l - lo * q.pool == (r & 0x7f)) {
+      const size_t o = (size_t)b * q.out_sb + (size_t)lo * q.out_sl + c;
+      const float g = dy[o] * (y[o] > 0.0f ? 1.0f : q.slope);
+      out = (r & 0x80) ? -g : g;
+    }
+  }
+  dx[e] = out;
+}
+
+// vector path (C % 4 == 0, 16-byte aligned rows): four channels per thread, one thread per OUTPUT frame and quad — a wave
+// reads and writes whole 16-byte pieces of contiguous channel rows; the four route bytes travel as one word.  The
+// backward thread writes dx for every frame of its dense window [lo * pool, min(L, lo * pool + pool)), zeros included.
+__global__ void __launch_bounds__(256)
+pool_act_len_fwd_route4_kernel(const float* __restrict__ x, float* __restrict__ y, unsigned char* __restrict__ route,
+                               const PoolActLenParams q) {
+  const int C4 = q.C >> 2;
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long long)q.B * q.L_out * C4) return;
+  const int c = (int)(e % C4) * 4;
+  const long long bl = e / C4;
+  const int lo = (int)(bl % q.L_out), b = (int)(bl / q.L_out);
+  const int n = clamp_len(q.lengths, b, q.L);
+  const int l0 = lo * q.pool, l1 = min(n, l0 + q.pool);
+  float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
+  unsigned rx = 0, ry = 0, rz = 0, rw = 0;
+  if (l0 < n) {
+    float4 best = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+    for (int l = l0; l < l1; ++l) {
+      const float4 v = *reinterpret_cast<const float4*>(x + ((size_t)b * q.L + l) * q.C + c);
+      route_take(v.x, q.do_abs, l - l0, best.x, rx);
+      route_take(v.y, q.do_abs, l - l0, best.y, ry);
+      route_take(v.z, q.do_abs, l - l0, best.z, rz);
+      route_take(v.w, q.do_abs, l - l0, best.w, rw);
+    }
+    out = make_float4(best.x > 0.0f ? best.x : best.x * q.slope, best.y > 0.0f ? best.y : best.y * q.slope,
+                      best.z > 0.0f ? best.z : best.z * q.slope, best.w > 0.0f ? best.w : best.w * q.slope);
+  }
+  *reinterpret_cast<float4*>(y + (size_t)b * q.out_sb + (size_t)lo * q.out_sl + c) = out;
+  *reinterpret_cast<unsigned*>(route + (size_t)bl * q.C + c) = rx | (ry << 8) | (rz << 16) | (rw << 24);
+}
+
+__device__ __forceinline__ float route_grad(float dy, float y, unsigned r, float slope) {
+  const float g = dy * (y > 0.0f ? 1.0f : slope);
+  return (r & 0x80u) ? -g : g;
+}
+
+__global__ void __launch_bounds__(256)
+pool_act_len_bwd4_kernel(const float* __restrict__ dy, const float* __restrict__ y, const unsigned char* __restrict__ route,
+                         float* __restrict__ dx, const PoolActLenParams q) {
+  const int C4 = q.C >> 2;
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long long)q.B * q.L_out * C4) return;
+  const int c = (int)(e % C4) * 4;
+  const long long bl = e / C4;
+  const int lo = (int)(bl % q.L_out), b = (int)(bl / q.L_out);
+  const int n = clamp_len(q.lengths, b, q.L);
+  const int l0 = lo * q.pool;                                          // lo < L_out: l0 < L
+  const int lend = min(q.L, l0 + q.pool);                              // the dense window [l0, lend) is this thread's to write
+  float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+  int ax = -1, ay = -1, az = -1, aw = -1;                              // no frame of a padded window matches
+  if (l0 < n) {
+    const size_t o = (size_t)b * q.out_sb + (size_t)lo * q.out_sl + c;
+    const float4 d = *reinterpret_cast<const float4*>(dy + o);
+    const float4 yy = *reinterpret_cast<const float4*>(y + o);
+    const unsigned r = *reinterpret_cast<const unsigned*>(route + (size_t)bl * q.C + c);
+    g = make_float4(route_grad(d.x, yy.x, r, q.slope), route_grad(d.y, yy.y, r >> 8, q.slope),
+                    route_grad(d.z, yy.z, r >> 16, q.slope), route_grad(d.w, yy.w, r >> 24, q.slope));
+    ax = r & 0x7f; ay = (r >> 8) & 0x7f; az = (r >> 16) & 0x7f; aw = (r >> 24) & 0x7f;
+  }
+  for (int l = l0; l < lend; ++l) {
+    const int k = l < n ? l - l0 : -2;                                 // a frame at or beyond n_b matches nothing
+    *reinterpret_cast<float4*>(dx + ((size_t)b * q.L + l) * q.C + c) =
+        make_float4(k == ax ? g.x : 0.f, k == ay ? g.y : 0.f, k == az ? g.z : 0.f, k == aw ? g.w : 0.f);
+  }
+}
+
+static int pool_act_len_fill(PoolActLenParams& q, const char* who, const int32_t* lengths, int64_t B, int64_t L, int64_t C,
+                             int64_t pool, int do_abs, float slope, int64_t out_sb, int64_t out_sl) {
+  SLU_REQUIRE(lengths, "%s: null lengths", who);
+  SLU_REQUIRE(B > 0 && L > 0 && C > 0 && pool >= 1 && pool <= 127, "%s: bad size (pool width 1..127)", who);
+  SLU_REQUIRE(B < (1ll << 31) && L < (1ll << 31) - 128 && C < (1ll << 31) && cdiv(B * L * C, 256) < (1ll << 31),
+              "%s: tensor too large", who);
+  q.lengths = (const int*)lengths; q.B = (int)B; q.L = (int)L; q.C = (int)C; q.L_out = (int)cdiv(L, pool);
+  q.pool = (int)pool; q.do_abs = do_abs; q.slope = slope; q.out_sb = out_sb; q.out_sl = out_sl;
+  return SLU_OK;
+}
+
+// float4 path: channel count, strides and every buffer 16-byte aligned (the route words 4-byte aligned)
+static bool pool_act_len_vec_ok(const PoolActLenParams& q, const void* a, const void* b, const void* c, const void* route) {
+  if (q.C % 4 != 0 || q.out_sb % 4 != 0 || q.out_sl % 4 != 0) return false;
+  return ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) | ((uintptr_t)route & 3)) == 0;
+}
+
 static int pool_len_fill(PoolLenParams& q, const char* who, const float* mask, int64_t m_st, int64_t m_sb, float p,
                          uint64_t seed, uint64_t offset, const uint64_t* offset_dev, const int32_t* lengths, int method,
                          int64_t factor, int64_t T, int64_t B, int64_t C) {
@@ -437,6 +585,44 @@ extern "C" int slu_pool_act_len_fwd(const float* x, float* y, const int32_t* len
                      x, y, (const int*)lengths, (int)B, (int)L, (int)C, (int)L_out, (int)pool, do_abs, slope,
                      (long long)out_sb, (long long)out_sl);
   SLU_CHECK_LAUNCH("pool_act_len_fwd_kernel");
+  return SLU_OK;
+}
+
+extern "C" int slu_pool_act_len_fwd_route(const float* x, float* y, uint8_t* route, const int32_t* lengths, int64_t B,
+                                          int64_t L, int64_t C, int64_t pool, int do_abs, float slope, int64_t out_sb,
+                                          int64_t out_sl, void* stream) {
+  SLU_REQUIRE(x && y && route, "slu_pool_act_len_fwd_route: null pointer");
+  PoolActLenParams q;
+  int rc = pool_act_len_fill(q, "slu_pool_act_len_fwd_route", lengths, B, L, C, pool, do_abs, slope, out_sb, out_sl);
+  if (rc) return rc;
+  if (pool_act_len_vec_ok(q, x, y, nullptr, route)) {
+    hipLaunchKernelGGL(pool_act_len_fwd_route4_kernel, dim3((unsigned)cdiv(B * q.L_out * (C / 4), 256)), dim3(256), 0,
+                       (hipStream_t)stream, x, y, route, q);
+    SLU_CHECK_LAUNCH("pool_act_len_fwd_route4_kernel");
+    return SLU_OK;
+  }
+  hipLaunchKernelGGL(pool_act_len_fwd_route_kernel, dim3((unsigned)cdiv(B * q.L_out * C, 256)), dim3(256), 0,
+                     (hipStream_t)stream, x, y, route, q);
+  SLU_CHECK_LAUNCH("pool_act_len_fwd_route_kernel");
+  return SLU_OK;
+}
+
+extern "C" int slu_pool_act_len_bwd(const float* dy, const float* y, const uint8_t* route, const int32_t* lengths, float* dx,
+                                    int64_t B, int64_t L, int64_t C, int64_t pool, float slope, int64_t out_sb,
+                                    int64_t out_sl, void* stream) {
+  SLU_REQUIRE(dy && y && route && dx, "slu_pool_act_len_bwd: null pointer");
+  PoolActLenParams q;
+  int rc = pool_act_len_fill(q, "slu_pool_act_len_bwd", lengths, B, L, C, pool, 0, slope, out_sb, out_sl);
+  if (rc) return rc;
+  if (pool_act_len_vec_ok(q, dy, y, dx, route)) {
+    hipLaunchKernelGGL(pool_act_len_bwd4_kernel, dim3((unsigned)cdiv(B * q.L_out * (C / 4), 256)), dim3(256), 0,
+                       (hipStream_t)stream, dy, y, route, dx, q);
+    SLU_CHECK_LAUNCH("pool_act_len_bwd4_kernel");
+    return SLU_OK;
+  }
+  hipLaunchKernelGGL(pool_act_len_bwd_kernel, dim3((unsigned)cdiv(B * L * C, 256)), dim3(256), 0, (hipStream_t)stream, dy, y,
+                     route, dx, q);
+  SLU_CHECK_LAUNCH("pool_act_len_bwd_kernel");
   return SLU_OK;
 }
 

@@ -219,6 +219,16 @@ def beam_eos_enabled():
     return v == "1"
 
 
+def mask_train_cnn_enabled():
+    """SLU_MASK_TRAIN_CNN: "0" (default) — Model.forward(lengths=...) refuses a trainable CNN block; "1" — such a block
+    runs length-aware inside autograd (ops.SincBlockLenFn / ConvBlockLenFn), so masked training goes on when the unfreezing
+    reaches the convolutions, or with nothing frozen."""
+    v = os.environ.get("SLU_MASK_TRAIN_CNN", "0")
+    if v not in ("0", "1"):
+        raise ValueError("SLU_MASK_TRAIN_CNN=%r: expected 0 or 1" % (v,))
+    return v == "1"
+
+
 def _require_device(t):
     if not t.is_cuda:
         raise _lib.SluHipError("the HIP kernels are the only compute path of this package: move the "
@@ -921,7 +931,9 @@ def _run_stages_len(stages, h, lengths, training=None):
     slu_gemm_f32, slu_gru_seq_fwd_len — whatever SLU_FROZEN_MATH says: both sides of the invariant (an utterance in a
     padded batch / alone) then differ by summation order only.  A split-precision length-aware path does not exist.
     training (None: the evaluation above; else the module's training flag): the masked training step — every stage through
-    run_len_train, i.e. inside autograd where it has something to differentiate and with its dropout when `training`."""
+    run_len_train, i.e. inside autograd where it has something to differentiate and with its dropout when `training`.  The
+    table then also carries, behind the stages' rows, one row of input frames * channels for every conv block that follows
+    a stage with a trainable parameter (what ops.ConvBlockLenFn masks the gradient of its input with)."""
     rows = [list(lengths)]
     for st in stages:
         if isinstance(st, _ConvStage):
@@ -929,13 +941,25 @@ def _run_stages_len(stages, h, lengths, training=None):
             rows.append([st.out_len(n) for n in rows[-2]])
         else:
             rows.append([st.out_len(n) for n in rows[-1]])
+    n_rows, k, flat, grad_above = len(rows), 0, {}, False
+    for st in stages:
+        # a conv block behind a trainable stage masks the gradient of its input: input frames * channels (the row table of
+        # slu_mask_rows_len on the (B, L * C) view), appended to the same table behind the stages' rows
+        if training is not None and isinstance(st, _ConvStage) and grad_above:
+            flat[k] = len(rows)
+            rows.append([n * st.in_channels() for n in rows[k]])
+        grad_above = grad_above or any(q.requires_grad for q in st.parameters())
+        k += 2 if isinstance(st, _ConvStage) else 1
     table = torch.tensor(rows, dtype=torch.int32).to(h.device, non_blocking=True)
     k = 0
     for st in stages:
-        n_dev = table[k + 1] if isinstance(st, _ConvStage) else table[k]
-        h = st.run_len(h, n_dev) if training is None else st.run_len_train(h, n_dev, training)
+        if isinstance(st, _ConvStage):
+            h = (st.run_len(h, table[k + 1]) if training is None
+                 else st.run_len_train(h, table[k + 1], training, table[flat[k]] if k in flat else None))
+        else:
+            h = st.run_len(h, table[k]) if training is None else st.run_len_train(h, table[k], training)
         k += 2 if isinstance(st, _ConvStage) else 1
-    return h, rows[-1], table[k]
+    return h, rows[n_rows - 1], table[k]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -981,10 +1005,31 @@ class _ConvStage:
             raw, _, _ = _ops.wconv_fwd(h, w, bias, B, l_in, c_in, self.conv.stride, False, 1, 1.0, False, False)
             return _ops.pool_act_len_fwd(raw, n_conv, self.pool, self.do_abs, self.slope, time_major)
 
-    def run_len_train(self, h, n_conv, training):
-        """A FROZEN block inside a masked training step (Model.forward(lengths=...) refuses trainable ones): run_len, then
-        the block's nn.Dropout as run() applies it — on the channels-last tensor, the same stream and masks as without
-        lengths; a dropped padded frame is still zero."""
+    def in_channels(self):
+        return 1 if self.is_sinc else self.conv.in_channels
+
+    def run_len_train(self, h, n_conv, training, n_in_flat=None):
+        """The block inside a masked training step: run_len, then the block's nn.Dropout as run() applies it — on the
+        channels-last tensor, the same stream and masks as without lengths; a dropped padded frame is still zero.  A block
+        with a trainable parameter (SLU_MASK_TRAIN_CNN=1: Model._forward_len refuses it otherwise), or behind one (h requires
+        a gradient), runs as ops.SincBlockLenFn / ConvBlockLenFn with the dropout inside autograd; n_in_flat = the int32
+        device lengths of h times its channels (what the gradient of h is masked with).  A frozen one runs the same
+        kernels outside autograd, without route bytes."""
+        if any(q.requires_grad for q in self.parameters()) or h.requires_grad:
+            drop = self.drop > 0.0 and training
+            tm = self.time_major and not drop
+            if self.is_sinc:
+                h = _ops.SincBlockLenFn.apply(h, self.conv.filt_b1, self.conv.filt_band, n_conv, self.conv.Filt_dim,
+                                              self.conv.fs, self.conv.stride, self.pool, self.slope, tm, self.do_abs)
+            else:
+                if h.dim() == 2:
+                    h = h.unsqueeze(2)
+                h = _ops.ConvBlockLenFn.apply(h, self.conv.weight, self.conv.bias, n_conv, n_in_flat, self.conv.stride,
+                                              self.do_abs, self.pool, self.slope, tm)
+            if drop:
+                p, mask, seed, offset = _dropout_args(self.drop_name, self.site, self.drop, training, cnn=True)
+                h = _DropOnlyFn.apply(h.contiguous(), p, mask, seed, offset)
+            return h.transpose(0, 1).contiguous() if self.time_major and not tm else h
         if not (self.drop > 0.0 and training):
             return self.run_len(h, n_conv)
         h = self.run_len(h, n_conv, time_major=False)
@@ -1643,8 +1688,9 @@ class Model(torch.nn.Module):
 
     def _forward_len(self, x, y_intent, lengths, rng_step, n_prefix):
         """Model.forward with per-utterance lengths (DESIGN.md section 7 "Lengths"): the waveform tail is zeroed, every
-        stage runs length-aware in exact fp32 (frozen ones outside autograd, trainable GRU layers as ops.GRULayerLenFn),
-        the head is ops.IntentHeadLenFn.  In train() mode every dropout site draws the masks it draws without lengths
+        stage runs length-aware in exact fp32 (frozen ones outside autograd, trainable GRU layers as ops.GRULayerLenFn,
+        trainable CNN blocks — with SLU_MASK_TRAIN_CNN=1 — as ops.SincBlockLenFn / ConvBlockLenFn), the head is
+        ops.IntentHeadLenFn.  In train() mode every dropout site draws the masks it draws without lengths
         (the dense batch's Philox stream or the injected masks), so with p = 0 or injected masks the gradients equal the
         mean of the alone runs' exactly, with Philox masks in distribution.  Everything that can be refused is refused
         here, on the host, before the first launch."""
@@ -1663,11 +1709,12 @@ class Model(torch.nn.Module):
         _check_len_stages(stages)
         if self.augment and self.training:
             raise ValueError("lengths: augment=True is not supported (the augmentation moves the utterances' ends)")
-        for st in pm._cnn_stages:
-            if any(q.requires_grad for q in st.parameters()):
-                raise ValueError("lengths: a trainable CNN block (the unfreezing has reached the convolutions) has no "
-                                 "length-aware backward pass yet — that is the next step; freeze the CNN blocks or train "
-                                 "without lengths")
+        if not mask_train_cnn_enabled():
+            for st in pm._cnn_stages:
+                if any(q.requires_grad for q in st.parameters()):
+                    raise ValueError("lengths: a trainable CNN block (the unfreezing has reached the convolutions) runs "
+                                     "length-aware only with SLU_MASK_TRAIN_CNN=1 (off by default): setting it is the next step; or "
+                                     "freeze the CNN blocks, or train without lengths")
         (x,) = pm._to_device(x)
         pm._cnn_stages[-1].time_major = True
         _DropoutState.current = next_rng_step() if rng_step is None else rng_step

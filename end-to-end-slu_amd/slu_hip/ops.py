@@ -1247,6 +1247,54 @@ def pool_act_len_fwd(x, lengths, pool, do_abs, slope, time_major):
     return y
 
 
+def pool_act_len_fwd_route(x, lengths, pool, do_abs, slope, time_major):
+    """pool_act_len_fwd (the same y, bit for bit) -> (y, route (B, L_out, C) uint8: PoolActFn's route bytes, 0 at padded
+    outputs) — the forward of a conv block that pool_act_len_bwd differentiates."""
+    L = _lib.load()
+    x = _f32c(x, "x")
+    B, Lin, C = x.shape
+    _len_ok(lengths, B)
+    l_out = -(-Lin // pool)
+    if time_major:
+        y = torch.empty(l_out, B, C, dtype=torch.float32, device=x.device)
+        sb, sl = C, B * C
+    else:
+        y = torch.empty(B, l_out, C, dtype=torch.float32, device=x.device)
+        sb, sl = l_out * C, C
+    route = torch.empty(B, l_out, C, dtype=torch.uint8, device=x.device)
+    _lib.check(L.slu_pool_act_len_fwd_route(x.data_ptr(), y.data_ptr(), route.data_ptr(), lengths.data_ptr(), B, Lin, C, pool,
+                                            int(do_abs), float(slope), sb, sl, _stream()), "slu_pool_act_len_fwd_route")
+    return y, route
+
+
+def pool_act_len_bwd(dy, y, route, lengths, Lin, pool, slope, time_major):
+    """dy / y as pool_act_len_fwd_route returned y, lengths = valid frames of the pooled tensor's input -> dx (B, Lin, C):
+    exactly zero at l >= lengths[b] whatever dy and y hold beyond the valid outputs (they are not read there)."""
+    L = _lib.load()
+    B, l_out, C = route.shape
+    _len_ok(lengths, B)
+    dy = _f32c(dy, "dy")
+    assert y.dtype == torch.float32 and y.is_contiguous() and tuple(y.shape) == tuple(dy.shape) == (
+        (l_out, B, C) if time_major else (B, l_out, C)) and l_out == -(-Lin // pool), "y / dy: not pool_act_len_fwd_route's output"
+    sb, sl = (C, B * C) if time_major else (l_out * C, C)
+    dx = torch.empty(B, Lin, C, dtype=torch.float32, device=dy.device)
+    _lib.check(L.slu_pool_act_len_bwd(dy.data_ptr(), y.data_ptr(), route.data_ptr(), lengths.data_ptr(), dx.data_ptr(), B, Lin,
+                                      C, pool, float(slope), sb, sl, _stream()), "slu_pool_act_len_bwd")
+    return dx
+
+
+def mask_frames_len_(x, lengths_flat):
+    """In place: x (B, L, C) contiguous, lengths_flat[b] = valid frames of row b * C -> x[b, l] = 0 at the frames beyond
+    (slu_mask_rows_len on the (B, L * C) view)."""
+    L = _lib.load()
+    B = x.shape[0]
+    _len_ok(lengths_flat, B)
+    assert x.is_contiguous() and x.dtype == torch.float32
+    _lib.check(L.slu_mask_rows_len(x.data_ptr(), x.data_ptr(), lengths_flat.data_ptr(), B, x.numel() // B, _stream()),
+               "slu_mask_rows_len")
+    return x
+
+
 def gru_seq_fwd_len(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lengths, T, B, H, D):
     """gru_seq_fwd (no reserve) with per-sequence lengths -> out (T, B, D*H), zero at t >= lengths[b]."""
     L = _lib.load()
@@ -1579,9 +1627,51 @@ class SincBlockFn(torch.autograd.Function):
         x, b1, band, out, route = ctx.saved_tensors
         n = b1.numel()
         d_conv = wconv_bwd_act(dy, out, route, B, l_conv, n, do_abs, pool, slope, time_major)
-        dW, _ = wconv_bwd_weight(d_conv, x, B, T, 1, n, filt_dim, stride, False)
-        db1, dband = sinc_filters_bwd(b1, band, dW.view(n, filt_dim), filt_dim, fs)
+        db1, dband = _sinc_block_grads(d_conv, x, b1, band, B, T, filt_dim, fs, stride)
         return None, db1, dband, None, None, None, None, None, None, None
+
+
+def _sinc_block_grads(d_conv, x, b1, band, B, T, filt_dim, fs, stride):
+    """d_conv (B, l_conv, N_filt) at the raw convolution of the waveform x (B, T) -> (d filt_b1, d filt_band)."""
+    n = b1.numel()
+    dW, _ = wconv_bwd_weight(d_conv, x, B, T, 1, n, filt_dim, stride, False)
+    return sinc_filters_bwd(b1, band, dW.view(n, filt_dim), filt_dim, fs)
+
+
+def _conv_block_grads(needs, has_bias, d_conv, x, weight, B, l_in, c_in, stride, l_conv, exact=False):
+    """d_conv (B, l_conv, c_out) at the raw convolution of x (B, l_in, c_in) -> (dx, dW, db) as needs = (x, weight, bias)
+    asks; exact: the data gradient on the exact fp32 kernel whatever the training arithmetic (masked steps)."""
+    c_out, _, k_t = weight.shape
+    dx = dW = db = None
+    dev = x.device
+    if needs[1] or (has_bias and needs[2]):
+        dW = torch.empty(c_out, c_in, k_t, dtype=torch.float32, device=dev)
+        db = torch.empty(c_out, dtype=torch.float32, device=dev) if has_bias else None
+        with _Fork(dev, 0):                        # independent of the data gradient below
+            wconv_bwd_weight(d_conv, x, B, l_in, c_in, c_out, k_t, stride, has_bias, out=(dW, db))
+    if needs[0]:
+        if stride != 1:
+            # a strided layer that is not the first one (the reference accepts any cnn_stride, models.py:200): its data
+            # gradient is the stride-1 data gradient of d_conv with stride - 1 zeros inserted between frames — the zeros
+            # add nothing, so the result is exact; the kernel does `stride` times the necessary work, which is fine for
+            # a geometry no shipped cfg uses.  (zeros + strided copy: data movement only)
+            l_conv1 = l_in + 2 * (k_t // 2) - k_t + 1
+            d_up = torch.zeros(B, l_conv1, c_out, dtype=torch.float32, device=dev)
+            d_up[:, :(l_conv - 1) * stride + 1:stride] = d_conv
+            d_conv_dx, l_dx = d_up, l_conv1
+        else:
+            d_conv_dx, l_dx = d_conv, l_conv
+        ns = 0 if exact else train_nsplit(True)
+        if ns and k_t % 2 == 1 and wconv_bf16_supported(c_out, 1, 1, k_t, ns) and c_in <= 128:
+            # data gradient = the same windowed contraction with the filters transposed and reversed in time, on
+            # split-precision operands (the flip / transpose is a 72 KB copy).  Odd kernel sizes only: for an even k_t
+            # the "same"-padded forward convolution is one frame longer than its input and is not this transpose
+            w_t = weight.detach().transpose(0, 1).flip(2).contiguous()
+            dx = wconv_fwd_bf16(d_conv_dx, w_t, None, B, l_dx, c_out, 1, False, 1, 1.0, False, ns)
+        else:
+            dx = wconv_bwd_data(d_conv_dx, weight, B, l_in)
+    _Fork.join(dev)
+    return dx, dW, db
 
 
 class ConvBlockFn(torch.autograd.Function):
@@ -1613,36 +1703,69 @@ class ConvBlockFn(torch.autograd.Function):
         x, weight, out, route = ctx.saved_tensors
         c_out, _, k_t = weight.shape
         d_conv = wconv_bwd_act(dy, out, route, B, l_conv, c_out, do_abs, pool, slope, time_major)
-        dx = dW = db = None
-        dev = x.device
-        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            dW = torch.empty(c_out, c_in, k_t, dtype=torch.float32, device=dev)
-            db = torch.empty(c_out, dtype=torch.float32, device=dev) if ctx.has_bias else None
-            with _Fork(dev, 0):                        # independent of the data gradient below
-                wconv_bwd_weight(d_conv, x, B, l_in, c_in, c_out, k_t, stride, ctx.has_bias, out=(dW, db))
-        if ctx.needs_input_grad[0]:
-            if stride != 1:
-                # a strided layer that is not the first one (the reference accepts any cnn_stride, models.py:200): its data
-                # gradient is the stride-1 data gradient of d_conv with stride - 1 zeros inserted between frames — the zeros
-                # add nothing, so the result is exact; the kernel does `stride` times the necessary work, which is fine for
-                # a geometry no shipped cfg uses.  (zeros + strided copy: data movement only)
-                l_conv1 = l_in + 2 * (k_t // 2) - k_t + 1
-                d_up = torch.zeros(B, l_conv1, c_out, dtype=torch.float32, device=dev)
-                d_up[:, :(l_conv - 1) * stride + 1:stride] = d_conv
-                d_conv_dx, l_dx = d_up, l_conv1
-            else:
-                d_conv_dx, l_dx = d_conv, l_conv
-            ns = train_nsplit(True)
-            if ns and k_t % 2 == 1 and wconv_bf16_supported(c_out, 1, 1, k_t, ns) and c_in <= 128:
-                # data gradient = the same windowed contraction with the filters transposed and reversed in time, on
-                # split-precision operands (the flip / transpose is a 72 KB copy).  Odd kernel sizes only: for an even k_t
-                # the "same"-padded forward convolution is one frame longer than its input and is not this transpose
-                w_t = weight.detach().transpose(0, 1).flip(2).contiguous()
-                dx = wconv_fwd_bf16(d_conv_dx, w_t, None, B, l_dx, c_out, 1, False, 1, 1.0, False, ns)
-            else:
-                dx = wconv_bwd_data(d_conv_dx, weight, B, l_in)
-        _Fork.join(dev)
+        dx, dW, db = _conv_block_grads(ctx.needs_input_grad[:3], ctx.has_bias, d_conv, x, weight, B, l_in, c_in, stride, l_conv)
         return dx, dW, db, None, None, None, None, None
+
+
+class SincBlockLenFn(torch.autograd.Function):
+    """SincBlockFn with per-utterance lengths (masked training): x (B, T) with a zero tail, n_conv = int32 device lengths
+    of the raw convolution -> (B, L_out, N_filt) or time-major, zero at lo >= ceil(n_conv[b] / pool).  Always exact fp32:
+    slu_wconv_fwd (pool 1, slope 1, no abs) -> slu_pool_act_len_fwd_route; backward slu_pool_act_len_bwd (d_conv exactly
+    0 at l >= n_conv[b]) -> SincBlockFn's weight-gradient and filter-parameter calls.  The first block: no dx."""
+
+    @staticmethod
+    def forward(ctx, x, b1, band, n_conv, filt_dim, fs, stride, pool, slope, time_major, do_abs=True):
+        B, T = x.shape
+        x = _f32c(x, "x")
+        filters = sinc_filters(b1, band, filt_dim, fs)
+        raw, _, l_conv = wconv_fwd(x, filters.view(-1, 1, filt_dim), None, B, T, 1, stride, False, 1, 1.0, False, False)
+        out, route = pool_act_len_fwd_route(raw, n_conv, pool, do_abs, slope, time_major)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            ctx.cfg = (B, T, filt_dim, fs, stride, pool, slope, time_major, l_conv)
+            ctx.save_for_backward(x, b1, band, out, route, n_conv)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        B, T, filt_dim, fs, stride, pool, slope, time_major, l_conv = ctx.cfg
+        x, b1, band, out, route, n_conv = ctx.saved_tensors
+        d_conv = pool_act_len_bwd(dy, out, route, n_conv, l_conv, pool, slope, time_major)
+        db1, dband = _sinc_block_grads(d_conv, x, b1, band, B, T, filt_dim, fs, stride)
+        return None, db1, dband, None, None, None, None, None, None, None, None
+
+
+class ConvBlockLenFn(torch.autograd.Function):
+    """ConvBlockFn with per-utterance lengths (masked training): x channels-last (B, L, Cin), zero at l >= m_b; n_conv =
+    int32 device lengths of the raw convolution; n_in_flat = m_b * Cin (int32, device; None when x needs no gradient) ->
+    (B, L_out, Cout) or time-major, zero at lo >= ceil(n_conv[b] / pool).  Always exact fp32: slu_wconv_fwd (pool 1, slope
+    1, no abs) -> slu_pool_act_len_fwd_route; backward slu_pool_act_len_bwd -> ConvBlockFn's weight / bias / data-gradient
+    calls on a d_conv that is exactly 0 at l >= n_conv[b] -> dx zeroed at l >= m_b (the data gradient of valid outputs
+    reaches k / 2 frames into the tail)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, n_conv, n_in_flat, stride, do_abs, pool, slope, time_major):
+        B, l_in, c_in = x.shape
+        x = x.contiguous()
+        if ctx.needs_input_grad[0] and n_in_flat is None:
+            raise ValueError("lengths: ConvBlockLenFn needs n_in_flat to mask the gradient of its input")
+        raw, _, l_conv = wconv_fwd(x, weight, bias, B, l_in, c_in, stride, False, 1, 1.0, False, False)
+        out, route = pool_act_len_fwd_route(raw, n_conv, pool, do_abs, slope, time_major)
+        if any(ctx.needs_input_grad[:3]):
+            ctx.cfg = (B, l_in, c_in, stride, pool, slope, time_major, l_conv)
+            ctx.save_for_backward(x, weight, out, route, n_conv, n_in_flat)
+            ctx.has_bias = bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        B, l_in, c_in, stride, pool, slope, time_major, l_conv = ctx.cfg
+        x, weight, out, route, n_conv, n_in_flat = ctx.saved_tensors
+        d_conv = pool_act_len_bwd(dy, out, route, n_conv, l_conv, pool, slope, time_major)
+        dx, dW, db = _conv_block_grads(ctx.needs_input_grad[:3], ctx.has_bias, d_conv, x, weight, B, l_in, c_in, stride,
+                                       l_conv, exact=True)
+        if dx is not None:
+            mask_frames_len_(dx, n_in_flat)
+        return dx, dW, db, None, None, None, None, None, None, None
 
 
 def gemm_tn_bf16_ok(a, b):

@@ -662,6 +662,34 @@ int slu_cls_maxpool_len_ce_fwd(const float* h, const float* weight, const float*
                                int32_t* argmax_t, int64_t* pred, float* d_logits, float* row_stats, float* loss_acc,
                                int64_t T, int64_t B, int64_t C, void* stream);
 
+/* -------- masked training through a trainable CNN block — added under ABI 10 (two new entry points; nothing existing
+ * changed, so the version number stays).  Forward: the length-aware block above (slu_wconv_fwd with pool 1, slope 1, no
+ * abs on a zero-tailed input, then the masked [abs ->] max-pool(ceil) -> LeakyReLU pass).  Backward, for a block whose raw
+ * convolution has n_b valid frames for row b and whose input has m_b:
+ *   d_conv[b, l, c]   exactly 0.0f for l >= n_b (selected, never a product: NaN in dy, y or the raw convolution beyond the
+ *                     valid frames reaches nothing — they are not read there); at a valid frame the gradient of
+ *                     [abs ->] max over the clipped window [lo * pool, min(n_b, lo * pool + pool)) -> LeakyReLU(slope): the
+ *                     first maximum of the window takes dy * (y > 0 ? 1 : slope) (slu_pool_act_bwd's convention), negated
+ *                     where abs flipped the sign; every other frame of the window takes 0;
+ *   dW, db, d filt_b1 / d filt_band   slu_wconv_bwd_weight (+ slu_sinc_filters_bwd) on this d_conv and the saved
+ *                     zero-tailed input: the sum over the rows of what each row truncated to m_b gives alone (the zero tail
+ *                     is the truncated row's "same" padding);
+ *   dx                slu_wconv_bwd_data on this d_conv, then exactly 0.0f at frames >= m_b (the data gradient of valid
+ *                     outputs reaches k / 2 frames into the tail): slu_mask_rows_len in place on the (B, L * C) view with
+ *                     lengths m_b * C.
+ * x / dx channels-last (B, L, C), lengths (B) = n_b (clamped into [1, L]); y / dy at b * out_sb + lo * out_sl + c
+ * (channels-last or time-major); route (B, ceil(L / pool), C) bytes in slu_pool_act_fwd's format.  One thread per element,
+ * or per four channels where C % 4 == 0 and the buffers are 16-byte aligned.  NULL lengths or pointers, pool outside
+ * [1, 127]: SLU_ERR_INVALID_ARG.
+ *   slu_pool_act_len_fwd_route   slu_pool_act_len_fwd (y bit-equal) that also writes the route bytes: arg-max offset
+ *                            inside the window | negative-before-abs << 7; 0 at lo >= ceil(n_b / pool).
+ *   slu_pool_act_len_bwd     dx (B, L, C), every element written, by the definition of d_conv above.                    */
+int slu_pool_act_len_fwd_route(const float* x, float* y, uint8_t* route, const int32_t* lengths, int64_t B, int64_t L,
+                               int64_t C, int64_t pool, int do_abs, float slope, int64_t out_sb, int64_t out_sl,
+                               void* stream);
+int slu_pool_act_len_bwd(const float* dy, const float* y, const uint8_t* route, const int32_t* lengths, float* dx, int64_t B,
+                         int64_t L, int64_t C, int64_t pool, float slope, int64_t out_sb, int64_t out_sl, void* stream);
+
 /* -------- Adam: torch.optim.Adam(model.parameters(), lr) (training.py:19, default betas / eps) ------
  * One launch updates up to slu_adam_max_tensors() tensors of one dtype (elem_bytes 4 / 8); the pointer
  * arrays are HOST arrays of device pointers (they travel in the kernel arguments: hipGraph-safe).
