@@ -98,24 +98,42 @@ gru_cell_bwd_kernel(const CellBwdArgs a) {
 // Attention (models.py:427-438): scores_t = <keys[b,t], query[b]> / sqrt(key_dim); a = softmax_t(scores);
 // context[b] = sum_t a_t values[b,t].  keys / values are addressed as ptr + t * s_t + b * s_b (+ k): time-major or
 // batch-major alike.  One workgroup of 256 threads per utterance.
+//
+// LEN (slu_attention_len_fwd / _bwd; the rule is in include/slu_hip.h): row b attends over its first n_b = clamp(n[b], 0, T)
+// frames only.  n_b is block-uniform and bounds EVERY loop over frames, so keys / values at t >= n_b are never read, the
+// padding costs nothing, and — the loops, the strides of the per-thread partials and the reduction trees being the ones
+// of the dense instantiation — row b's numbers are bit-equal to the dense kernel on the one-row problem with T = n_b.  The
+// LDS layout keeps T (the host does not know n_b).
 // ------------------------------------------------------------------------------------------------------------
 struct AttArgs {
   const float* keys; const float* values; long long s_t, s_b, v_t, v_b;
   const float* query; long long ld_q;         // (B, Kd)
   float* ctx; long long ld_ctx;               // (B, Vd)
   float* weights;                             // (B, T) contiguous (saved for backward)
+  const int32_t* n;                           // LEN: (B) valid frames per row; unused otherwise
   float inv_scale;
   int B, T, Kd, Vd;
 };
 
+__device__ __forceinline__ int att_frames(const int32_t* n, int b, int T) { return min(max(n[b], 0), T); }
+
+template <bool LEN>
 __global__ void __launch_bounds__(256)
 attention_fwd_kernel(const AttArgs a) {
   extern __shared__ float lds[];              // q[Kd] | s[T] | red[4]
   float* q = lds; float* s = lds + a.Kd; float* red = s + a.T;
   const int b = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  const int T = LEN ? att_frames(a.n, b, a.T) : a.T;          // the frames this row attends over
+  if (LEN) {
+    for (int t = T + tid; t < a.T; t += 256) a.weights[(size_t)b * a.T + t] = 0.0f;      // the saved plane is whole
+    if (T == 0) {                             // nothing to attend over: zero context, no 1 / 0
+      for (int v = tid; v < a.Vd; v += 256) a.ctx[(size_t)b * a.ld_ctx + v] = 0.0f;
+      return;
+    }
+  }
   for (int k = tid; k < a.Kd; k += 256) q[k] = a.query[(size_t)b * a.ld_q + k];
   __syncthreads();
-  for (int t = w; t < a.T; t += 4) {          // one wave per frame: dot product over the key dimension
+  for (int t = w; t < T; t += 4) {            // one wave per frame: dot product over the key dimension
     const float* kp = a.keys + (size_t)t * a.s_t + (size_t)b * a.s_b;
     float acc = 0.0f;
     for (int k = lane; k < a.Kd; k += 64) acc = fmaf(kp[k], q[k], acc);
@@ -124,18 +142,18 @@ attention_fwd_kernel(const AttArgs a) {
   }
   __syncthreads();
   float m = -INFINITY;
-  for (int t = tid; t < a.T; t += 256) m = fmaxf(m, s[t]);
+  for (int t = tid; t < T; t += 256) m = fmaxf(m, s[t]);
   m = block_max(m, red);
   float z = 0.0f;
-  for (int t = tid; t < a.T; t += 256) { const float ex = expf(s[t] - m); s[t] = ex; z += ex; }
+  for (int t = tid; t < T; t += 256) { const float ex = expf(s[t] - m); s[t] = ex; z += ex; }
   z = block_sum(z, red);
   const float inv = 1.0f / z;
   __syncthreads();
-  for (int t = tid; t < a.T; t += 256) { const float p = s[t] * inv; s[t] = p; a.weights[(size_t)b * a.T + t] = p; }
+  for (int t = tid; t < T; t += 256) { const float p = s[t] * inv; s[t] = p; a.weights[(size_t)b * a.T + t] = p; }
   __syncthreads();
   for (int v = tid; v < a.Vd; v += 256) {
     float acc = 0.0f;
-    for (int t = 0; t < a.T; ++t) acc = fmaf(s[t], a.values[(size_t)t * a.v_t + (size_t)b * a.v_b + v], acc);
+    for (int t = 0; t < T; ++t) acc = fmaf(s[t], a.values[(size_t)t * a.v_t + (size_t)b * a.v_b + v], acc);
     a.ctx[(size_t)b * a.ld_ctx + v] = acc;
   }
 }
@@ -147,20 +165,27 @@ struct AttBwdArgs {
   const float* weights;                       // (B, T)
   float* d_keys; float* d_values;             // same addressing as keys / values; ACCUMULATED into (+=)
   float* d_query; long long ld_dq;            // (B, Kd), overwritten
+  const int32_t* n;                           // LEN: (B) valid frames per row; unused otherwise
   float inv_scale;
   int B, T, Kd, Vd;
 };
 
+template <bool LEN>
 __global__ void __launch_bounds__(256)
 attention_bwd_kernel(const AttBwdArgs a) {
   extern __shared__ float lds[];              // q[Kd] | dc[Vd] | w[T] | ds[T] | red[4]
   float* q = lds; float* dc = q + a.Kd; float* wt = dc + a.Vd; float* ds = wt + a.T; float* red = ds + a.T;
   const int b = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  const int T = LEN ? att_frames(a.n, b, a.T) : a.T;          // d_keys / d_values at t >= T are not touched
+  if (LEN && T == 0) {
+    for (int k = tid; k < a.Kd; k += 256) a.d_query[(size_t)b * a.ld_dq + k] = 0.0f;
+    return;
+  }
   for (int k = tid; k < a.Kd; k += 256) q[k] = a.query[(size_t)b * a.ld_q + k];
   for (int v = tid; v < a.Vd; v += 256) dc[v] = a.d_ctx[(size_t)b * a.ld_dctx + v];
-  for (int t = tid; t < a.T; t += 256) wt[t] = a.weights[(size_t)b * a.T + t];
+  for (int t = tid; t < T; t += 256) wt[t] = a.weights[(size_t)b * a.T + t];
   __syncthreads();
-  for (int t = w; t < a.T; t += 4) {          // d a_t = <values[b,t], d_ctx>; d_values[b,t] += a_t d_ctx
+  for (int t = w; t < T; t += 4) {          // d a_t = <values[b,t], d_ctx>; d_values[b,t] += a_t d_ctx
     const size_t o = (size_t)t * a.v_t + (size_t)b * a.v_b;
     const float at = wt[t];
     float acc = 0.0f;
@@ -173,15 +198,15 @@ attention_bwd_kernel(const AttBwdArgs a) {
   }
   __syncthreads();
   float dot = 0.0f;
-  for (int t = tid; t < a.T; t += 256) dot += wt[t] * ds[t];
+  for (int t = tid; t < T; t += 256) dot += wt[t] * ds[t];
   dot = block_sum(dot, red);
   __syncthreads();
-  for (int t = tid; t < a.T; t += 256) ds[t] = wt[t] * (ds[t] - dot) * a.inv_scale;     // d score_t
+  for (int t = tid; t < T; t += 256) ds[t] = wt[t] * (ds[t] - dot) * a.inv_scale;     // d score_t
   __syncthreads();
   for (int k = tid; k < a.Kd; k += 256) {
     float acc = 0.0f;
     const float qk = q[k];
-    for (int t = 0; t < a.T; ++t) {
+    for (int t = 0; t < T; ++t) {
       const size_t o = (size_t)t * a.s_t + (size_t)b * a.s_b + k;
       acc = fmaf(ds[t], a.keys[o], acc);
       a.d_keys[o] += ds[t] * qk;
@@ -289,20 +314,57 @@ extern "C" int slu_gru_cell_bwd(const float* d_h, int64_t ld_dh, const float* d_
   return SLU_OK;
 }
 
+// n == nullptr: the dense kernel; else the length-aware one (same arguments, same LDS bound)
+static int attention_fwd(const char* who, const float* keys, int64_t k_st, int64_t k_sb, const float* values, int64_t v_st,
+                         int64_t v_sb, const float* query, int64_t ld_q, float* ctx, int64_t ld_ctx, float* weights,
+                         const int32_t* n, float inv_scale, int64_t B, int64_t T, int64_t Kd, int64_t Vd, void* stream) {
+  SLU_REQUIRE(keys && values && query && ctx && weights, "%s: null pointer", who);
+  SLU_REQUIRE(B > 0 && T > 0 && Kd > 0 && Vd > 0, "%s: non-positive size", who);
+  const size_t lds = (size_t)(Kd + T + 4) * sizeof(float);
+  if (lds > 64 * 1024) SLU_FAIL(SLU_ERR_UNSUPPORTED, "%s: key_dim + T too large (%zu bytes of LDS)", who, lds);
+  AttArgs a;
+  a.keys = keys; a.values = values; a.s_t = k_st; a.s_b = k_sb; a.v_t = v_st; a.v_b = v_sb; a.query = query; a.ld_q = ld_q;
+  a.ctx = ctx; a.ld_ctx = ld_ctx; a.weights = weights; a.n = n; a.inv_scale = inv_scale;
+  a.B = (int)B; a.T = (int)T; a.Kd = (int)Kd; a.Vd = (int)Vd;
+  if (n) hipLaunchKernelGGL(attention_fwd_kernel<true>, dim3((unsigned)B), dim3(256), lds, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(attention_fwd_kernel<false>, dim3((unsigned)B), dim3(256), lds, (hipStream_t)stream, a);
+  SLU_CHECK_LAUNCH("attention_fwd_kernel");
+  return SLU_OK;
+}
+
 extern "C" int slu_attention_fwd(const float* keys, int64_t k_st, int64_t k_sb, const float* values, int64_t v_st,
                                  int64_t v_sb, const float* query, int64_t ld_q, float* ctx, int64_t ld_ctx,
                                  float* weights, float inv_scale, int64_t B, int64_t T, int64_t Kd, int64_t Vd,
                                  void* stream) {
-  SLU_REQUIRE(keys && values && query && ctx && weights, "slu_attention_fwd: null pointer");
-  SLU_REQUIRE(B > 0 && T > 0 && Kd > 0 && Vd > 0, "slu_attention_fwd: non-positive size");
-  const size_t lds = (size_t)(Kd + T + 4) * sizeof(float);
-  if (lds > 64 * 1024) SLU_FAIL(SLU_ERR_UNSUPPORTED, "slu_attention_fwd: key_dim + T too large (%zu bytes of LDS)", lds);
-  AttArgs a;
+  return attention_fwd("slu_attention_fwd", keys, k_st, k_sb, values, v_st, v_sb, query, ld_q, ctx, ld_ctx, weights, nullptr,
+                       inv_scale, B, T, Kd, Vd, stream);
+}
+
+extern "C" int slu_attention_len_fwd(const float* keys, int64_t k_st, int64_t k_sb, const float* values, int64_t v_st,
+                                     int64_t v_sb, const float* query, int64_t ld_q, float* ctx, int64_t ld_ctx,
+                                     float* weights, const int32_t* n, float inv_scale, int64_t B, int64_t T, int64_t Kd,
+                                     int64_t Vd, void* stream) {
+  SLU_REQUIRE(n, "slu_attention_len_fwd: null lengths");
+  return attention_fwd("slu_attention_len_fwd", keys, k_st, k_sb, values, v_st, v_sb, query, ld_q, ctx, ld_ctx, weights, n,
+                       inv_scale, B, T, Kd, Vd, stream);
+}
+
+static int attention_bwd(const char* who, const float* keys, int64_t k_st, int64_t k_sb, const float* values, int64_t v_st,
+                         int64_t v_sb, const float* query, int64_t ld_q, const float* d_ctx, int64_t ld_dctx,
+                         const float* weights, float* d_keys, float* d_values, float* d_query, int64_t ld_dq,
+                         const int32_t* n, float inv_scale, int64_t B, int64_t T, int64_t Kd, int64_t Vd, void* stream) {
+  SLU_REQUIRE(keys && values && query && d_ctx && weights && d_keys && d_values && d_query, "%s: null pointer", who);
+  SLU_REQUIRE(B > 0 && T > 0 && Kd > 0 && Vd > 0, "%s: non-positive size", who);
+  const size_t lds = (size_t)(Kd + Vd + 2 * T + 4) * sizeof(float);
+  if (lds > 64 * 1024) SLU_FAIL(SLU_ERR_UNSUPPORTED, "%s: key_dim + value_dim + 2 T too large (%zu bytes of LDS)", who, lds);
+  AttBwdArgs a;
   a.keys = keys; a.values = values; a.s_t = k_st; a.s_b = k_sb; a.v_t = v_st; a.v_b = v_sb; a.query = query; a.ld_q = ld_q;
-  a.ctx = ctx; a.ld_ctx = ld_ctx; a.weights = weights; a.inv_scale = inv_scale;
+  a.d_ctx = d_ctx; a.ld_dctx = ld_dctx; a.weights = weights; a.d_keys = d_keys; a.d_values = d_values;
+  a.d_query = d_query; a.ld_dq = ld_dq; a.n = n; a.inv_scale = inv_scale;
   a.B = (int)B; a.T = (int)T; a.Kd = (int)Kd; a.Vd = (int)Vd;
-  hipLaunchKernelGGL(attention_fwd_kernel, dim3((unsigned)B), dim3(256), lds, (hipStream_t)stream, a);
-  SLU_CHECK_LAUNCH("attention_fwd_kernel");
+  if (n) hipLaunchKernelGGL(attention_bwd_kernel<true>, dim3((unsigned)B), dim3(256), lds, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(attention_bwd_kernel<false>, dim3((unsigned)B), dim3(256), lds, (hipStream_t)stream, a);
+  SLU_CHECK_LAUNCH("attention_bwd_kernel");
   return SLU_OK;
 }
 
@@ -310,18 +372,18 @@ extern "C" int slu_attention_bwd(const float* keys, int64_t k_st, int64_t k_sb, 
                                  int64_t v_sb, const float* query, int64_t ld_q, const float* d_ctx, int64_t ld_dctx,
                                  const float* weights, float* d_keys, float* d_values, float* d_query, int64_t ld_dq,
                                  float inv_scale, int64_t B, int64_t T, int64_t Kd, int64_t Vd, void* stream) {
-  SLU_REQUIRE(keys && values && query && d_ctx && weights && d_keys && d_values && d_query, "slu_attention_bwd: null pointer");
-  SLU_REQUIRE(B > 0 && T > 0 && Kd > 0 && Vd > 0, "slu_attention_bwd: non-positive size");
-  const size_t lds = (size_t)(Kd + Vd + 2 * T + 4) * sizeof(float);
-  if (lds > 64 * 1024) SLU_FAIL(SLU_ERR_UNSUPPORTED, "slu_attention_bwd: key_dim + value_dim + 2 T too large (%zu bytes of LDS)", lds);
-  AttBwdArgs a;
-  a.keys = keys; a.values = values; a.s_t = k_st; a.s_b = k_sb; a.v_t = v_st; a.v_b = v_sb; a.query = query; a.ld_q = ld_q;
-  a.d_ctx = d_ctx; a.ld_dctx = ld_dctx; a.weights = weights; a.d_keys = d_keys; a.d_values = d_values;
-  a.d_query = d_query; a.ld_dq = ld_dq; a.inv_scale = inv_scale;
-  a.B = (int)B; a.T = (int)T; a.Kd = (int)Kd; a.Vd = (int)Vd;
-  hipLaunchKernelGGL(attention_bwd_kernel, dim3((unsigned)B), dim3(256), lds, (hipStream_t)stream, a);
-  SLU_CHECK_LAUNCH("attention_bwd_kernel");
-  return SLU_OK;
+  return attention_bwd("slu_attention_bwd", keys, k_st, k_sb, values, v_st, v_sb, query, ld_q, d_ctx, ld_dctx, weights,
+                       d_keys, d_values, d_query, ld_dq, nullptr, inv_scale, B, T, Kd, Vd, stream);
+}
+
+extern "C" int slu_attention_len_bwd(const float* keys, int64_t k_st, int64_t k_sb, const float* values, int64_t v_st,
+                                     int64_t v_sb, const float* query, int64_t ld_q, const float* d_ctx, int64_t ld_dctx,
+                                     const float* weights, float* d_keys, float* d_values, float* d_query, int64_t ld_dq,
+                                     const int32_t* n, float inv_scale, int64_t B, int64_t T, int64_t Kd, int64_t Vd,
+                                     void* stream) {
+  SLU_REQUIRE(n, "slu_attention_len_bwd: null lengths");
+  return attention_bwd("slu_attention_len_bwd", keys, k_st, k_sb, values, v_st, v_sb, query, ld_q, d_ctx, ld_dctx, weights,
+                       d_keys, d_values, d_query, ld_dq, n, inv_scale, B, T, Kd, Vd, stream);
 }
 
 extern "C" int slu_logsoftmax_dot_fwd(const float* logits, const float* y, int64_t ld_y, float* logp_acc, float* lse,

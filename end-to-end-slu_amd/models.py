@@ -229,6 +229,24 @@ def mask_train_cnn_enabled():
     return v == "1"
 
 
+def mask_seq2seq_enabled():
+    """SLU_MASK_SEQ2SEQ: "0" (default) — every lengths=... call refuses a seq2seq model; "1" — the intent encoder runs
+    length-aware and the decoder's attention ranges over every utterance's own frames (ops.attention_len_fwd / _bwd):
+    Model.forward(lengths=...), eval_group, predict_intents, decode_intents and decode_nbest take lengths for seq2seq models."""
+    v = os.environ.get("SLU_MASK_SEQ2SEQ", "0")
+    if v not in ("0", "1"):
+        raise ValueError("SLU_MASK_SEQ2SEQ=%r: expected 0 or 1" % (v,))
+    return v == "1"
+
+
+def _refuse_seq2seq_lengths():
+    """The refusal of a seq2seq model in a lengths=... call unless SLU_MASK_SEQ2SEQ=1 (a bad value of the knob is an error)."""
+    if not mask_seq2seq_enabled():
+        raise ValueError("lengths: seq2seq models run length-aware only with SLU_MASK_SEQ2SEQ=1 (off by default): setting it "
+                         "is the next step (the decoder's attention then masks the encoder frames as well); or call without "
+                         "lengths")
+
+
 def _require_device(t):
     if not t.is_cuda:
         raise _lib.SluHipError("the HIP kernels are the only compute path of this package: move the "
@@ -516,19 +534,26 @@ class Attention(torch.nn.Module):
         self.value_linear = torch.nn.Linear(encoder_dim, value_dim)
         self.softmax = torch.nn.Softmax(dim=1)
 
-    def forward(self, encoder_states, decoder_state):
+    def forward(self, encoder_states, decoder_state, lengths=None):
         """encoder_states (B, T, encoder_dim), decoder_state (B, decoder_dim) -> (B, value_dim); inference helper
-        (no gradient path: training goes through Seq2SeqDecoder.forward's fused Function)."""
+        (no gradient path: training goes through Seq2SeqDecoder.forward's fused Function).
+        lengths (not in the reference; None: the call above): B encoder frame counts in [1, T] -> row b attends over its
+        first lengths[b] frames; the states beyond are never read."""
+        B, T, C = encoder_states.shape
+        n = None if lengths is None else _host_lengths(lengths, B, T, "encoder frames")
         _require_device(encoder_states)
         with torch.no_grad():
-            B, T, C = encoder_states.shape
             enc = encoder_states.transpose(0, 1).contiguous().view(T * B, C)
             keys = _ops.gemm(enc, self.key_linear.weight.t(), self.key_linear.bias).view(T, B, -1)
             values = _ops.gemm(enc, self.value_linear.weight.t(), self.value_linear.bias).view(T, B, -1)
             q = _ops.gemm(decoder_state.contiguous(), self.query_linear.weight.t(), self.query_linear.bias)
             ctx = torch.empty(B, values.shape[2], dtype=torch.float32, device=enc.device)
             w = torch.empty(B, T, dtype=torch.float32, device=enc.device)
-            _ops.attention_fwd(keys, values, q, ctx, w, 1.0 / float(self.scale_factor))
+            if n is None:
+                _ops.attention_fwd(keys, values, q, ctx, w, 1.0 / float(self.scale_factor))
+            else:
+                _ops.attention_len_fwd(keys, values, q, ctx, w, 1.0 / float(self.scale_factor),
+                                       torch.tensor(n, dtype=torch.int32).to(enc.device))
         return ctx
 
 
@@ -626,9 +651,10 @@ class Seq2SeqDecoder(torch.nn.Module):
                   ("linear.bias", self.linear.bias)]
         return tuple(n for n, _ in items), [t for _, t in items]
 
-    def teacher_forced(self, enc_tm, y):
+    def teacher_forced(self, enc_tm, y, n_dev=None):
         """enc_tm time-major (T, B, 2 * encoder_dim), y (B, U, num_labels) -> (loss_acc (2) = [-mean log p, 0],
-        log_p (B)) on the current dropout step (models._DropoutState)."""
+        log_p (B)) on the current dropout step (models._DropoutState).  n_dev (None: dense): int32 device tensor of B
+        encoder frame counts, already validated -> the attention of row b ranges over its first n_dev[b] frames."""
         p = self.rnn.dropout if self.training else 0.0
         masks, seed, offset, offset_dev = None, 0, 0, None
         if p > 0.0:
@@ -641,17 +667,27 @@ class Seq2SeqDecoder(torch.nn.Module):
                 else:
                     offset = _DropoutState.current * 16 + _DECODER_SITE
         names, tensors = self._params()
-        return _ops.Seq2SeqDecoderFn.apply(enc_tm, y, (names, self.SOS, p, masks, seed, offset, offset_dev), *tensors)
+        meta = (names, self.SOS, p, masks, seed, offset, offset_dev)
+        if n_dev is not None:
+            meta += (n_dev,)
+        return _ops.Seq2SeqDecoderFn.apply(enc_tm, y, meta, *tensors)
 
-    def forward(self, encoder_outputs, y, y_lengths=None):
+    def forward(self, encoder_outputs, y, y_lengths=None, enc_lengths=None):
         """encoder_outputs (B, T, 2 * encoder_dim), y (B, U, num_labels) one-hot, padded with <eos> -> log p(y|x) (B)
-        (reference models.py:519-557; y_lengths is unused there too)."""
+        (reference models.py:519-557; y_lengths is unused there too).
+        enc_lengths (not in the reference; None: the call above): B encoder frame counts in [1, T] -> row b's log p is
+        that of encoder_outputs[b:b+1, :enc_lengths[b]] alone; the frames beyond are never read."""
+        n = None
+        if enc_lengths is not None:
+            n = _host_lengths(enc_lengths, encoder_outputs.shape[0], encoder_outputs.shape[1], "encoder frames")
         _require_device(encoder_outputs)
+        if n is not None:
+            n = torch.tensor(n, dtype=torch.int32).to(encoder_outputs.device, non_blocking=True)
         _DropoutState.current = next_rng_step()
-        _, log_p = self.teacher_forced(encoder_outputs.transpose(0, 1), y)
+        _, log_p = self.teacher_forced(encoder_outputs.transpose(0, 1), y, n)
         return log_p
 
-    def infer(self, encoder_outputs, Sy, B=4, debug=False, y_lengths=None, eos=None, want_lengths=False):
+    def infer(self, encoder_outputs, Sy, B=4, debug=False, y_lengths=None, eos=None, want_lengths=False, enc_lengths=None):
         """Beam search of width B for argmax_y log p(y|x) (reference models.py:559-651; B = 1 is greedy search).
         -> (beam_scores (B, batch), beam (B, batch, U, |Sy|) one-hot), U = 200 or max(y_lengths).
         All B hypotheses of all utterances advance in ONE batched decoder step on the HIP kernels (rows w * batch +
@@ -673,7 +709,14 @@ class Seq2SeqDecoder(torch.nn.Module):
         with the hypotheses: the source's length if it was finished, else u + 1 (the <eos> counts; U if it never came).
         An utterance whose W survivors are all finished is done — further steps would select the same W, in the same
         order; the loop ends when every utterance is, and the remaining steps are filled with eos.
-        -> (beam_scores, beam[, lengths when want_lengths])."""
+        -> (beam_scores, beam[, lengths when want_lengths]).
+
+        enc_lengths (None: the search above): batch encoder frame counts in [1, T] -> every hypothesis of utterance b
+        attends over its first enc_lengths[b] frames (ops.attention_len_fwd, the counts replicated per hypothesis):
+        utterance b's hypotheses and scores are those of encoder_outputs[b:b+1, :enc_lengths[b]] searched alone."""
+        n_host = None
+        if enc_lengths is not None:
+            n_host = _host_lengths(enc_lengths, encoder_outputs.shape[0], encoder_outputs.shape[1], "encoder frames")
         _require_device(encoder_outputs)
         if want_lengths and eos is None:
             raise ValueError("want_lengths needs eos: without it every hypothesis has U labels")
@@ -697,6 +740,8 @@ class Seq2SeqDecoder(torch.nn.Module):
             keys = _ops.gemm(enc2, P["key.weight"].t(), P["key.bias"]).view(T, 1, bsz, Kd).expand(T, W, bsz, Kd).reshape(T, W * bsz, Kd)
             values = _ops.gemm(enc2, P["value.weight"].t(), P["value.bias"]).view(T, 1, bsz, Vd).expand(T, W, bsz, Vd).reshape(T, W * bsz, Vd)
             R = W * bsz
+            # row w * bsz + b of the step batch carries utterance b's count
+            n_rows = None if n_host is None else torch.tensor(n_host * W, dtype=torch.int32).to(dev, non_blocking=True)
             state, state_next = f(R, Lc, Dd), f(R, Lc, Dd)
             _ops.broadcast_rows(P["initial_state"].contiguous().view(-1), state.view(R, Lc * Dd))
             y_prev = torch.zeros(R, V, dtype=torch.float32, device=dev)
@@ -710,7 +755,7 @@ class Seq2SeqDecoder(torch.nn.Module):
             lengths = torch.zeros(W, bsz, dtype=torch.int32, device=dev)
             for u in range(U):
                 _ops.decoder_step(P, keys, values, state, state_next, y_prev, q, inp0, att_w, gi, gh, None, drop, logits, u,
-                                  (0.0, None, 0, 0, None, R * Dd))
+                                  (0.0, None, 0, 0, None, R * Dd), n_rows)
                 _ops.logsoftmax_dot_fwd(logits, zeros_y, sink, lse)                     # lse only (y = 0)
                 top_s, top_i = logits.topk(W, dim=1)                                    # log_softmax keeps the order
                 cand = (top_s - lse.unsqueeze(1)).view(W, bsz, W) + scores.unsqueeze(2)  # [src hypothesis, b, extension]
@@ -753,22 +798,23 @@ class Seq2SeqDecoder(torch.nn.Module):
     SEARCH_CHUNK = 8
     SEARCH_PLANS = 4            # captured shapes kept (ragged evaluation batches differ in T), least recently used out
 
-    def _search_plan(self, P, dev, bsz, T, W, U, V, eos=None):
-        """Static buffers (+ the captured chunk of SEARCH_CHUNK steps) of one search shape and eos label."""
+    def _search_plan(self, P, dev, bsz, T, W, U, V, eos=None, with_lengths=False):
+        """Static buffers (+ the captured chunk of SEARCH_CHUNK steps) of one search shape, eos label and attention kind
+        (with_lengths: the chunk's attention reads the plan's own (W * bsz) int32 frame counts)."""
         from slu_hip import pipeline as _pipeline
         use_graph = _pipeline.graphs_enabled()
-        key = (bsz, T, W, U, V, eos, str(dev), use_graph, tuple((n, t.data_ptr(), tuple(t.shape)) for n, t in P.items()
+        key = (bsz, T, W, U, V, eos, bool(with_lengths), str(dev), use_graph, tuple((n, t.data_ptr(), tuple(t.shape)) for n, t in P.items()
                                                           if torch.is_tensor(t)))
         plans = self.__dict__.setdefault("_search_plans", {})
         plan = plans.pop(key, None)
         if plan is None:
-            plan = self._build_search_plan(P, dev, bsz, T, W, U, V, use_graph, eos)
+            plan = self._build_search_plan(P, dev, bsz, T, W, U, V, use_graph, eos, with_lengths)
             while len(plans) >= self.SEARCH_PLANS:
                 plans.pop(next(iter(plans)))
         plans[key] = plan                                   # most recently used last
         return plan
 
-    def _build_search_plan(self, P, dev, bsz, T, W, U, V, use_graph, eos=None):
+    def _build_search_plan(self, P, dev, bsz, T, W, U, V, use_graph, eos=None, with_lengths=False):
         from slu_hip import pipeline as _pipeline
         Kd, Vd = P["key.weight"].shape[0], P["value.weight"].shape[0]
         Lc, Dd = P["initial_state"].shape
@@ -783,6 +829,8 @@ class Seq2SeqDecoder(torch.nn.Module):
              # count of finished utterances (1 int32) share one buffer: ONE fill re-arms a search
              "ctl": i32(bsz + 2 * R + 1), "backptr": i32(U, W, bsz), "labels": i32(U, W, bsz), "graph": None}
         b["ctl"].zero_()
+        # the rows' encoder frame counts: a static buffer the (captured) chunk reads, filled by one copy per search
+        b["n_rows"] = torch.full((R,), T, dtype=torch.int32, device=dev) if with_lengths else None
         b["step"], b["scores"] = b["ctl"][:bsz], b["ctl"][bsz:bsz + R].view(torch.float32).view(W, bsz)
         b["lengths"], b["n_done"] = b["ctl"][bsz + R:bsz + 2 * R].view(W, bsz), b["ctl"][bsz + 2 * R:]
         if eos is not None:
@@ -796,7 +844,7 @@ class Seq2SeqDecoder(torch.nn.Module):
                 # y_prev=None: slu_beam_select has written the embedding half of inp0 (the bias before the first step)
                 _ops.decoder_step(P, b["keys"], b["values"], b["state"], b["state_next"], None, b["q"], b["inp0"],
                                   b["att_w"], b["gi"], b["gh"], None, b["drop"], b["logits"], 0,
-                                  (0.0, None, 0, 0, None, R * Dd))
+                                  (0.0, None, 0, 0, None, R * Dd), b["n_rows"])
                 _ops.beam_select(b["logits"], b["scores"], b["state_next"], b["state"], b["step"], b["backptr"],
                                  b["labels"], None, embed, **fin)
         b["chunk"] = chunk
@@ -816,7 +864,8 @@ class Seq2SeqDecoder(torch.nn.Module):
             b["graph"] = graph
         return b
 
-    def search(self, encoder_outputs, Sy, B=4, y_lengths=None, want_beam=False, eos=None, want_lengths=False):
+    def search(self, encoder_outputs, Sy, B=4, y_lengths=None, want_beam=False, eos=None, want_lengths=False,
+               enc_lengths=None):
         """infer's beam search with the books kept on the device -> (scores (B, batch) float32, labels (B, batch, U) int64)
         [, beam (B, batch, U, |Sy|) one-hot float32 when want_beam], U = 200 or max(y_lengths): the hypotheses, bit-equal
         scores and tie rule of infer (tests/test_hip_beam.py).  Per step: ops.decoder_step (its embedding GEMM left out:
@@ -832,7 +881,14 @@ class Seq2SeqDecoder(torch.nn.Module):
         (a done utterance's slu_beam_select_eos returns at once; the decoder steps touch scratch).  labels / beam keep
         their (..., U[, V]) shapes, filled with eos.  -> (scores, labels[, beam][, lengths (B, batch) int32 when
         want_lengths]).  self.last_search_steps = the decoder steps this call launched (without eos: SEARCH_CHUNK *
-        ceil(U / SEARCH_CHUNK))."""
+        ceil(U / SEARCH_CHUNK)).
+
+        enc_lengths: as infer's, bit-equal to it.  A search with lengths has a plan of its own (the chunk's attention is
+        ops.attention_len_fwd on the plan's static (W * batch) int32 buffer, which one copy per call fills); the chunk stays
+        one linear chain."""
+        n_host = None
+        if enc_lengths is not None:
+            n_host = _host_lengths(enc_lengths, encoder_outputs.shape[0], encoder_outputs.shape[1], "encoder frames")
         _require_device(encoder_outputs)
         if want_lengths and eos is None:
             raise ValueError("want_lengths needs eos: without it every hypothesis has U labels")
@@ -850,8 +906,10 @@ class Seq2SeqDecoder(torch.nn.Module):
             enc = encoder_outputs.detach().float().transpose(0, 1).contiguous()          # (T, bsz, C)
             T = enc.shape[0]
             enc2 = enc.view(T * bsz, -1)
-            p = self._search_plan(P, dev, bsz, T, W, U, V, eos)
+            p = self._search_plan(P, dev, bsz, T, W, U, V, eos, n_host is not None)
             R = W * bsz
+            if n_host is not None:
+                p["n_rows"].copy_(torch.tensor(n_host * W, dtype=torch.int32), non_blocking=True)
             # set-up as in infer: keys / values once, replicated per hypothesis; initial state; all-zero first input
             p["keys"].view(T, W, bsz, Kd).copy_(_ops.gemm(enc2, P["key.weight"].t(), P["key.bias"]).view(T, 1, bsz, Kd).expand(T, W, bsz, Kd))
             p["values"].view(T, W, bsz, Vd).copy_(_ops.gemm(enc2, P["value.weight"].t(), P["value.bias"]).view(T, 1, bsz, Vd).expand(T, W, bsz, Vd))
@@ -886,15 +944,15 @@ class Seq2SeqDecoder(torch.nn.Module):
 # per-utterance lengths (padding-invariant inference and masked training; the definition is in include/slu_hip.h and
 # DESIGN.md section 7)
 # ------------------------------------------------------------------------------------------------
-def _host_lengths(lengths, B, T):
+def _host_lengths(lengths, B, T, unit="samples"):
     """lengths (list / tensor of B sample counts) -> list of B Python ints, each in [1, T]; ValueError otherwise.  Host
-    arithmetic only: a bad length never reaches a launch."""
+    arithmetic only: a bad length never reaches a launch.  unit: what the counts count, for the messages."""
     if torch.is_tensor(lengths):
         if lengths.is_floating_point() or lengths.dtype == torch.bool:
             raise ValueError("lengths: expected integers, got %s" % lengths.dtype)
         lengths = lengths.detach().cpu().reshape(-1).tolist() if lengths.dim() <= 1 else lengths
     if torch.is_tensor(lengths) or not hasattr(lengths, "__len__"):
-        raise ValueError("lengths: expected a 1-D sequence of %d sample counts" % B)
+        raise ValueError("lengths: expected a 1-D sequence of %d %s" % (B, "sample counts" if unit == "samples" else "counts of " + unit))
     vals = list(lengths)
     if len(vals) != B:
         raise ValueError("lengths: %d entries for a batch of %d" % (len(vals), B))
@@ -902,7 +960,7 @@ def _host_lengths(lengths, B, T):
         if isinstance(v, bool) or int(v) != v:
             raise ValueError("lengths: expected integers, got %r" % (v,))
         if not 1 <= int(v) <= T:
-            raise ValueError("lengths: %d outside [1, %d] (the batch has %d samples per row)" % (int(v), T, T))
+            raise ValueError("lengths: %d outside [1, %d] (the batch has %d %s per row)" % (int(v), T, T, unit))
     return [int(v) for v in vals]
 
 
@@ -1690,15 +1748,15 @@ class Model(torch.nn.Module):
         """Model.forward with per-utterance lengths (DESIGN.md section 7 "Lengths"): the waveform tail is zeroed, every
         stage runs length-aware in exact fp32 (frozen ones outside autograd, trainable GRU layers as ops.GRULayerLenFn,
         trainable CNN blocks — with SLU_MASK_TRAIN_CNN=1 — as ops.SincBlockLenFn / ConvBlockLenFn), the head is
-        ops.IntentHeadLenFn.  In train() mode every dropout site draws the masks it draws without lengths
-        (the dense batch's Philox stream or the injected masks), so with p = 0 or injected masks the gradients equal the
+        ops.IntentHeadLenFn — or, for a seq2seq model under SLU_MASK_SEQ2SEQ=1, the intent encoder's stages the same way and
+        the teacher-forced decoder on the frame counts behind them.  In train() mode every dropout site draws the masks it
+        draws without lengths (the dense batch's Philox stream or the injected masks), so with p = 0 or injected masks the gradients equal the
         mean of the alone runs' exactly, with Philox masks in distribution.  Everything that can be refused is refused
         here, on the host, before the first launch."""
         if n_prefix > 0:
             raise ValueError("lengths: the look-ahead pipeline (n_prefix > 0) has no masked steps")
         if self.seq2seq:
-            raise ValueError("lengths: seq2seq models are not supported (the decoder's attention would have to mask the "
-                             "encoder frames as well)")
+            _refuse_seq2seq_lengths()
         if torch.is_tensor(rng_step):
             raise ValueError("lengths: captured steps (a device-resident rng_step) are not supported")
         if x.dim() != 2:
@@ -1723,6 +1781,12 @@ class Model(torch.nn.Module):
             dev_len = torch.tensor(host, dtype=torch.int32).to(x.device, non_blocking=True)
             x = _ops.mask_rows_len(x, dev_len)
         h, _, n_dev = _run_stages_len(stages, x, host, training=self.training)
+        if self.seq2seq:
+            # loss = -mean over the padded batch's rows of log p(y_b | x_b[:lengths[b]]); a host zero for the accuracy, as
+            # the dense branch (forward_from)
+            loss_acc, _ = self.decoder.teacher_forced(h, y_intent.to(h.device), n_dev.contiguous())
+            self.last_loss_acc = loss_acc
+            return loss_acc[0], torch.tensor([0.])
         cls = self.intent_layers[-2]
         loss, acc, _, _ = _ops.IntentHeadLenFn.apply(h, n_dev.contiguous(), cls.weight, cls.bias, y_intent.to(h.device),
                                                      tuple(self.values_per_slot))
@@ -1743,10 +1807,10 @@ class Model(torch.nn.Module):
         return [r[0] for r in out] if single else out
 
     def _intent_features_tm_len(self, x, lengths):
-        """Length-aware encoder + intent layers -> (h time-major, host lengths, device lengths of h)."""
+        """Length-aware encoder + intent layers (a seq2seq model's intent encoder, under SLU_MASK_SEQ2SEQ=1) -> (h
+        time-major, host lengths, device lengths of h)."""
         if self.seq2seq:
-            raise ValueError("lengths: seq2seq models are not supported (the decoder's attention would have to mask the "
-                             "encoder frames as well)")
+            _refuse_seq2seq_lengths()
         return self.pretrained_model._features_tm_len(x, lengths, self._intent_stages)
 
     def eval_group(self, xs, ys, lengths=None):
@@ -1755,12 +1819,16 @@ class Model(torch.nn.Module):
         the same latency), then the per-batch loss/accuracy.  Returns [(loss, acc), ...] — the values
         forward() gives batch by batch.
         lengths (None: the evaluation above): one sequence of sample counts per batch -> the padding-invariant
-        evaluation: every utterance contributes the loss / correctness of the utterance run alone."""
+        evaluation: every utterance contributes the loss / correctness of the utterance run alone.  A seq2seq model
+        (SLU_MASK_SEQ2SEQ=1) is evaluated batch by batch: the (loss, host zero) of forward(lengths=...) without autograd."""
         assert not self.training
         pm = self.pretrained_model
         if lengths is not None:
             if len(lengths) != len(xs):
                 raise ValueError("lengths: %d entries for %d batches" % (len(lengths), len(xs)))
+            if self.seq2seq:
+                with torch.no_grad():
+                    return [self._forward_len(x, y, l, None, 0) for x, y, l in zip(xs, ys, lengths)]
             B = xs[0].shape[0]
             host = []
             for x, l in zip(xs, lengths):
@@ -1797,10 +1865,19 @@ class Model(torch.nn.Module):
         """-> (intent_logits (B, num_values_total), predicted_intent (B, num_slots)) (models.py:830-846)
         lengths (not in the reference; None: the call as it was): the utterances' sample counts, each in [1, T] ->
         padding-invariant inference: row b's logits are those of x[b:b+1, :lengths[b]] run alone (eval mode, fixed-slot
-        models, GRU hidden sizes 16 / 32 / 64 / 128; exact fp32 kernels whatever SLU_FROZEN_MATH says)."""
+        models, GRU hidden sizes 16 / 32 / 64 / 128; exact fp32 kernels whatever SLU_FROZEN_MATH says).  A seq2seq model
+        (SLU_MASK_SEQ2SEQ=1): the beam search below on the lengths — utterance b's hypotheses and scores are those of
+        x[b:b+1, :lengths[b]] searched alone."""
         if lengths is not None:
-            h, _, n_dev = self._intent_features_tm_len(x, lengths)
+            h, n_host, n_dev = self._intent_features_tm_len(x, lengths)
             _DropoutState.current = next_rng_step()
+            if self.seq2seq:
+                enc = h.contiguous().transpose(0, 1)
+                if beam_search_mode() == "host":
+                    return self.decoder.infer(enc, self.Sy_intent, B=4, enc_lengths=n_host, **self._beam_eos())
+                scores, _, beam = self.decoder.search(enc, self.Sy_intent, B=4, want_beam=True, enc_lengths=n_host,
+                                                      **self._beam_eos())
+                return scores, beam
             cls = self.intent_layers[-2]
             _, logits, pred, _ = _ops.cls_maxpool_len_fwd(h.contiguous(), cls.weight.detach(), cls.bias.detach(), n_dev,
                                                           None, tuple(self.values_per_slot))
@@ -1820,23 +1897,29 @@ class Model(torch.nn.Module):
         """The search's eos argument under SLU_BEAM_EOS (nothing when the knob is off: the calls are today's)."""
         return {"eos": self.Sy_intent.index("<eos>")} if beam_eos_enabled() else {}
 
-    def decode_nbest(self, x, n=4):
+    def decode_nbest(self, x, n=4, lengths=None):
         """seq2seq: -> list (batch) of lists of (string, score): the n <= 4 best hypotheses of the width-4 device search
         (Seq2SeqDecoder.search), best first; score = the hypothesis' log-probability as the search ranks it.  With
         SLU_BEAM_EOS=1 a hypothesis is cut at its length before the cleaning decode_intents applies (so entry 0 is
         decode_intents' string); without, the whole row is cleaned.  Labels, scores and lengths cross to the host in one
-        copy."""
+        copy.  lengths (None: the call above): the utterances' sample counts, as decode_intents (SLU_MASK_SEQ2SEQ=1)."""
         if not self.seq2seq:
             raise ValueError("decode_nbest: the n-best list comes from the seq2seq decoder's beam search")
         W = 4
         if not 1 <= n <= W:
             raise ValueError("decode_nbest: n = %r outside [1, %d]" % (n, W))
         fin = self._beam_eos()
-        h = self._intent_features_tm(x).contiguous()
-        out = self.decoder.search(h.transpose(0, 1), self.Sy_intent, B=W, want_lengths=bool(fin), **fin)
+        if lengths is not None:
+            h, n_host, _ = self._intent_features_tm_len(x, lengths)
+            _DropoutState.current = next_rng_step()
+            fin = dict(fin, enc_lengths=n_host)
+        else:
+            h = self._intent_features_tm(x)
+        h = h.contiguous()
+        out = self.decoder.search(h.transpose(0, 1), self.Sy_intent, B=W, want_lengths="eos" in fin, **fin)
         scores, labels = out[0], out[1]
         U = labels.shape[2]
-        lengths = out[2] if fin else torch.full_like(scores, U, dtype=torch.int32)
+        lengths = out[2] if "eos" in fin else torch.full_like(scores, U, dtype=torch.int32)
         # float64 holds all three exactly
         packed = torch.cat([labels[:n].double(), lengths[:n].double().unsqueeze(2), scores[:n].double().unsqueeze(2)],
                            dim=2).cpu()
@@ -1853,7 +1936,17 @@ class Model(torch.nn.Module):
 
     def decode_intents(self, x, lengths=None):
         """-> list (batch) of lists (slots) of slot-value strings (reference models.py:853-865).
-        lengths: as predict_intents (fixed-slot models only)."""
+        lengths: as predict_intents; a seq2seq model (SLU_MASK_SEQ2SEQ=1) -> list (batch) of the best hypotheses' strings."""
+        if lengths is not None and self.seq2seq:
+            if beam_search_mode() == "device":
+                h, n_host, _ = self._intent_features_tm_len(x, lengths)
+                _DropoutState.current = next_rng_step()
+                _, labels = self.decoder.search(h.contiguous().transpose(0, 1), self.Sy_intent, B=4, enc_lengths=n_host,
+                                                **self._beam_eos())
+                S = self.Sy_intent
+                return ["".join([S[c] for c in row]).lstrip("<sos>").rstrip("<eos>") for row in labels[0].cpu().tolist()]
+            pred = self.predict_intents(x, lengths)[1].cpu()
+            return [self.one_hot_to_string(pred[0, i], self.Sy_intent) for i in range(pred.shape[1])]
         if lengths is not None:
             pred = self.predict_intents(x, lengths)[1].cpu()
             inverse = [{idx: value for value, idx in self.Sy_intent[slot].items()} for slot in self.Sy_intent]

@@ -2070,6 +2070,33 @@ def attention_bwd(keys, values, query, d_ctx, weights, d_keys, d_values, d_query
                                    d_query.stride(0), float(inv_scale), B, T, Kd, Vd, _stream()), "slu_attention_bwd")
 
 
+def attention_len_fwd(keys, values, query, ctx, weights, inv_scale, n):
+    """attention_fwd over the first n[b] frames of row b (n: int32 CUDA tensor of B frame counts; include/slu_hip.h has
+    the rule): weights[b, n[b]:] = 0, keys / values beyond are never read; bit-equal to attention_fwd on every row alone."""
+    L = _lib.load()
+    T, B, Kd = keys.shape
+    Vd = values.shape[2]
+    _len_ok(n, B)
+    _lib.check(L.slu_attention_len_fwd(keys.data_ptr(), keys.stride(0), keys.stride(1), values.data_ptr(), values.stride(0),
+                                       values.stride(1), query.data_ptr(), query.stride(0), ctx.data_ptr(), ctx.stride(0),
+                                       weights.data_ptr(), n.data_ptr(), float(inv_scale), B, T, Kd, Vd, _stream()),
+               "slu_attention_len_fwd")
+
+
+def attention_len_bwd(keys, values, query, d_ctx, weights, d_keys, d_values, d_query, inv_scale, n):
+    """attention_bwd over the first n[b] frames of row b: d_keys / d_values accumulated below n[b], untouched beyond."""
+    L = _lib.load()
+    T, B, Kd = keys.shape
+    Vd = values.shape[2]
+    _len_ok(n, B)
+    assert d_keys.stride() == keys.stride() and d_values.stride() == values.stride()
+    _lib.check(L.slu_attention_len_bwd(keys.data_ptr(), keys.stride(0), keys.stride(1), values.data_ptr(), values.stride(0),
+                                       values.stride(1), query.data_ptr(), query.stride(0), d_ctx.data_ptr(), d_ctx.stride(0),
+                                       weights.data_ptr(), d_keys.data_ptr(), d_values.data_ptr(), d_query.data_ptr(),
+                                       d_query.stride(0), n.data_ptr(), float(inv_scale), B, T, Kd, Vd, _stream()),
+               "slu_attention_len_bwd")
+
+
 def logsoftmax_dot_fwd(logits, y_u, logp_acc, lse):
     L = _lib.load()
     B, V = logits.shape
@@ -2158,14 +2185,16 @@ def beam_backtrack(backptr, labels, out, one_hot=None):
 
 
 def decoder_step(P, keys, values, state_prev, state_next, y_prev, q, inp0, att_w, gi, gh, save, drop, logits, step,
-                 drop_cfg):
+                 drop_cfg, n_rows=None):
     """One decoding step (models.py:528-536) on the HIP kernels, shared by the teacher-forced forward and the beam
     search: attention on the top layer's state, embedding of the previous label, the GRUCell stack (+ dropout between
     the cells), output logits.  P: parameter dict (detached tensors); state_* (B, L, Dd); save / drop: per-layer
     buffers or None (inference); drop_cfg = (p, masks or None, seed, offset, offset_dev, B * Dd).
     y_prev None: the embedding half of inp0 is already filled; logits None: the caller computes them later (teacher
     forcing knows every input label up front and needs the logits only after the loop: both become ONE GEMM over all
-    steps instead of one small launch per step)."""
+    steps instead of one small launch per step).
+    n_rows (None: every row attends over all T frames): int32 CUDA tensor, one encoder frame count per row of the step
+    batch -> the length-aware attention (attention_len_fwd); nothing else in the step looks at the encoder."""
     Lc, Dd = state_prev.shape[1], state_prev.shape[2]
     E = P["embed.weight"].shape[0]
     p, masks, seed, offset, offset_dev, bd = drop_cfg
@@ -2174,7 +2203,10 @@ def decoder_step(P, keys, values, state_prev, state_next, y_prev, q, inp0, att_w
     group = [(state_prev[:, Lc - 1], P["query.weight"], P["query.bias"], q, 0, 0)]
     group += [(state_prev[:, l], P["w_hh%d" % l], P["b_hh%d" % l], gh[l], 0, 0) for l in range(Lc)]
     gemm_small_batched(group)
-    attention_fwd(keys, values, q, inp0[:, E:], att_w, P["inv_scale"])
+    if n_rows is None:
+        attention_fwd(keys, values, q, inp0[:, E:], att_w, P["inv_scale"])
+    else:
+        attention_len_fwd(keys, values, q, inp0[:, E:], att_w, P["inv_scale"], n_rows)
     if y_prev is not None:
         gemm(y_prev, P["embed.weight"].t(), P["embed.bias"], out=inp0[:, :E])
     x_in = inp0
@@ -2196,12 +2228,17 @@ class Seq2SeqDecoderFn(torch.autograd.Function):
     teacher-forced log p(y | x) of every utterance and loss = -mean.  enc time-major (T, B, 2 * encoder_dim); y
     (B, U, V) float (one-hot rows, padded with <eos>).  One autograd node for the whole decoder: the backward is a
     hand-written BPTT over the U steps on the same kernels (every Linear's weight gradient is ONE GEMM over the
-    (U * B)-row history).  Returns (loss_acc (2) = [loss, 0], log_p (B)); only loss_acc[0] carries a gradient."""
+    (U * B)-row history).  Returns (loss_acc (2) = [loss, 0], log_p (B)); only loss_acc[0] carries a gradient.
+    meta may carry an eighth entry, n_rows (int32 CUDA tensor of B encoder frame counts): row b's attention then ranges over
+    its first n_rows[b] frames at every step, forward and backward (attention_len_fwd / _bwd).  d_keys / d_values start
+    zeroed and stay so at the padded frames, hence d_enc is exactly 0 there and key / value.weight.grad receive nothing
+    from them; the 1 / B of the loss is the padded batch's B.  Everything else is the dense path, call for call."""
     NAMES = None    # set per call: parameter names in argument order
 
     @staticmethod
     def forward(ctx, enc, y, meta, *params):
-        names, SOS, p, masks, seed, offset, offset_dev = meta
+        names, SOS, p, masks, seed, offset, offset_dev = meta[:7]
+        n_rows = meta[7] if len(meta) > 7 else None
         P = {n: t.detach() for n, t in zip(names, params)}
         dev = enc.device
         enc = _f32c(enc, "encoder output")
@@ -2234,7 +2271,7 @@ class Seq2SeqDecoderFn(torch.autograd.Function):
         gemm(yprev.view(U * B, V), P["embed.weight"].t(), P["embed.bias"], out=inp0.view(U * B, E + Vd)[:, :E])
         for u in range(U):
             decoder_step(P, keys, values, state[u], state[u + 1], None, q[u], inp0[u], att_w[u], gi, gh, save[u],
-                         [drop[l][u] for l in range(Lc - 1)], None, u, dcfg)
+                         [drop[l][u] for l in range(Lc - 1)], None, u, dcfg, n_rows)
         # ... and the output layer of all steps in one GEMM over the state history; the per-step scores are then added
         # in step order (the reference's running sum, models.py:540)
         top = slice((Lc - 1) * Dd, Lc * Dd)
@@ -2245,7 +2282,7 @@ class Seq2SeqDecoderFn(torch.autograd.Function):
         loss_acc = torch.zeros(2, dtype=torch.float32, device=dev)
         L = _lib.load()
         _lib.check(L.slu_neg_mean_f32(logp.data_ptr(), loss_acc.data_ptr(), B, _stream()), "slu_neg_mean_f32")
-        ctx.meta = (names, p, masks, seed, offset, offset_dev, (T, B, E2, U, V, Lc, Dd, E, Kd, Vd), P["inv_scale"])
+        ctx.meta = (names, p, masks, seed, offset, offset_dev, (T, B, E2, U, V, Lc, Dd, E, Kd, Vd), P["inv_scale"], n_rows)
         ctx.save_for_backward(enc, ycat, yprev, keys, values, state, q, att_w, inp0, save, drop, logits, lse, *params)
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(logp)
@@ -2253,7 +2290,7 @@ class Seq2SeqDecoderFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_loss_acc, _d_logp):
-        names, p, masks, seed, offset, offset_dev, dims, inv_scale = ctx.meta
+        names, p, masks, seed, offset, offset_dev, dims, inv_scale, n_rows = ctx.meta
         T, B, E2, U, V, Lc, Dd, E, Kd, Vd = dims
         n_par = len(names)
         if d_loss_acc is None:
@@ -2287,7 +2324,10 @@ class Seq2SeqDecoderFn(torch.autograd.Function):
                 # one grouped launch: the recurrent part of d h_{u-1} (accumulated) and the gradient of the cell's input
                 gemm_small_batched([(d_gh[l, u], P["w_hh%d" % l], None, d_state[:, l], 1, 1),
                                     (d_gi[l, u], P["w_ih%d" % l], None, d_x if l > 0 else d_inp0[u], 1, 0)])
-            attention_bwd(keys, values, q[u], d_inp0[u][:, E:], att_w[u], d_keys, d_values, d_q[u], inv_scale)
+            if n_rows is None:
+                attention_bwd(keys, values, q[u], d_inp0[u][:, E:], att_w[u], d_keys, d_values, d_q[u], inv_scale)
+            else:
+                attention_len_bwd(keys, values, q[u], d_inp0[u][:, E:], att_w[u], d_keys, d_values, d_q[u], inv_scale, n_rows)
             gemm_small_batched([(d_q[u], P["query.weight"], None, d_state[:, Lc - 1], 1, 1)])
         grads = {}
         st_prev = state[:U].view(U * B, Lc * Dd)                     # rows (u, b): the state BEFORE step u

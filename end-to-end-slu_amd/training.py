@@ -816,7 +816,7 @@ class Trainer:
                     # reference training.py:158-164: from the third epoch on the test accuracy is the fraction of
                     # utterances whose beam-search string equals the label string
                     x, y = current[:2]
-                    guess = self.model.decode_intents(x)
+                    guess = self.model.decode_intents(x, *self._seq2seq_lengths(current))
                     truth = [self.model.one_hot_to_string(y[i], self.model.Sy_intent) for i in range(batch_size)]
                     hit = sum(g == t for g, t in zip(guess, truth)) / batch_size
                     string_acc += hit * batch_size
@@ -847,6 +847,13 @@ class Trainer:
             means[1] = means[1] + means[-1]          # intent_acc += string accuracy (the model's own acc is 0)
         return means[:len(names)]
 
+    @staticmethod
+    def _seq2seq_lengths(batch):
+        """(lengths,) for the decoding calls where the batch carries them (SLU_MASK_PADDING=1) and the seq2seq decoder takes
+        them (SLU_MASK_SEQ2SEQ=1); () otherwise: the calls are then the ones without the knobs."""
+        import models
+        return (batch[2],) if len(batch) == 3 and models.mask_seq2seq_enabled() else ()
+
     def _say_seq2seq_sample(self, batch):
         """Reference training.py:103-112: decode the first utterance of the batch the step just consumed."""
         x, y = batch[:2]
@@ -856,7 +863,7 @@ class Trainer:
         self.model.eval()
         try:
             print("seq2seq output")
-            print("guess: " + self.model.decode_intents(x[:1])[0])
+            print("guess: " + self.model.decode_intents(x[:1], *[l[:1] for l in self._seq2seq_lengths(batch)])[0])
             print("truth: " + self.model.one_hot_to_string(y[0].cpu(), self.model.Sy_intent))
         finally:
             self.model.train(was_training)

@@ -690,6 +690,29 @@ int slu_pool_act_len_fwd_route(const float* x, float* y, uint8_t* route, const i
 int slu_pool_act_len_bwd(const float* dy, const float* y, const uint8_t* route, const int32_t* lengths, float* dx, int64_t B,
                          int64_t L, int64_t C, int64_t pool, float slope, int64_t out_sb, int64_t out_sl, void* stream);
 
+/* -------- lengths through the seq2seq decoder's attention — added under ABI 10 (two new entry points; nothing existing
+ * changed, so the version number stays).  slu_attention_fwd / _bwd with n (B) int32: row b attends over its first
+ * n_b = clamp(n[b], 0, T) frames (the valid frames behind the intent encoder; beam-search rows w * batch + b carry the
+ * utterance's count, replicated by the host).
+ *   weights[b, t]   exactly 0.0f for t >= n_b (written: the saved plane is whole); softmax over t < n_b below.
+ *   keys / values   at t >= n_b are never read (they may hold anything, NaN included).
+ *   d_keys / d_values   ACCUMULATED into (+=) at t < n_b; at t >= n_b neither read nor written.
+ *   n_b == 0        ctx[b] = 0, weights[b] = 0, d_query[b] = 0; no division by an empty sum.
+ * One workgroup per row; n_b is uniform in it and bounds every loop over frames, which are otherwise the dense kernels'
+ * (a wave per frame for the dot products, per-thread partials over t = tid, tid + 256, ... reduced by the same tree, sums
+ * over t in order for the context and d_query).  So row b's ctx, weights[:n_b], d_query and d_keys / d_values[:n_b] are
+ * BIT-EQUAL to slu_attention_fwd / _bwd on that row alone with T = n_b, and n_b = T for every row is the dense call.
+ * NULL n: SLU_ERR_INVALID_ARG ("... lengths"), before any launch.  The LDS bound (and SLU_ERR_UNSUPPORTED) is the dense
+ * pair's, on T.  Model-level consequences (loss, gradients, beam search of a padded batch = each utterance alone):
+ * DESIGN.md section 7 "Lengths".                                                                                       */
+int slu_attention_len_fwd(const float* keys, int64_t k_st, int64_t k_sb, const float* values, int64_t v_st, int64_t v_sb,
+                          const float* query, int64_t ld_q, float* ctx, int64_t ld_ctx, float* weights, const int32_t* n,
+                          float inv_scale, int64_t B, int64_t T, int64_t Kd, int64_t Vd, void* stream);
+int slu_attention_len_bwd(const float* keys, int64_t k_st, int64_t k_sb, const float* values, int64_t v_st, int64_t v_sb,
+                          const float* query, int64_t ld_q, const float* d_ctx, int64_t ld_dctx, const float* weights,
+                          float* d_keys, float* d_values, float* d_query, int64_t ld_dq, const int32_t* n, float inv_scale,
+                          int64_t B, int64_t T, int64_t Kd, int64_t Vd, void* stream);
+
 /* -------- Adam: torch.optim.Adam(model.parameters(), lr) (training.py:19, default betas / eps) ------
  * One launch updates up to slu_adam_max_tensors() tensors of one dtype (elem_bytes 4 / 8); the pointer
  * arrays are HOST arrays of device pointers (they travel in the kernel arguments: hipGraph-safe).
