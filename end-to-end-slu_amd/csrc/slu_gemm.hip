@@ -200,43 +200,6 @@ colsum_kernel(const float* __restrict__ X, long long rs, float* __restrict__ out
   }
 }
 
-// Two-stage, atomic-free column sum for tall matrices: partial[rsplit][n] then a fixed-order reduce.
-__global__ void __launch_bounds__(256)
-colsum_partial_kernel(const float* __restrict__ X, long long rs, float* __restrict__ part, int M,
-                      int N, int rows_per_split) {
-  __shared__ float red[4][64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int n = blockIdx.x * 64 + lane;
-  const int m0 = blockIdx.y * rows_per_split;
-  const int m1 = min(M, m0 + rows_per_split);
-  float s = 0.0f;
-  if (n < N)
-    for (int m = m0 + w; m < m1; m += 4) s += X[(long long)m * rs + n];
-  red[w][lane] = s;
-  __syncthreads();
-  if (w == 0 && n < N)
-    part[(size_t)blockIdx.y * N + n] = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
-}
-
-// 64 columns x 4 row groups per workgroup: the (up to 256) partial rows are summed by four waves in
-// parallel (fixed order: deterministic), not by one serial loop per column.
-__global__ void __launch_bounds__(256)
-colsum_final_kernel(const float* __restrict__ part, float* __restrict__ out, int N, int RS) {
-  __shared__ float red[4][64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int n = blockIdx.x * 64 + lane;
-  float s0 = 0.0f, s1 = 0.0f;
-  if (n < N) {
-    int r = w;
-#pragma unroll 4
-    for (; r + 4 < RS; r += 8) { s0 += part[(size_t)r * N + n]; s1 += part[(size_t)(r + 4) * N + n]; }
-    if (r < RS) s0 += part[(size_t)r * N + n];
-  }
-  red[w][lane] = s0 + s1;
-  __syncthreads();
-  if (w == 0 && n < N) out[n] = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
-}
-
 // ---- batched small "A^T B" GEMMs: the weight gradients of ONE small GRU layer in one launch -------------------
 //   C_q (M_q x N_q) = A_q^T B_q,  A_q (K_q x M_q, row stride lda), B_q (K_q x N_q, row stride ldb), q < count <= 4
 // (dW_ih = d_gx^T x and dW_hh = d_gh^T h_prev of each direction).  With K = T*B of a few thousand rows (the intent
@@ -741,25 +704,6 @@ gemm_tn_small_mt_kernel(const TnArgs a) {
     }
 }
 
-int colsum_splits(int64_t M) {
-  int64_t rs = cdiv(M, 64);
-  return (int)(rs > 256 ? 256 : (rs < 1 ? 1 : rs));
-}
-
-// out[n] = sum_m X[m*rs + n] using `ws` (colsum_splits(M) * N floats).
-int colsum_two_stage(const float* X, int64_t rs, float* out, int64_t M, int64_t N, float* ws,
-                     hipStream_t st) {
-  const int RS = colsum_splits(M);
-  const int rows = (int)cdiv(M, RS);
-  hipLaunchKernelGGL(colsum_partial_kernel, dim3((unsigned)cdiv(N, 64), (unsigned)RS), dim3(256), 0, st,
-                     X, (long long)rs, ws, (int)M, (int)N, rows);
-  SLU_CHECK_LAUNCH("colsum_partial_kernel");
-  hipLaunchKernelGGL(colsum_final_kernel, dim3((unsigned)cdiv(N, 64)), dim3(256), 0, st,
-                     (const float*)ws, out, (int)N, RS);
-  SLU_CHECK_LAUNCH("colsum_final_kernel");
-  return SLU_OK;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // Grouped small-M GEMMs in ONE launch (the seq2seq decoder's per-step products: 64 utterances x a few hundred
 // columns x K <= 768, reference models.py:427-485): up to four independent problems
@@ -908,6 +852,13 @@ extern "C" size_t slu_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K) {
   int KS, kper, wt;
   split_plan(M, N, K, &KS, &kper, &wt);
   return KS > 1 ? (size_t)KS * M * N * sizeof(float) : 0;
+}
+
+extern "C" int slu_gemm_plan(int64_t M, int64_t N, int64_t K, int* ksplit, int* k_per_split, int* tile) {
+  SLU_REQUIRE(ksplit && k_per_split && tile, "slu_gemm_plan: null pointer");
+  SLU_REQUIRE(M > 0 && N > 0 && K > 0, "slu_gemm_plan: non-positive size");
+  split_plan(M, N, K, ksplit, k_per_split, tile);
+  return SLU_OK;
 }
 
 extern "C" int slu_gemm_f32(const float* A, int64_t a_rs, int64_t a_cs, const float* B,

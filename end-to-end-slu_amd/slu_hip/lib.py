@@ -63,6 +63,7 @@ SIGNATURES = {
     "slu_wconv_bwd_weight": (c_int, [vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, vp,
                                      c_sz, vp]),
     "slu_gemm_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "slu_gemm_plan": (c_int, [c_i64, c_i64, c_i64, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "slu_gemm_f32": (c_int, [vp, c_i64, c_i64, vp, c_i64, c_i64, vp, c_i64, c_i64, vp, c_i64, c_i64,
                              c_i64, c_int, vp, c_sz, vp]),
     "slu_split_bf16": (c_int, [vp, c_i64, vp, c_i64, c_i64, c_i64, c_int, vp]),

@@ -130,6 +130,10 @@ int slu_wconv_bwd_weight(const float* d_conv, const float* in, float* d_weight, 
  * with A(m,k) = A[m*a_rs + k*a_cs], B(k,n) = B[k*b_rs + n*b_cs], C(m,n) = C[m*c_rs + n*c_cs].
  * Exact fp32 (v_mfma_f32_16x16x4_f32), split-K through the workspace when M*N is small.          */
 size_t slu_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K);
+/* What slu_gemm_f32 will do for this shape, launching nothing (host only): *ksplit k ranges of *k_per_split (a multiple
+ * of 32; the last one may be shorter; > 1: split-K through the workspace plus a reduce launch), *tile = 2 (64 x 64
+ * workgroup tiles) or 4 (128 x 128).  The tile order is renumbered per XCD when the tile count is a multiple of 8.     */
+int slu_gemm_plan(int64_t M, int64_t N, int64_t K, int* ksplit, int* k_per_split, int* tile);
 int slu_gemm_f32(const float* A, int64_t a_rs, int64_t a_cs, const float* B, int64_t b_rs,
                  int64_t b_cs, float* C, int64_t c_rs, int64_t c_cs, const float* bias_n,
                  int64_t M, int64_t N, int64_t K, int accumulate, void* workspace,
