@@ -67,6 +67,7 @@ struct GruBfParams {
   const unsigned* keep;   // EPI > 0: keep bits (T, B, D*H/32), bit c % 32 of word c / 32 = element (t, b, c); null: no dropout
   float keep_scale;       // 1 / (1 - p)
   int T, B, D;
+  const int* lengths;     // (B) valid steps per sequence: read by the LEN instantiations only
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -112,8 +113,16 @@ struct GruLds {
 // REV (round 6): the direction is a template parameter of the body — blockIdx.y picks the instantiation —, so that the ~20
 // selects per step on the (workgroup-uniform) direction in the Dropout + pooling epilogue and the time arithmetic are
 // resolved at compile time: the loop is bound by instruction issue, every VALU slot counts (same arithmetic, same bits).
-template <int H, int NS, int KI, int EPI, bool REV>
+//
+// LEN (slu_gru_seq_fwd_len_bf16; EPI 0, KI 0, NS 3): `lengths` (B) gives every sequence its own number of valid steps n_b
+// (clamped to [1, T]) — slu_gru_seq_fwd_len's definition on this kernel's arithmetic.  A lane owns four units of ONE
+// sequence, so it keeps that sequence's n in one register and selects h_t = t < n ? h_t : 0 between the blend and the
+// split: direction 0 writes zeros from n_b on, direction 1 stays at h = 0 through the padding and so starts its step
+// t = n_b - 1 from h = 0.  A select, not a product: gx at padded steps may hold anything (NaN), it seeds the chains of
+// that sequence's MFMA column only, and columns do not mix.  LEN = false is the kernel as it was.
+template <int H, int NS, int KI, int EPI, bool REV, bool LEN = false>
 __device__ __forceinline__ void gru_bf_fwd_body(const GruBfParams& p) {
+  static_assert(!LEN || (EPI == 0 && KI == 0 && NS == 3), "lengths: fp32 output of every step, gx given, bf16x3");
   constexpr int NW = H / 16;          // waves
   constexpr int KC = H / 32;          // 32-wide k-chunks
   constexpr int SLOTS = H / 8;        // 16-byte slots per h row
@@ -135,6 +144,8 @@ __device__ __forceinline__ void gru_bf_fwd_body(const GruBfParams& p) {
   const int T = p.T, B = p.B, D = p.D;
   const int seq = b0 + i;
   const int seqc = seq < B ? seq : B - 1;       // rows past B repeat the last sequence and are never stored
+  int nlen = 0;                                 // LEN: valid steps of this lane's sequence
+  if constexpr (LEN) nlen = min(max(p.lengths[seqc], 1), p.T);
 
   if constexpr (NS == 2) f16_denorm_flush();
 
@@ -392,6 +403,7 @@ __device__ __forceinline__ void gru_bf_fwd_body(const GruBfParams& p) {
       const float zz = bf_sigmoid(acc[1][r]);
       const float nn = bf_tanh(gn[r] + rr * acc[2][r]);
       hn[r] = nn + zz * (hprev[r] - nn);
+      if constexpr (LEN) hn[r] = (t < nlen) ? hn[r] : 0.0f;
     }
     // h_t -> LDS as NS planes: four consecutive units = one 8-byte store per plane
     {
@@ -508,11 +520,11 @@ __device__ __forceinline__ void gru_bf_fwd_body(const GruBfParams& p) {
 #undef SLU_GX_STAGE
 }
 
-template <int H, int NS, int KI, int EPI>
+template <int H, int NS, int KI, int EPI, bool LEN = false>
 __global__ void __launch_bounds__(H * 4)
 gru_bf_fwd_kernel(const GruBfParams p) {
-  if (blockIdx.y) gru_bf_fwd_body<H, NS, KI, EPI, true>(p);
-  else gru_bf_fwd_body<H, NS, KI, EPI, false>(p);
+  if (blockIdx.y) gru_bf_fwd_body<H, NS, KI, EPI, true, LEN>(p);
+  else gru_bf_fwd_body<H, NS, KI, EPI, false, LEN>(p);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1004,15 +1016,15 @@ gru_bf_fwd_rs_kernel(const GruBfParams p) {
   }
 }
 
-template <int H, int NS, int KI, int EPI>
+template <int H, int NS, int KI, int EPI, bool LEN = false>
 static void gru_bf_launch(dim3 grid, hipStream_t st, const GruBfParams& p) {
   constexpr int lds = GruLds<H, NS, KI, EPI>::BYTES;
   static bool raised = false;      // > 64 KiB of dynamic LDS needs the function attribute (once per instantiation)
   if (lds > 64 * 1024 && !raised) {
-    (void)hipFuncSetAttribute((const void*)gru_bf_fwd_kernel<H, NS, KI, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute((const void*)gru_bf_fwd_kernel<H, NS, KI, EPI, LEN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     raised = true;
   }
-  hipLaunchKernelGGL((gru_bf_fwd_kernel<H, NS, KI, EPI>), grid, dim3(H * 4), lds, st, p);
+  hipLaunchKernelGGL((gru_bf_fwd_kernel<H, NS, KI, EPI, LEN>), grid, dim3(H * 4), lds, st, p);
 }
 
 template <int H, int NS, int EPI>
@@ -1090,7 +1102,7 @@ static int gru_bf_common(const char* who, GruBfParams& p, const float* gx, const
   p.xp = (const unsigned short*)x_planes; p.x_plane = x_plane_stride; p.wih = (const uint4*)w_ih_packed; p.b_ih = b_ih;
   p.gx = gx; p.w_hh[0] = w_hh_fwd; p.w_hh[1] = w_hh_rev; p.b_hh[0] = b_hh_fwd; p.b_hh[1] = b_hh_rev;
   p.out = nullptr; p.reserve = nullptr; p.planes = nullptr; p.plane = 0; p.keep = nullptr; p.keep_scale = 1.0f;
-  p.T = (int)T; p.B = (int)B; p.D = (int)D;
+  p.T = (int)T; p.B = (int)B; p.D = (int)D; p.lengths = nullptr;
   return SLU_OK;
 }
 
@@ -1150,4 +1162,37 @@ extern "C" int slu_gru_seq_fwd_pool_bf16(const float* gx, const float* w_hh_fwd,
   if (out_planes)
     return H == 128 ? gru_bf_dispatch<128, 1>(nsplit, ki, seq_tiles, grid, st, p) : gru_bf_dispatch<64, 1>(nsplit, ki, seq_tiles, grid, st, p);
   return H == 128 ? gru_bf_dispatch<128, 2>(nsplit, ki, seq_tiles, grid, st, p) : gru_bf_dispatch<64, 2>(nsplit, ki, seq_tiles, grid, st, p);
+}
+
+// The LEN instantiations of gru_bf_fwd_kernel: bf16x3, gx given, fp32 output of every step, one sequence tile per
+// workgroup.  Everything is validated before the launch; no allocation, no synchronisation.
+extern "C" int slu_gru_seq_fwd_len_bf16(const float* gx, const float* w_hh_fwd, const float* w_hh_rev,
+                                        const float* b_hh_fwd, const float* b_hh_rev, const int32_t* lengths,
+                                        float* out, int64_t T, int64_t B, int64_t H, int64_t D, int nsplit,
+                                        void* stream) {
+  const char* who = "slu_gru_seq_fwd_len_bf16";
+  SLU_REQUIRE(gx, "%s: null gx", who);
+  SLU_REQUIRE(w_hh_fwd, "%s: null w_hh_fwd", who);
+  SLU_REQUIRE(b_hh_fwd, "%s: null b_hh_fwd", who);
+  SLU_REQUIRE(lengths, "%s: null lengths", who);
+  SLU_REQUIRE(out, "%s: null out", who);
+  if (D != 1 && D != 2) SLU_FAIL(SLU_ERR_UNSUPPORTED, "%s: D must be 1 or 2 (got %lld)", who, (long long)D);
+  SLU_REQUIRE(D == 1 || w_hh_rev, "%s: null w_hh_rev (D = 2)", who);
+  SLU_REQUIRE(D == 1 || b_hh_rev, "%s: null b_hh_rev (D = 2)", who);
+  if (nsplit != 3)
+    SLU_FAIL(SLU_ERR_UNSUPPORTED, "%s: the length-aware recurrence is instantiated for bf16x3 only (nsplit 3, got %d)", who, nsplit);
+  if (H != 64 && H != 128)
+    SLU_FAIL(SLU_ERR_UNSUPPORTED, "%s: hidden size %lld not instantiated (64, 128)", who, (long long)H);
+  GruBfParams p;
+  int rc = gru_bf_common(who, p, gx, w_hh_fwd, w_hh_rev, b_hh_fwd, b_hh_rev, nullptr, 0, 0, nullptr, nullptr, T, B, H, D,
+                         nsplit, false, 1);
+  if (rc) return rc;
+  SLU_REQUIRE(((uintptr_t)out & 15) == 0, "%s: out must be 16-byte aligned", who);
+  p.out = out; p.lengths = (const int*)lengths;
+  dim3 grid((unsigned)cdiv(B, 16), (unsigned)D);
+  hipStream_t st = (hipStream_t)stream;
+  if (H == 128) gru_bf_launch<128, 3, 0, 0, true>(grid, st, p);
+  else gru_bf_launch<64, 3, 0, 0, true>(grid, st, p);
+  SLU_CHECK_LAUNCH("gru_bf_fwd_kernel<LEN>");
+  return SLU_OK;
 }

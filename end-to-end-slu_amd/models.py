@@ -239,6 +239,21 @@ def mask_seq2seq_enabled():
     return v == "1"
 
 
+_MASK_FROZEN_MATH = ("fp32", "bf16x3")
+
+
+def mask_frozen_math_mode():
+    """SLU_MASK_FROZEN_MATH: the contraction arithmetic of FROZEN stages in every lengths=... call: "fp32" (default) — the
+    exact kernels, whatever SLU_FROZEN_MATH says; "bf16x3" — a stage with no trainable parameter whose input needs no
+    gradient runs its convolution / input projection / recurrence on the split-precision kernels (ops.wconv_fwd_bf16,
+    ops.gemm_a32, ops.gru_seq_fwd_len_bf16) where they take its shape, else its fp32 form.  A knob of its own: it does not
+    follow SLU_FROZEN_MATH, and f16x2 / auto are refused (the range guard is not wired through the length-aware path)."""
+    mode = os.environ.get("SLU_MASK_FROZEN_MATH", "fp32")
+    if mode not in _MASK_FROZEN_MATH:
+        raise ValueError("SLU_MASK_FROZEN_MATH=%r: expected one of %s" % (mode, sorted(_MASK_FROZEN_MATH)))
+    return mode
+
+
 def _refuse_seq2seq_lengths():
     """The refusal of a seq2seq model in a lengths=... call unless SLU_MASK_SEQ2SEQ=1 (a bad value of the knob is an error)."""
     if not mask_seq2seq_enabled():
@@ -985,13 +1000,15 @@ def _check_len_stages(stages):
 def _run_stages_len(stages, h, lengths, training=None):
     """Length-aware evaluation of `stages` (no dropout, no autograd): h = the first stage's input, whose frames at or
     beyond lengths[b] are zero; -> (output, its valid lengths).  The host computes every stage's valid lengths
-    (_stage_lengths) and sends them to the device in ONE int32 table.  Always the exact fp32 kernels — slu_wconv_fwd,
+    (_stage_lengths) and sends them to the device in ONE int32 table.  By default the exact fp32 kernels — slu_wconv_fwd,
     slu_gemm_f32, slu_gru_seq_fwd_len — whatever SLU_FROZEN_MATH says: both sides of the invariant (an utterance in a
-    padded batch / alone) then differ by summation order only.  A split-precision length-aware path does not exist.
+    padded batch / alone) then differ by summation order only.  SLU_MASK_FROZEN_MATH=bf16x3 (mask_frozen_math_mode) moves
+    the frozen stages' contractions to the split-precision kernels, stage by stage (_ConvStage / _RnnStage._len_split).
     training (None: the evaluation above; else the module's training flag): the masked training step — every stage through
     run_len_train, i.e. inside autograd where it has something to differentiate and with its dropout when `training`.  The
     table then also carries, behind the stages' rows, one row of input frames * channels for every conv block that follows
     a stage with a trainable parameter (what ops.ConvBlockLenFn masks the gradient of its input with)."""
+    mask_frozen_math_mode()          # a bad value of the knob is an error before any launch
     rows = [list(lengths)]
     for st in stages:
         if isinstance(st, _ConvStage):
@@ -1045,22 +1062,34 @@ class _ConvStage:
         """Valid frames of the block's output: ceil(conv_len / pool)."""
         return -(-self.conv_len(n) // self.pool)
 
+    def _len_split(self, h, c_in):
+        """SLU_MASK_FROZEN_MATH=bf16x3 and run()'s rule: no trainable parameter, nothing to differentiate, and a shape the
+        split-precision convolution takes (raw convolution: pool 1) — else this block stays on the exact fp32 kernel."""
+        if mask_frozen_math_mode() != "bf16x3" or h.requires_grad or any(q.requires_grad for q in self.parameters()):
+            return False
+        k_t = self.conv.Filt_dim if self.is_sinc else self.conv.kernel_size
+        return _ops.wconv_bf16_supported(c_in, self.conv.stride, 1, k_t, 3)
+
     def run_len(self, h, n_conv, time_major=None):
-        """Length-aware evaluation (exact fp32, no dropout): h = (B, T) waveform or channels-last (B, L, C) with a zero
+        """Length-aware evaluation (no dropout): h = (B, T) waveform or channels-last (B, L, C) with a zero
         tail, n_conv = int32 device lengths of the raw convolution's output.  The existing convolution call with pool 1,
         slope 1 and no abs (convolution + bias), then slu_pool_act_len_fwd: abs / max-pool over the valid frames /
-        activation, zero beyond — channels-last, or time-major on the last CNN block (time_major overrides that)."""
+        activation, zero beyond — channels-last, or time-major on the last CNN block (time_major overrides that).
+        Exact fp32, or (_len_split) the frozen block's convolution on the bf16x3 kernel with run()'s cached pack."""
         time_major = self.time_major if time_major is None else time_major
         with torch.no_grad():
             if h.dim() == 2:
                 h = h.unsqueeze(2)
             h = h.contiguous()
             B, l_in, c_in = h.shape
-            if self.is_sinc:
-                w, bias = self.conv.filters().view(self.conv.N_filt, 1, self.conv.Filt_dim), None
+            if self._len_split(h, c_in):
+                cache = self._frozen_cache(3)
+                w, bias = self._filters(cache)
+                raw = _ops.wconv_fwd_bf16(h, w, bias, B, l_in, c_in, self.conv.stride, False, 1, 1.0, False, 3,
+                                          pack_cache=cache["pack"])
             else:
-                w, bias = self.conv.weight.detach(), self.conv.bias.detach()
-            raw, _, _ = _ops.wconv_fwd(h, w, bias, B, l_in, c_in, self.conv.stride, False, 1, 1.0, False, False)
+                w, bias = self._filters()
+                raw, _, _ = _ops.wconv_fwd(h, w, bias, B, l_in, c_in, self.conv.stride, False, 1, 1.0, False, False)
             return _ops.pool_act_len_fwd(raw, n_conv, self.pool, self.do_abs, self.slope, time_major)
 
     def in_channels(self):
@@ -1111,6 +1140,19 @@ class _ConvStage:
             c = caches[key] = {"version": version, "filters": None, "pack": {}}
         return c
 
+    def _filters(self, cache=None):
+        """(w (C_out, C_in, k), bias or None) of the block outside autograd: the Sinc filterbank or the Conv1d parameters.
+        cache (a _frozen_cache entry, FROZEN blocks only): the filterbank is computed once per weight version and kept
+        there (not under capture: memory allocated then belongs to the graph)."""
+        if not self.is_sinc:
+            return self.conv.weight.detach(), self.conv.bias.detach()
+        filt = None
+        if cache is not None:
+            if cache.get("filters") is None and not torch.cuda.is_current_stream_capturing():
+                cache["filters"] = self.conv.filters()
+            filt = cache.get("filters")
+        return (filt if filt is not None else self.conv.filters()).view(self.conv.N_filt, 1, self.conv.Filt_dim), None
+
     def run(self, h, training, out_planes=False):
         """h: (B,T) for the first block, else channels-last (B,L,C).
         out_planes: the consumer is a frozen split-precision GRU layer — hand over bf16 planes (SplitAct) when this
@@ -1131,14 +1173,7 @@ class _ConvStage:
                 and _ops.wconv_bf16_supported(c_in, self.conv.stride, pool, k_t, nsplit)):
             with torch.no_grad():
                 cache = self._frozen_cache(nsplit)
-                if self.is_sinc:
-                    if cache.get("filters") is None and not torch.cuda.is_current_stream_capturing():
-                        cache["filters"] = self.conv.filters()
-                    filt = cache.get("filters")
-                    w = (filt if filt is not None else self.conv.filters()).view(self.conv.N_filt, 1, self.conv.Filt_dim)
-                    bias, do_abs = None, self.do_abs
-                else:
-                    w, bias, do_abs = self.conv.weight.detach(), self.conv.bias.detach(), self.do_abs
+                (w, bias), do_abs = self._filters(cache), self.do_abs
                 if isinstance(h, _ops.RowTable):       # a look-ahead super-batch read where its batches lie
                     x3, (B, l_in) = h, h.shape
                 else:
@@ -1203,27 +1238,52 @@ class _RnnStage:
         """Valid frames behind the layer's Downsample: ceil(n / factor) for every method (the GRU keeps n)."""
         return -(-n // self.factor)
 
+    def _len_split(self, xt):
+        """SLU_MASK_FROZEN_MATH=bf16x3 and GRU.run_time_major's rule: no trainable parameter, nothing to differentiate,
+        and a hidden size the split-precision length-aware recurrence takes — else this layer stays exact fp32."""
+        g = self.gru
+        return (mask_frozen_math_mode() == "bf16x3" and g.hidden_size in _ops.LEN_BF16_HIDDEN_SIZES
+                and not xt.requires_grad and not any(q.requires_grad for q in g.parameters()))
+
+    def _gx_len_split(self, x2, w_ih, b_ih):
+        """The frozen layer's input projection on bf16x3 (x split inside the kernel, W_ih packed once per weight version
+        as GRU.run_time_major does), or the exact GEMM where slu_gemm_bf16_a32 does not take the shape."""
+        g, N = self.gru, w_ih.shape[0]
+        if not _ops.gemm_a32_ok(x2, N, x2.shape[1]):
+            return _ops.gemm(x2, w_ih.detach().t(), b_ih.detach())
+        key = (3, w_ih.data_ptr(), w_ih._version)
+        if getattr(g, "_packed_ih", (None, None))[0] != key:
+            g._packed_ih = (key, _ops.gemm_bf16_pack(w_ih.detach(), 3))
+        return _ops.gemm_a32(x2, g._packed_ih[1], b_ih.detach(), N, 3)
+
     def run_len(self, xt, n_in):
-        """Length-aware evaluation (exact fp32, no dropout): xt time-major (T, B, I) with zero rows at t >= n_in[b],
+        """Length-aware evaluation (no dropout): xt time-major (T, B, I) with zero rows at t >= n_in[b],
         n_in int32 device lengths -> (ceil(T / factor), B, D*H), zero beyond ceil(n / factor).  slu_gemm_f32 (the padded
-        rows' projections are b_ih: never read), slu_gru_seq_fwd_len, slu_seq_pool_len_fwd."""
+        rows' projections are b_ih: never read), slu_gru_seq_fwd_len, slu_seq_pool_len_fwd — or (_len_split) the projection
+        and the recurrence of a frozen layer on bf16x3: slu_gemm_bf16_a32, slu_gru_seq_fwd_len_bf16."""
         g = self.gru
         with torch.no_grad():
             xt = xt.contiguous()
             T, B, I = xt.shape
             H, D = g.hidden_size, 2 if g.bidirectional else 1
             w_ih, b_ih = g._stacked_ih()
-            gx = _ops.gemm(xt.view(T * B, I), w_ih.detach().t(), b_ih.detach())
             rev = (g.weight_hh_l0_reverse.detach(), g.bias_hh_l0_reverse.detach()) if g.bidirectional else (None, None)
-            out = _ops.gru_seq_fwd_len(gx, g.weight_hh_l0.detach(), rev[0], g.bias_hh_l0.detach(), rev[1], n_in, T, B, H, D)
+            if self._len_split(xt):
+                gx = self._gx_len_split(xt.view(T * B, I), w_ih, b_ih)
+                out = _ops.gru_seq_fwd_len_bf16(gx, g.weight_hh_l0.detach(), rev[0], g.bias_hh_l0.detach(), rev[1], n_in, T, B,
+                                                H, D)
+            else:
+                gx = _ops.gemm(xt.view(T * B, I), w_ih.detach().t(), b_ih.detach())
+                out = _ops.gru_seq_fwd_len(gx, g.weight_hh_l0.detach(), rev[0], g.bias_hh_l0.detach(), rev[1], n_in, T, B, H, D)
             if self.factor > 1:
                 out = _ops.seq_pool_len_fwd(out, n_in, self.method, self.factor)
             return out
 
     def run_len_train(self, xt, n_in, training):
-        """The layer inside a masked training step (exact fp32): xt and n_in as run_len, dropout when `training` (the dense
+        """The layer inside a masked training step: xt and n_in as run_len, dropout when `training` (the dense
         batch's masks: _dropout_args).  A layer with a trainable parameter, or behind one (xt requires a gradient), runs as
-        ops.GRULayerLenFn; a frozen one runs the same kernels outside autograd, without a reserve."""
+        ops.GRULayerLenFn (exact fp32); a frozen one runs the same kernels outside autograd, without a reserve — or, as in
+        run_len, its projection and recurrence on bf16x3 (the dropout + pooling launch, and so every draw, is the same)."""
         g = self.gru
         p, mask, seed, offset = _dropout_args(self.drop_name, self.site, self.p, training)
         w_ih, b_ih = g._stacked_ih()
@@ -1239,10 +1299,15 @@ class _RnnStage:
             xt = xt.contiguous()
             T, B, I = xt.shape
             H, D = g.hidden_size, 2 if g.bidirectional else 1
-            gx = _ops.gemm(xt.view(T * B, I), w_ih.detach().t(), b_ih.detach())
             rev = (g.weight_hh_l0_reverse.detach(), g.bias_hh_l0_reverse.detach()) if g.bidirectional else (None, None)
-            out, _ = _ops.gru_seq_fwd_len_rsv(gx, g.weight_hh_l0.detach(), rev[0], g.bias_hh_l0.detach(), rev[1], n_in, T, B,
-                                              H, D, False)
+            if self._len_split(xt):
+                gx = self._gx_len_split(xt.view(T * B, I), w_ih, b_ih)
+                out = _ops.gru_seq_fwd_len_bf16(gx, g.weight_hh_l0.detach(), rev[0], g.bias_hh_l0.detach(), rev[1], n_in, T, B,
+                                                H, D)
+            else:
+                gx = _ops.gemm(xt.view(T * B, I), w_ih.detach().t(), b_ih.detach())
+                out, _ = _ops.gru_seq_fwd_len_rsv(gx, g.weight_hh_l0.detach(), rev[0], g.bias_hh_l0.detach(), rev[1], n_in, T,
+                                                  B, H, D, False)
             if p > 0.0 or self.factor > 1:
                 offset, offset_dev, sub_batch = offset if isinstance(offset, tuple) else (offset, None, 0)
                 assert sub_batch == 0

@@ -88,6 +88,7 @@ SIGNATURES = {
     "slu_pool_act_len_fwd": (c_int, [vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_int, c_f32, c_i64, c_i64, vp]),
     "slu_gru_seq_fwd_len": (c_int, [vp, vp, vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, vp]),
     "slu_seq_pool_len_fwd": (c_int, [vp, vp, vp, c_int, c_i64, c_i64, c_i64, c_i64, vp]),
+    "slu_gru_seq_fwd_len_bf16": (c_int, [vp, vp, vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_int, vp]),
     "slu_cls_maxpool_len_fwd": (c_int, [vp, vp, vp, vp, vp, ctypes.POINTER(c_i64), c_i64, vp, vp, vp, vp, vp, c_i64, c_i64,
                                         c_i64, vp]),
     "slu_gru_seq_fwd_len_rsv": (c_int, [vp, vp, vp, vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, vp]),

@@ -1308,6 +1308,25 @@ def gru_seq_fwd_len(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lengths, T, B, H, D):
     return out
 
 
+LEN_BF16_HIDDEN_SIZES = (64, 128)          # hidden sizes slu_gru_seq_fwd_len_bf16 takes (the split-precision recurrence)
+
+
+def gru_seq_fwd_len_bf16(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lengths, T, B, H, D):
+    """gru_seq_fwd_len on the split-precision recurrence (bf16x3, one sequence tile per workgroup) -> out (T, B, D*H):
+    zero at t >= lengths[b], elsewhere bit-equal to gru_seq_fwd_bf16(nsplit=3, seq_tiles=1) on the truncated sequence."""
+    L = _lib.load()
+    _len_check(lengths, B, gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r)
+    if H not in LEN_BF16_HIDDEN_SIZES:
+        raise ValueError("lengths: hidden size %d has no split-precision length-aware recurrence kernel (supported: %s)"
+                         % (H, ", ".join(map(str, LEN_BF16_HIDDEN_SIZES))))
+    gx = _f32c(gx, "gx")
+    out = torch.empty(T, B, D * H, dtype=torch.float32, device=gx.device)
+    _lib.check(L.slu_gru_seq_fwd_len_bf16(gx.data_ptr(), w_hh_f.data_ptr(), _ptr(w_hh_r), b_hh_f.data_ptr(), _ptr(b_hh_r),
+                                          lengths.data_ptr(), out.data_ptr(), T, B, H, D, 3, _stream()),
+               "slu_gru_seq_fwd_len_bf16")
+    return out
+
+
 def seq_pool_len_fwd(x, lengths, method, factor):
     """Downsample(method, factor) of a time-major (T, B, C) activation with per-sequence lengths."""
     L = _lib.load()

@@ -621,6 +621,21 @@ int slu_cls_maxpool_len_fwd(const float* h, const float* weight, const float* bi
                             int32_t* argmax_t, int64_t* pred, float* row_stats, float* loss_acc, int64_t T, int64_t B,
                             int64_t C, void* stream);
 
+/* slu_gru_seq_fwd_len_bf16 — added under ABI 10 (one new entry point; nothing existing changed, so the version number
+ * stays): slu_gru_seq_fwd_len's definition on the split-precision recurrence (bf16x3: W_hh and h_{t-1} as three bf16
+ * terms, bf16 MFMA, fp32 accumulation), for frozen layers.  Nothing new is defined, only a second arithmetic:
+ *   out (T, B, D*H) is exactly 0.0f at t >= n_b, and at t < n_b it equals, bit for bit, what
+ *   slu_gru_seq_fwd_bf16(nsplit = 3, seq_tiles = 1, no reserve, no fused input) writes for sequence b truncated to n_b
+ *   frames (n_b = lengths[b] clamped into [1, T]); no gx value at t >= n_b reaches any result (NaN there is harmless).
+ * Validated before any launch: a NULL gx / w_hh_fwd / b_hh_fwd / lengths / out (or reverse weights with D = 2) is
+ * SLU_ERR_INVALID_ARG and slu_last_error() names the null argument; H outside {64, 128}, nsplit != 3 and D outside
+ * {1, 2} are SLU_ERR_UNSUPPORTED.  gx, out and the biases 16-byte aligned, as slu_gru_seq_fwd_bf16 asks.  No allocation,
+ * no synchronisation.  Not built: the Dropout + avg-pool epilogues, two sequence tiles per workgroup, the fused
+ * K <= 64 input projection, the reserve-writing kernel, nsplit 1 / 2.                                                */
+int slu_gru_seq_fwd_len_bf16(const float* gx, const float* w_hh_fwd, const float* w_hh_rev,
+                             const float* b_hh_fwd, const float* b_hh_rev, const int32_t* lengths,
+                             float* out, int64_t T, int64_t B, int64_t H, int64_t D, int nsplit, void* stream);
+
 /* -------- masked training: the lengths through BPTT and the intent head — added under ABI 10 (five new entry points;
  * nothing existing changed, so the version number stays).  The definition is this library's own:
  *   forward   exactly the length-aware definition above, now also with dropout: element (t, b, c) of a dropout site takes

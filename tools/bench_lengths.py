@@ -3,8 +3,10 @@ B = 64 utterances of 3 s at the reference architecture, frozen encoder, HIP even
 
   python tools/bench_lengths.py [--out profiles/lengths_predict.json]
 
-Three numbers: the length-aware path (always exact fp32 kernels), the plain path under SLU_FROZEN_MATH=fp32, and the plain
-path on the default arithmetic.  The environment variable is read per call, so one process measures all three."""
+Four numbers: the length-aware path on the exact fp32 kernels (SLU_MASK_FROZEN_MATH unset), the same call with
+SLU_MASK_FROZEN_MATH=bf16x3 (the frozen stages on the split-precision kernels), the plain path under SLU_FROZEN_MATH=fp32, and
+the plain path on the default arithmetic.  The environment variables are read per call, so one process measures all four.
+--batch 256 is the larger shape on record (profiles/lengths_predict_bf16x3.json)."""
 import argparse
 import json
 import os
@@ -60,7 +62,11 @@ def main():
     res = {"B": B, "T": T, "device": torch.cuda.get_device_name(0), "lengths_min_max": [min(lengths), max(lengths)]}
     with torch.no_grad():
         os.environ["SLU_FROZEN_MATH"] = "fp32"
+        os.environ.pop("SLU_MASK_FROZEN_MATH", None)
         res["lengths_fp32"] = timed(lambda: model.predict_intents(x, lengths))
+        os.environ["SLU_MASK_FROZEN_MATH"] = "bf16x3"
+        res["lengths_bf16x3"] = timed(lambda: model.predict_intents(x, lengths))
+        os.environ.pop("SLU_MASK_FROZEN_MATH")
         res["plain_fp32"] = timed(lambda: model.predict_intents(x))
         os.environ.pop("SLU_FROZEN_MATH")
         res["plain_default"] = timed(lambda: model.predict_intents(x))
