@@ -235,6 +235,17 @@ def mask_padding_enabled():
     return v == "1"
 
 
+def mask_asr_enabled():
+    """SLU_MASK_ASR: "0" (default) — ASR batches are (x, y_phoneme, y_word), also under SLU_MASK_PADDING=1; "1" —
+    CollateWavsASR adds the snippets' own sample counts.  Needs SLU_MASK_PADDING=1."""
+    v = os.environ.get("SLU_MASK_ASR", "0")
+    if v not in ("0", "1"):
+        raise ValueError("SLU_MASK_ASR=%r: expected 0 or 1" % (v,))
+    if v == "1" and not mask_padding_enabled():
+        raise ValueError("SLU_MASK_ASR=1 needs SLU_MASK_PADDING=1: the lengths come from the collate function")
+    return v == "1"
+
+
 class CollateWavsSLU:
     """list of (waveform, [action, object, location]) -> (x (B, T_max) float32 zero-padded at the end,
     y_intent (B, 3) int64), as reference data.py:344-376.  seq2seq: the labels are <sos> ... <eos> index
@@ -545,19 +556,36 @@ def _strip_stress(mark):
 class CollateWavsASR:
     """list of (waveform, phoneme labels, word labels) -> (x (B,T_max) float32 zero-padded, y_phoneme
     (B,U_p) int64, y_word (B,U_w) int64, both padded with the ignore index -1) — reference data.py:511-545.
-    Assembled in one buffer per tensor (pinned by the DataLoader)."""
+    Assembled in one buffer per tensor (pinned by the DataLoader).
+    Opt-in (SLU_MASK_ASR=1, with SLU_MASK_PADDING=1; or mask_asr=True): also return the snippets' own sample counts, (x,
+    y_phoneme, y_word, lengths int32 (B)), so that PretrainedModel.forward(lengths=...) can skip the padded frames.
+    pad_multiple (samples; 0, the default and what ASRDataset uses: none) rounds T_max up to a multiple, and the label
+    tracks follow by the dataset's own rule, one label per factors = (phone, word downsample factor) samples: with lengths
+    a masked step must not depend on how far its batch is padded, and this is how a test pads it further."""
+
+    def __init__(self, mask_asr=None, pad_multiple=0, factors=None):
+        self.mask_asr = mask_asr_enabled() if mask_asr is None else bool(mask_asr)
+        self.pad_multiple = int(pad_multiple)
+        if self.pad_multiple > 1 and factors is None:
+            raise ValueError("CollateWavsASR: pad_multiple needs factors = (phone_downsample_factor, word_downsample_factor)")
+        self.factors = factors
 
     def __call__(self, batch):
         n = len(batch)
         T = max(len(b[0]) for b in batch)
         Up = max(len(b[1]) for b in batch)
         Uw = max(len(b[2]) for b in batch)
+        if self.pad_multiple > 1:
+            T = -(-T // self.pad_multiple) * self.pad_multiple
+            Up, Uw = max(Up, -(-T // self.factors[0])), max(Uw, -(-T // self.factors[1]))
         x = _pad_waveforms([b[0] for b in batch], T)
         yp = torch.full((n, Up), -1, dtype=torch.int64)
         yw = torch.full((n, Uw), -1, dtype=torch.int64)
         for i, (xi, pi, wi) in enumerate(batch):
             yp[i, :len(pi)] = torch.as_tensor(np.asarray(pi, dtype=np.int64))
             yw[i, :len(wi)] = torch.as_tensor(np.asarray(wi, dtype=np.int64))
+        if self.mask_asr:
+            return x, yp, yw, torch.tensor([len(b[0]) for b in batch], dtype=torch.int32)
         return x, yp, yw
 
 

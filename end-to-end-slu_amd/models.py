@@ -262,6 +262,16 @@ def _refuse_seq2seq_lengths():
                          "lengths")
 
 
+def _refuse_trainable_cnn_lengths(cnn_stages):
+    """The refusal of a trainable CNN block in a masked step unless SLU_MASK_TRAIN_CNN=1 (a bad value of the knob is an error)."""
+    if not mask_train_cnn_enabled():
+        for st in cnn_stages:
+            if any(q.requires_grad for q in st.parameters()):
+                raise ValueError("lengths: a trainable CNN block (the unfreezing has reached the convolutions) runs "
+                                 "length-aware only with SLU_MASK_TRAIN_CNN=1 (off by default): setting it is the next step; or "
+                                 "freeze the CNN blocks, or train without lengths")
+
+
 def _require_device(t):
     if not t.is_cuda:
         raise _lib.SluHipError("the HIP kernels are the only compute path of this package: move the "
@@ -997,7 +1007,7 @@ def _check_len_stages(stages):
                                 ", ".join(map(str, _ops.LEN_HIDDEN_SIZES))))
 
 
-def _run_stages_len(stages, h, lengths, training=None):
+def _run_stages_len(stages, h, lengths, training=None, pack=False):
     """Length-aware evaluation of `stages` (no dropout, no autograd): h = the first stage's input, whose frames at or
     beyond lengths[b] are zero; -> (output, its valid lengths).  The host computes every stage's valid lengths
     (_stage_lengths) and sends them to the device in ONE int32 table.  By default the exact fp32 kernels — slu_wconv_fwd,
@@ -1007,7 +1017,9 @@ def _run_stages_len(stages, h, lengths, training=None):
     training (None: the evaluation above; else the module's training flag): the masked training step — every stage through
     run_len_train, i.e. inside autograd where it has something to differentiate and with its dropout when `training`.  The
     table then also carries, behind the stages' rows, one row of input frames * channels for every conv block that follows
-    a stage with a trainable parameter (what ops.ConvBlockLenFn masks the gradient of its input with)."""
+    a stage with a trainable parameter (what ops.ConvBlockLenFn masks the gradient of its input with).
+    pack: a frame head follows (ops.FrameHeadLenFn) — the table's last row is the exclusive prefix sum of the output's
+    valid lengths (ops.frame_pack_plan) and the result gains a fourth entry, (that row on the device, N = their sum)."""
     mask_frozen_math_mode()          # a bad value of the knob is an error before any launch
     rows = [list(lengths)]
     for st in stages:
@@ -1025,6 +1037,9 @@ def _run_stages_len(stages, h, lengths, training=None):
             rows.append([n * st.in_channels() for n in rows[k]])
         grad_above = grad_above or any(q.requires_grad for q in st.parameters())
         k += 2 if isinstance(st, _ConvStage) else 1
+    if pack:
+        offsets, n_total = _ops.frame_pack_plan(rows[n_rows - 1])
+        rows.append(offsets)
     table = torch.tensor(rows, dtype=torch.int32).to(h.device, non_blocking=True)
     k = 0
     for st in stages:
@@ -1034,6 +1049,8 @@ def _run_stages_len(stages, h, lengths, training=None):
         else:
             h = st.run_len(h, table[k]) if training is None else st.run_len_train(h, table[k], training)
         k += 2 if isinstance(st, _ConvStage) else 1
+    if pack:
+        return h, rows[n_rows - 1], table[k], (table[len(rows) - 1], n_total)
     return h, rows[n_rows - 1], table[k]
 
 
@@ -1539,11 +1556,16 @@ class PretrainedModel(torch.nn.Module):
         return self.run_stages(x, 0, len(self._stages()))
 
     # -- reference API --------------------------------------------------------------------------
-    def forward(self, x, y_phoneme, y_word, rng_step=None):
+    def forward(self, x, y_phoneme, y_word, rng_step=None, *, lengths=None):
         """x (B,T), y_phoneme (B,T'), y_word (B,T'') -> (phoneme_loss, word_loss, phoneme_acc,
         word_acc); cross-entropy ignores label -1 (reference models.py:291-331).
         rng_step (not in the reference): the dropout stream index of this forward — None = the next
-        one, or a 1-element int64 CUDA tensor holding step*16 (hipGraph-captured steps)."""
+        one, or a 1-element int64 CUDA tensor holding step*16 (hipGraph-captured steps).
+        lengths (not in the reference; None: the call as it was): the utterances' sample counts, each in [1, T] -> the
+        masked pre-training step (_forward_len): a frame counts iff its label is not -1 and it lies inside its utterance,
+        and losses and gradients are the kept-frame-weighted mean of what each x[b:b+1, :lengths[b]] gives run alone."""
+        if lengths is not None:
+            return self._forward_len(x, y_phoneme, y_word, lengths, rng_step)
         x, y_phoneme, y_word = self._to_device(x, y_phoneme, y_word)
         if torch.is_tensor(rng_step):
             _DropoutState.current_dev = rng_step
@@ -1563,7 +1585,84 @@ class PretrainedModel(torch.nn.Module):
         finally:
             _DropoutState.current_dev = None
 
-    def compute_posteriors(self, x):
+    def _len_plan(self, x, lengths, y_phoneme=None, y_word=None):
+        """Host side of a lengths=... call of this model, before any launch: -> (host lengths, phoneme-side stages, word
+        stages — none for pretraining_type 1 in a training call).  Refuses a bad batch shape, bad lengths, a hidden size
+        without a length-aware recurrence and labels that do not have the dense call's (B, T') / (B, T'') shapes."""
+        if x.dim() != 2:
+            raise ValueError("lengths: expected a (B, T) waveform batch")
+        B, T = x.shape
+        host = _host_lengths(lengths, B, T)
+        first = self._cnn_stages + self._phone_stages
+        word = list(self._word_stages) if (y_phoneme is None or self.pretraining_type != 1) else []
+        _check_len_stages(first + word)
+        frames = _stage_lengths(first + word, [T])
+        for y, name, t_out in ((y_phoneme, "y_phoneme", frames[len(first) - 1][0]),
+                               (y_word if word else None, "y_word", frames[-1][0])):
+            if y is not None and (y.dim() != 2 or y.shape[0] != B or y.shape[1] != t_out or y.dtype != torch.int64):
+                raise ValueError("lengths: %s must be int64 of shape (%d, %d), the dense call's, got %s %s"
+                                 % (name, B, t_out, y.dtype, tuple(y.shape)))
+        return host, first, word
+
+    def _forward_len(self, x, y_phoneme, y_word, lengths, rng_step):
+        """forward with per-utterance lengths (DESIGN.md section 7 "Lengths through ASR pre-training"): the waveform tail
+        is zeroed, the CNN blocks and the phoneme layers run length-aware (_run_stages_len, as Model._forward_len: frozen
+        stages outside autograd, trainable ones as ops.*LenFn), the phoneme head is ops.FrameHeadLenFn on the packed valid
+        frames; the phoneme features then feed the word layers and their head the same way, and autograd sums the two
+        gradients of the phoneme features.  In train() mode every dropout site draws the dense batch's masks.  Everything
+        that can be refused is refused here, on the host, before the first launch."""
+        if torch.is_tensor(rng_step):
+            raise ValueError("lengths: captured steps (a device-resident rng_step) are not supported")
+        host, first, word = self._len_plan(x, lengths, y_phoneme, y_word)
+        _refuse_trainable_cnn_lengths(self._cnn_stages)
+        x, y_phoneme, y_word = self._to_device(x, y_phoneme, y_word)
+        self._cnn_stages[-1].time_major = True
+        _DropoutState.current = next_rng_step() if rng_step is None else rng_step
+        with torch.no_grad():
+            x = _ops.pcm16_to_f32(x) if x.dtype == torch.int16 else x.float()
+            dev_len = torch.tensor(host, dtype=torch.int32).to(x.device, non_blocking=True)
+            x = _ops.mask_rows_len(x, dev_len)
+        ph_tm, n_p, n_p_dev, (off_p, rows_p) = _run_stages_len(first, x, host, training=self.training, pack=True)
+        pl = self.phoneme_linear
+        phoneme_loss, phoneme_acc = _ops.FrameHeadLenFn.apply(ph_tm, n_p_dev.contiguous(), off_p.contiguous(), rows_p,
+                                                              pl.weight, pl.bias, y_phoneme)
+        if self.pretraining_type == 1:
+            return phoneme_loss, torch.tensor([0.]), phoneme_acc, torch.tensor([0.])
+        wd_tm, _, n_w_dev, (off_w, rows_w) = _run_stages_len(word, ph_tm, n_p, training=self.training, pack=True)
+        wl = self.word_linear
+        word_loss, word_acc = _ops.FrameHeadLenFn.apply(wd_tm, n_w_dev.contiguous(), off_w.contiguous(), rows_w,
+                                                        wl.weight, wl.bias, y_word)
+        return phoneme_loss, word_loss, phoneme_acc, word_acc
+
+    def _posteriors_len(self, x, lengths):
+        """compute_posteriors with per-utterance lengths: the length-aware evaluation of compute_features(x, lengths), the two
+        Linear layers on the packed valid frames only, and one scatter each that writes the zeros beyond them."""
+        if self.training:
+            raise ValueError("lengths: the length-aware path is inference only (dropout is not applied): call eval() first")
+        host, first, word = self._len_plan(x, lengths)
+        (x,) = self._to_device(x)
+        self._cnn_stages[-1].time_major = True
+        with torch.no_grad():
+            x = _ops.pcm16_to_f32(x) if x.dtype == torch.int16 else x.float()
+            dev_len = torch.tensor(host, dtype=torch.int32).to(x.device, non_blocking=True)
+            x = _ops.mask_rows_len(x, dev_len)
+            ph_tm, n_p, n_p_dev, pack_p = _run_stages_len(first, x, host, pack=True)
+            wd_tm, _, n_w_dev, pack_w = _run_stages_len(word, ph_tm, n_p, pack=True)
+
+            def head(lin, h_tm, n_dev, pack):
+                T, B, _ = h_tm.shape
+                n_dev, off = n_dev.contiguous(), pack[0].contiguous()
+                hp, _ = _ops.frame_pack_len(h_tm, None, n_dev, off, pack[1])
+                out = _ops.gemm(hp, lin.weight.detach().t(), lin.bias.detach())
+                return _ops.frame_unpack_len(out, n_dev, off, T, B).transpose(0, 1)
+            return head(self.phoneme_linear, ph_tm, n_p_dev, pack_p), head(self.word_linear, wd_tm, n_w_dev, pack_w)
+
+    def compute_posteriors(self, x, lengths=None):
+        """(B,T) waveform -> (phoneme logits (B,T',num_phonemes), word logits (B,T'',vocabulary_size)).
+        lengths (not in the reference; None: the call as it was): the utterances' sample counts -> row b's logits at frames
+        t < n[b] (stage_lengths) are those of x[b:b+1, :lengths[b]] run alone, exactly 0 at and beyond n[b] (eval mode only)."""
+        if lengths is not None:
+            return self._posteriors_len(x, lengths)
         (x,) = self._to_device(x)
         _DropoutState.current = next_rng_step()
         ph_tm = self._phoneme_features_tm(x)
@@ -1832,12 +1931,7 @@ class Model(torch.nn.Module):
         _check_len_stages(stages)
         if self.augment and self.training:
             raise ValueError("lengths: augment=True is not supported (the augmentation moves the utterances' ends)")
-        if not mask_train_cnn_enabled():
-            for st in pm._cnn_stages:
-                if any(q.requires_grad for q in st.parameters()):
-                    raise ValueError("lengths: a trainable CNN block (the unfreezing has reached the convolutions) runs "
-                                     "length-aware only with SLU_MASK_TRAIN_CNN=1 (off by default): setting it is the next step; or "
-                                     "freeze the CNN blocks, or train without lengths")
+        _refuse_trainable_cnn_lengths(pm._cnn_stages)
         (x,) = pm._to_device(x)
         pm._cnn_stages[-1].time_major = True
         _DropoutState.current = next_rng_step() if rng_step is None else rng_step

@@ -105,6 +105,8 @@ SIGNATURES = {
                                       c_i64, c_i64, vp]),
     "slu_attention_len_bwd": (c_int, [vp, c_i64, c_i64, vp, c_i64, c_i64, vp, c_i64, vp, c_i64, vp, vp, vp, vp, c_i64, vp,
                                       c_f32, c_i64, c_i64, c_i64, c_i64, vp]),
+    "slu_frame_pack_len": (c_int, [vp, vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_i64, vp]),
+    "slu_frame_unpack_len": (c_int, [vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, vp]),
     "slu_comm_version": (c_int, []),
     "slu_comm_unique_id": (c_int, [vp]),
     "slu_comm_init": (c_int, [vp, vp, c_i64, c_i64]),

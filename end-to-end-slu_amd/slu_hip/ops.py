@@ -1616,6 +1616,109 @@ class FrameHeadFn(torch.autograd.Function):
         return dh, dW, db, None
 
 
+def frame_pack_plan(lengths):
+    """Host packing plan of a head's valid frames: lengths (B valid frame counts) -> (offsets, N): offsets = exclusive
+    prefix sum (utterance b's frames are packed rows offsets[b] .. offsets[b] + lengths[b] - 1), N = their sum."""
+    offsets, n = [], 0
+    for v in lengths:
+        offsets.append(n)
+        n += int(v)
+    return offsets, n
+
+
+def _pack_args(lengths, offsets, n_total, T, B):
+    _len_ok(lengths, B)
+    if (not torch.is_tensor(offsets) or offsets.dtype != torch.int32 or not offsets.is_cuda or offsets.dim() != 1
+            or offsets.numel() != B or not offsets.is_contiguous()):
+        raise TypeError("offsets must be a contiguous int32 CUDA tensor of %d entries" % B)
+    if not 1 <= n_total <= T * B:
+        raise ValueError("lengths: %d packed rows for %d frames" % (n_total, T * B))
+
+
+def frame_pack_len(h, y, lengths, offsets, n_total):
+    """h time-major (T, B, C) fp32, y (B, U >= T) int64 or None, lengths / offsets int32 CUDA (B), n_total = sum of the
+    lengths (host) -> (hp (n_total, C), yp (n_total) or None): row offsets[b] + t = h[t, b], y[b, t] for t < lengths[b].
+    Frames at or beyond lengths[b] are never read."""
+    L = _lib.load()
+    h = _f32c(h, "h")
+    T, B, C = h.shape
+    _pack_args(lengths, offsets, n_total, T, B)
+    yp = None
+    if y is not None:
+        if y.dtype != torch.int64 or y.dim() != 2 or y.shape[0] != B or y.shape[1] < T or not y.is_cuda:
+            raise TypeError("frame_pack_len: y must be an int64 CUDA tensor of shape (B, U >= T)")
+        y = y.contiguous()
+        yp = torch.empty(n_total, dtype=torch.int64, device=h.device)
+    hp = torch.empty(n_total, C, dtype=torch.float32, device=h.device)
+    _lib.check(L.slu_frame_pack_len(h.data_ptr(), _ptr(y), lengths.data_ptr(), offsets.data_ptr(), hp.data_ptr(), _ptr(yp),
+                                    T, B, C, 0 if y is None else y.shape[1], n_total, _stream()), "slu_frame_pack_len")
+    return hp, yp
+
+
+def frame_unpack_len(src, lengths, offsets, T, B, out=None):
+    """src (N, C) packed rows -> (T, B, C) time-major: src[offsets[b] + t] where t < lengths[b], exactly 0 elsewhere (every
+    element written; out: write into this (T, B, C) fp32 tensor, which may be a 16-byte misaligned view)."""
+    L = _lib.load()
+    if src.dtype != torch.float32 or not src.is_cuda or src.dim() != 2 or not src.is_contiguous():
+        raise TypeError("frame_unpack_len: src must be a contiguous float32 CUDA tensor (N, C)")
+    N, C = src.shape
+    _pack_args(lengths, offsets, N, T, B)
+    if out is None:
+        out = torch.empty(T, B, C, dtype=torch.float32, device=src.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (T, B, C) or not out.is_contiguous() or not out.is_cuda:
+        raise TypeError("frame_unpack_len: out must be a contiguous float32 CUDA tensor (T, B, C)")
+    _lib.check(L.slu_frame_unpack_len(src.data_ptr(), lengths.data_ptr(), offsets.data_ptr(), out.data_ptr(), T, B, C, N,
+                                      _stream()), "slu_frame_unpack_len")
+    return out
+
+
+class FrameHeadLenFn(torch.autograd.Function):
+    """FrameHeadFn over the valid frames of a padded batch (PretrainedModel.forward(lengths=...)): h time-major (T, B, C),
+    lengths / offsets int32 CUDA (B) = valid frames of h per row and their exclusive prefix sum, n_total = their sum (a
+    host int: no device read), y (B, U >= T) int64.  slu_frame_pack_len gathers the N = n_total valid rows (utterance-major)
+    and their labels; the Linear, slu_frame_ce_fwd (ignore index -1) and the backward GEMMs are FrameHeadFn's, on N rows
+    instead of T * B; slu_frame_unpack_len scatters d h back, exactly 0 at padded frames.  A frame is kept iff its label
+    is not -1 and t < lengths[b]: labels beyond the lengths are never read.  Returns (loss, acc)."""
+
+    @staticmethod
+    def forward(ctx, h, lengths, offsets, n_total, weight, bias, y):
+        L = _lib.load()
+        T, B, C = h.shape
+        V = weight.shape[0]
+        hp, yp = frame_pack_len(h, y, lengths, offsets, n_total)
+        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[4] or ctx.needs_input_grad[5]
+        logits = gemm_nt(hp, weight, bias, bf16_ok=False)          # (N, V): valid frames only
+        row_stats = torch.empty(2 * n_total, dtype=torch.float32, device=h.device)
+        out3 = torch.empty(3, dtype=torch.float32, device=h.device)
+        _lib.check(L.slu_frame_ce_fwd(logits.data_ptr(), yp.data_ptr(), n_total, V, -1, int(need),
+                                      row_stats.data_ptr(), out3.data_ptr(), _stream()), "slu_frame_ce_fwd")
+        if need:
+            ctx.save_for_backward(hp, weight, logits, lengths, offsets)
+        ctx.set_materialize_grads(False)
+        ctx.shape = (T, B, C)
+        acc = out3[1]
+        ctx.mark_non_differentiable(acc)
+        return out3[0], acc
+
+    @staticmethod
+    def backward(ctx, d_loss, _d_acc):
+        if d_loss is None:
+            return None, None, None, None, None, None, None
+        hp, weight, d_logits, lengths, offsets = ctx.saved_tensors
+        T, B, C = ctx.shape
+        g = d_loss.float()
+        dhp = dW = db = None
+        if ctx.needs_input_grad[0]:
+            dhp = gemm_nt(d_logits, weight.t(), grad=True, bf16_ok=False)
+        if ctx.needs_input_grad[4]:
+            dW = _wgrad(d_logits, hp, None, bf16_ok=False)
+        if ctx.needs_input_grad[5]:
+            db = colsum(d_logits)
+        scale_multi([t for t in (dhp, dW, db) if t is not None], g)     # d loss upstream (a device scalar), one launch
+        dh = frame_unpack_len(dhp, lengths, offsets, T, B) if dhp is not None else None
+        return dh, None, None, None, dW, db, None
+
+
 class SincBlockFn(torch.autograd.Function):
     """SincLayer -> Abs -> MaxPool1d(ceil) -> LeakyReLU  (models.py:77-110, :163-168, :205, :211).
     x (B,T) -> (B, L_out, N_filt) channels-last, or (L_out, B, N_filt) when time_major."""

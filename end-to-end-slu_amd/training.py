@@ -24,6 +24,7 @@ import torch
 from tqdm import tqdm
 
 from data import SLUDataset, ASRDataset, mask_padding_enabled as data_mask_padding_enabled
+from data import mask_asr_enabled
 from models import PretrainedModel, Model, next_rng_step
 from slu_hip import dp, ops, pipeline
 
@@ -171,12 +172,13 @@ class _drop_lengths:
     (Model.eval_group(lengths=...)) and, with SLU_MASK_TRAIN=1, so does training — then this wrapper is not applied.
     Keeps the loader's len() (the look-ahead pipeline sizes its first super-batches by the run's length)."""
 
-    def __init__(self, loader):
+    def __init__(self, loader, keep=2):
         self.loader = loader
+        self.keep = keep                  # 3 for ASR batches: (x, y_phoneme, y_word[, lengths]) of SLU_MASK_ASR=1
 
     def __iter__(self):
         for batch in self.loader:
-            yield tuple(batch[:2]) if len(batch) == 3 else batch
+            yield tuple(batch[:self.keep]) if len(batch) == self.keep + 1 else batch
 
     def __len__(self):
         return len(self.loader)           # TypeError for a generator, as on the loader itself
@@ -275,6 +277,7 @@ class Trainer:
         self.model = model
         self.config = config
         mask_train_enabled()                     # SLU_MASK_TRAIN=1 without SLU_MASK_PADDING=1 fails here, not at the first step
+        mask_asr_enabled()                       # and so does SLU_MASK_ASR=1
         if isinstance(self.model, PretrainedModel):
             self.lr = config.pretraining_lr
             self.checkpoint_path = os.path.join(self.config.folder, "pretraining")
@@ -374,8 +377,12 @@ class Trainer:
         """-> ([metric tensors in log order], loss to back-propagate).  rng_step: None = the model draws the
         next dropout-stream index itself (the plain reference-style call), else the index to use."""
         if asr:
-            x, y_phoneme, y_word = batch
-            if rng_step is None:
+            # (x, y_phoneme, y_word, lengths): SLU_MASK_ASR=1 — evaluation, and the masked steps of SLU_MASK_TRAIN=1 (_iterate)
+            extra = {"lengths": batch[3]} if len(batch) == 4 else {}
+            x, y_phoneme, y_word = batch[:3]
+            if extra:
+                phoneme_loss, word_loss, phoneme_acc, word_acc = self.model(x, y_phoneme, y_word, **extra)
+            elif rng_step is None:
                 phoneme_loss, word_loss, phoneme_acc, word_acc = self.model(x, y_phoneme, y_word)
             else:
                 phoneme_loss, word_loss, phoneme_acc, word_acc = self.model(x, y_phoneme, y_word, rng_step=rng_step)
@@ -746,6 +753,12 @@ class Trainer:
         if accumulate:
             sums = self._sums_buffer()
             sums.zero_()
+        if train and asr and mask_asr_enabled():
+            if mask_train_enabled():
+                # masked pre-training steps (PretrainedModel.forward(lengths=...)) are eager, like the SLU ones below
+                yield from self._iterate_eager(loader, train, asr, sums)
+                return
+            loader = _drop_lengths(loader, 3)    # SLU_MASK_ASR=1 alone: training drops the lengths, evaluation uses them
         if train and not asr:
             if mask_train_enabled():
                 # masked steps are eager: no look-ahead super-batches, no captured steps (a step's lengths table and the

@@ -732,6 +732,40 @@ int slu_attention_len_bwd(const float* keys, int64_t k_st, int64_t k_sb, const f
                           float* d_keys, float* d_values, float* d_query, int64_t ld_dq, const int32_t* n, float inv_scale,
                           int64_t B, int64_t T, int64_t Kd, int64_t Vd, void* stream);
 
+/* -------- lengths through ASR pre-training: frame packing for the phoneme / word heads — added under ABI 10 (two new
+ * entry points; nothing existing changed, so the version number stays).  The definition is this library's own (the
+ * reference's PretrainedModel.forward, models.py:291-331, takes no lengths; CollateWavsASR pads the labels with -1 and the
+ * waveforms with zeros, data.py).  PretrainedModel.forward(x, y_phoneme, y_word, lengths=...):
+ *   encoder   the waveform tail is zeroed and every stage runs length-aware by the definitions above (dropout: the dense
+ *             batch's draws); n_p[b] / n_w[b] = row b's valid frames behind the phoneme / word module;
+ *   kept      frame (b, t) of a head is kept iff y[b, t] != -1 AND t < n[b]: a label at or beyond n[b] is ignored
+ *             whatever its value (it is never read);
+ *   loss      sum of the kept frames' cross-entropies / number kept; accuracy = hits / number kept; no kept frame: NaN,
+ *             as F.cross_entropy;
+ *   hence     with k_b kept frames in row b, loss = sum_b k_b L_b / sum_b k_b where L_b is what x[b:b+1, :lengths[b]],
+ *             y[b:b+1, :n[b]] gives run alone, and every parameter gradient is the same weighted sum (up to summation
+ *             order with p = 0 or injected masks); no gradient reaches a padded frame: d h is exactly 0.0f there.
+ * The host knows every n[b] before the first launch, so the heads run on PACKED rows: N = sum_b n[b] rows, utterance-major,
+ * row offsets[b] + t = frame t of utterance b (offsets = exclusive prefix sum of the lengths, computed by the host and
+ * shipped in the same int32 table as the stage lengths; no device-to-host read).  Between the two calls below nothing new
+ * is needed: slu_gemm_f32, slu_frame_ce_fwd (N packed rows, ignore_index -1), the weight-gradient GEMM and slu_colsum_f32
+ * run unchanged on the packed rows — the (rows x 10 000) logits of the word head exist for valid frames only.
+ *   slu_frame_pack_len     h (T, B, C) time-major fp32, y (B, U) int64 labels (U >= T), lengths / offsets (B) int32 ->
+ *                          hp (N, C), yp (N): hp[offsets[b] + t] = h[t, b], yp[offsets[b] + t] = y[b, t] for t < lengths[b].
+ *                          One launch.  h and y at t >= lengths[b] are never read (NaN / garbage there is harmless).
+ *                          y = yp = NULL: activations only.
+ *   slu_frame_unpack_len   src (N, C), lengths, offsets -> dst (T, B, C): EVERY element written — src[offsets[b] + t] where
+ *                          t < lengths[b], exactly 0.0f elsewhere (selected, never a product).  The backward of the pack
+ *                          (d h) and the scatter of packed logits (posteriors, C = V).
+ * Memory-bound copies that walk the (T, B, C) side in memory order: 16 bytes per thread where C % 4 == 0 and both bases are
+ * 16-byte aligned, one float per thread otherwise; 64-bit row arithmetic.  NULL pointers / lengths / offsets, a
+ * non-positive size, N > T * B, T * B or N or C >= 2^31: SLU_ERR_INVALID_ARG before any launch.  lengths are clamped
+ * into [1, T] and a row index outside [0, N) is skipped: a bad table cannot index out of bounds (the host rejects it).  */
+int slu_frame_pack_len(const float* h, const int64_t* y, const int32_t* lengths, const int32_t* offsets, float* hp,
+                       int64_t* yp, int64_t T, int64_t B, int64_t C, int64_t U, int64_t N, void* stream);
+int slu_frame_unpack_len(const float* src, const int32_t* lengths, const int32_t* offsets, float* dst, int64_t T, int64_t B,
+                         int64_t C, int64_t N, void* stream);
+
 /* -------- Adam: torch.optim.Adam(model.parameters(), lr) (training.py:19, default betas / eps) ------
  * One launch updates up to slu_adam_max_tensors() tensors of one dtype (elem_bytes 4 / 8); the pointer
  * arrays are HOST arrays of device pointers (they travel in the kernel arguments: hipGraph-safe).
