@@ -13,6 +13,11 @@
 // semantics are stated in include/slu_hip.h (slu_wave_tempo).  It gathers its rows the same way (AugRow) and is split the
 // same way: the per-row search chain — segment k's best-overlap search needs segment k - 1's choice — is run by every
 // workgroup of the row, the write pass is divided.
+//
+// Both kernels have a length-taking form (template flag LEN; slu_wave_augment_len / slu_wave_tempo_len): len is read from
+// the caller's table instead of being scanned for (aug_row_len's pass over the row is gone), and the new end L' / len' is
+// stored for the caller.  Every sample is already read through a `j < len` guard (aug_window4, aug_at0), so what the
+// buffer holds at or beyond len — NaN, garbage — is never loaded; everything else is the same code.
 #include "slu_common.h"
 #include "slu_philox.h"
 #include "slu_reduce.h"
@@ -27,6 +32,8 @@ struct AugParams {
   float in_scale;
   float* out;                           // dense (B, T)
   float* params;                        // null, or (B, 8)
+  const int* lens;                      // LEN kernels: (B) valid samples per row
+  int* lens_out;                        // LEN kernels: null, or (B) = L' (may alias lens: then split == 1)
   int B, T, flags, split;
   unsigned long long seed, offset, sub_stride;
   const unsigned long long* offset_dev;
@@ -109,7 +116,15 @@ __device__ __forceinline__ int aug_row_len(const AugRow& r, int T, float* red) {
   return (int)block_max(last, red);
 }
 
+// the row's len: the caller's, clamped into [1, T] (LEN), or the scan above
+template <bool LEN>
+__device__ __forceinline__ int aug_len(const AugRow& r, const int* lens, int b, int T, float* red) {
+  if (LEN) return min(max(lens[b], 1), T);
+  return aug_row_len(r, T, red);
+}
+
 // grid: B * split workgroups of 256 threads, the workgroups of a row adjacent
+template <bool LEN>
 __global__ void __launch_bounds__(256)
 wave_augment_kernel(const AugParams p) {
   __shared__ float red[4];
@@ -128,7 +143,7 @@ wave_augment_kernel(const AugParams p) {
   uint32_t w[4];
   philox_block(p.seed, off, (1ull << 63) | (unsigned long long)bl, w);
 
-  const int len = aug_row_len(r, T, red);
+  const int len = aug_len<LEN>(r, p.lens, b, T, red);
 
   // ---- the drawn parameters ----
   float g = 1.0f;
@@ -171,6 +186,12 @@ wave_augment_kernel(const AugParams p) {
     float* q = p.params + (size_t)b * 8;
     q[0] = (float)len; q[1] = (float)Lp; q[2] = (float)d; q[3] = (float)(5 * snr_i);
     q[4] = g; q[5] = sigma; q[6] = energy; q[7] = 0.0f;
+  }
+  if (LEN && p.lens_out) {
+    // lens_out may be lens (in place; the launch then gives the row ONE workgroup): every wave has loaded lens[b] before
+    // the store — without the noise flag no block_sum barrier lies between the two
+    __syncthreads();
+    if (part == 0 && tid == 0) p.lens_out[b] = Lp;
   }
 
   // ---- write pass: this workgroup's share of the row's 4-sample chunks ----
@@ -223,6 +244,8 @@ struct TempoParams {
   float* out;                           // dense (B, T)
   int* shifts;                          // (B, nshift): delta_k, -1 behind the last segment
   float* params;                        // null, or (B, 4)
+  const int* lens;                      // LEN kernels: (B) valid samples per row
+  int* lens_out;                        // LEN kernels: null, or (B) = len' (never aliases lens)
   int B, T, S, O, R, split, nshift;
   float fixed;                          // > 0: the factor of every row
   unsigned long long seed, offset, sub_stride;
@@ -246,6 +269,7 @@ __device__ __forceinline__ float aug_at0(const AugRow& r, int j, int len) { retu
 // workgroup of a row runs the whole chain (below 128 rows the other CUs would idle) and stores the same delta_k.
 // Phase B, the write pass: output sample i belongs to segment i / H alone, so a workgroup writes its share of the row's
 // 4-sample chunks from the stored delta_k — the result does not depend on the split.
+template <bool LEN>
 __global__ void __launch_bounds__(256)
 wave_tempo_kernel(const TempoParams p) {
   __shared__ float red[4];
@@ -269,7 +293,7 @@ wave_tempo_kernel(const TempoParams p) {
     philox_block(p.seed, off, (1ull << 63) | (1ull << 62) | (unsigned long long)bl, w);
     f = __dadd_rn(0.9, __dmul_rn(0.2, (double)philox_to_uniform(w[0])));
   }
-  const int len = aug_row_len(r, T, red);
+  const int len = aug_len<LEN>(r, p.lens, b, T, red);
   const int Lp = min(T, (int)floor(__dadd_rn(__ddiv_rn((double)len, f), 0.5)));
   const int nseg = (Lp + H - 1) / H;
 
@@ -278,6 +302,7 @@ wave_tempo_kernel(const TempoParams p) {
       float* q = p.params + (size_t)b * 4;
       q[0] = (float)f; q[1] = (float)len; q[2] = (float)Lp; q[3] = (float)nseg;
     }
+    if (LEN && p.lens_out && tid == 0) p.lens_out[b] = Lp;
     for (int k = nseg + tid; k < p.nshift; k += 256) sh[k] = -1;
   }
 
@@ -365,28 +390,98 @@ wave_tempo_kernel(const TempoParams p) {
 
 using namespace slu;
 
-extern "C" int slu_wave_augment(const void* in, const void* const* in_table, int64_t table_rows, int in_pcm16, float in_scale,
-                                float* out, float* params, int64_t B, int64_t T, int flags, uint64_t seed, uint64_t offset,
-                                const uint64_t* offset_dev, int64_t sub_batch, uint64_t sub_stride, void* stream) {
-  SLU_REQUIRE((in || in_table) && out, "slu_wave_augment: null pointer");
-  SLU_REQUIRE(B > 0 && B < (1 << 29) && T > 0 && T <= (1 << 24), "slu_wave_augment: needs 1 <= B < 2^29 and 1 <= T <= 2^24 (got %lld x %lld)",
-              (long long)B, (long long)T);
-  SLU_REQUIRE(flags >= 0 && flags <= 7, "slu_wave_augment: flags must be a combination of 1 (gain), 2 (crop), 4 (noise)");
+// the two entry points of a kernel share their argument checks and launch: `len` = the length-taking form
+static int wave_augment_launch(const char* fn, bool len, const void* in, const void* const* in_table, int64_t table_rows,
+                               int in_pcm16, float in_scale, const int32_t* lengths, float* out, int32_t* lengths_out,
+                               float* params, int64_t B, int64_t T, int flags, uint64_t seed, uint64_t offset,
+                               const uint64_t* offset_dev, int64_t sub_batch, uint64_t sub_stride, void* stream) {
+  SLU_REQUIRE((in || in_table) && out, "%s: null pointer", fn);
+  SLU_REQUIRE(!len || lengths, "%s: null lengths", fn);
+  SLU_REQUIRE(B > 0 && B < (1 << 29) && T > 0 && T <= (1 << 24), "%s: needs 1 <= B < 2^29 and 1 <= T <= 2^24 (got %lld x %lld)",
+              fn, (long long)B, (long long)T);
+  SLU_REQUIRE(flags >= 0 && flags <= 7, "%s: flags must be a combination of 1 (gain), 2 (crop), 4 (noise)", fn);
   SLU_REQUIRE(!in_table || (table_rows >= 1 && table_rows <= B && B % table_rows == 0),
-              "slu_wave_augment: bad table_rows (B must be a whole number of tables' rows)");
-  SLU_REQUIRE(sub_batch >= 0 && (sub_batch == 0 || B % sub_batch == 0), "slu_wave_augment: B must be a multiple of sub_batch");
-  SLU_REQUIRE(in_table || ((uintptr_t)in & (in_pcm16 ? 1 : 3)) == 0, "slu_wave_augment: misaligned input");
-  SLU_REQUIRE(((uintptr_t)out & 3) == 0 && (!params || ((uintptr_t)params & 3) == 0), "slu_wave_augment: misaligned output");
-  SLU_REQUIRE(in_table || (const void*)out != in, "slu_wave_augment: out must not alias in");
+              "%s: bad table_rows (B must be a whole number of tables' rows)", fn);
+  SLU_REQUIRE(sub_batch >= 0 && (sub_batch == 0 || B % sub_batch == 0), "%s: B must be a multiple of sub_batch", fn);
+  SLU_REQUIRE(in_table || ((uintptr_t)in & (in_pcm16 ? 1 : 3)) == 0, "%s: misaligned input", fn);
+  SLU_REQUIRE(((uintptr_t)out & 3) == 0 && (!params || ((uintptr_t)params & 3) == 0), "%s: misaligned output", fn);
+  SLU_REQUIRE(!len || (((uintptr_t)lengths & 3) == 0 && ((uintptr_t)lengths_out & 3) == 0), "%s: misaligned lengths", fn);
+  SLU_REQUIRE(in_table || (const void*)out != in, "%s: out must not alias in", fn);
   AugParams p;
   p.in = in_table ? nullptr : in; p.in_tab = in_table; p.tab_rows = (int)(in_table ? table_rows : 1);
   p.pcm16 = in_pcm16 ? 1 : 0; p.in_scale = in_pcm16 ? in_scale : 1.0f;
-  p.out = out; p.params = params; p.B = (int)B; p.T = (int)T; p.flags = flags;
+  p.out = out; p.params = params; p.lens = lengths; p.lens_out = lengths_out;
+  p.B = (int)B; p.T = (int)T; p.flags = flags;
+  p.split = B < 128 ? 4 : B < 256 ? 2 : 1;
+  // lengths_out == lengths: the workgroups of a row all read lengths[b] and one of them overwrites it — one workgroup per
+  // row then (the result does not depend on the split), whose waves meet at a barrier between their loads and the store
+  if (len && lengths_out == lengths) p.split = 1;
+  p.seed = seed; p.offset = offset; p.sub_stride = sub_stride; p.offset_dev = (const unsigned long long*)offset_dev;
+  p.sub_batch = (int)sub_batch;
+  if (len)
+    hipLaunchKernelGGL(wave_augment_kernel<true>, dim3((unsigned)(B * p.split)), dim3(256), 0, (hipStream_t)stream, p);
+  else
+    hipLaunchKernelGGL(wave_augment_kernel<false>, dim3((unsigned)(B * p.split)), dim3(256), 0, (hipStream_t)stream, p);
+  SLU_CHECK_LAUNCH(len ? "wave_augment_kernel<len>" : "wave_augment_kernel");
+  return SLU_OK;
+}
+
+extern "C" int slu_wave_augment(const void* in, const void* const* in_table, int64_t table_rows, int in_pcm16, float in_scale,
+                                float* out, float* params, int64_t B, int64_t T, int flags, uint64_t seed, uint64_t offset,
+                                const uint64_t* offset_dev, int64_t sub_batch, uint64_t sub_stride, void* stream) {
+  return wave_augment_launch("slu_wave_augment", false, in, in_table, table_rows, in_pcm16, in_scale, nullptr, out, nullptr, params,
+                             B, T, flags, seed, offset, offset_dev, sub_batch, sub_stride, stream);
+}
+
+extern "C" int slu_wave_augment_len(const void* in, const void* const* in_table, int64_t table_rows, int in_pcm16, float in_scale,
+                                    const int32_t* lengths, float* out, int32_t* lengths_out, float* params, int64_t B, int64_t T,
+                                    int flags, uint64_t seed, uint64_t offset, const uint64_t* offset_dev, int64_t sub_batch,
+                                    uint64_t sub_stride, void* stream) {
+  return wave_augment_launch("slu_wave_augment_len", true, in, in_table, table_rows, in_pcm16, in_scale, lengths, out, lengths_out,
+                             params, B, T, flags, seed, offset, offset_dev, sub_batch, sub_stride, stream);
+}
+
+static int wave_tempo_launch(const char* fn, bool len, const void* in, const void* const* in_table, int64_t table_rows,
+                             int in_pcm16, float in_scale, const int32_t* lengths, float* out, int32_t* lengths_out,
+                             int32_t* shifts, float* params, int64_t B, int64_t T, int64_t segment, int64_t overlap,
+                             int64_t search, float fixed_factor, uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
+                             int64_t sub_batch, uint64_t sub_stride, void* stream) {
+  SLU_REQUIRE((in || in_table) && out && shifts, "%s: null pointer", fn);
+  SLU_REQUIRE(!len || lengths, "%s: null lengths", fn);
+  SLU_REQUIRE(B > 0 && B < (1 << 29) && T > 0 && T <= (1 << 24), "%s: needs 1 <= B < 2^29 and 1 <= T <= 2^24 (got %lld x %lld)",
+              fn, (long long)B, (long long)T);
+  SLU_REQUIRE(overlap >= 1 && 2 * overlap <= segment, "%s: needs 1 <= overlap and 2 overlap <= segment (got overlap %lld, segment %lld)",
+              fn, (long long)overlap, (long long)segment);
+  SLU_REQUIRE(segment <= T, "%s: segment %lld is longer than the rows (T = %lld)", fn, (long long)segment, (long long)T);
+  SLU_REQUIRE(search >= 1 && search <= TEMPO_RMAX, "%s: needs 1 <= search <= %d (got %lld)", fn, TEMPO_RMAX, (long long)search);
+  SLU_REQUIRE(fixed_factor == 0.0f || (fixed_factor >= 0.5f && fixed_factor <= 2.0f),
+              "%s: fixed_factor must be 0 (drawn per row) or in [0.5, 2]", fn);
+  SLU_REQUIRE(!in_table || (table_rows >= 1 && table_rows <= B && B % table_rows == 0),
+              "%s: bad table_rows (B must be a whole number of tables' rows)", fn);
+  SLU_REQUIRE(sub_batch >= 0 && (sub_batch == 0 || B % sub_batch == 0), "%s: B must be a multiple of sub_batch", fn);
+  SLU_REQUIRE(in_table || ((uintptr_t)in & (in_pcm16 ? 1 : 3)) == 0, "%s: misaligned input", fn);
+  SLU_REQUIRE(((uintptr_t)out & 3) == 0 && ((uintptr_t)shifts & 3) == 0 && (!params || ((uintptr_t)params & 3) == 0),
+              "%s: misaligned output", fn);
+  SLU_REQUIRE(!len || (((uintptr_t)lengths & 3) == 0 && ((uintptr_t)lengths_out & 3) == 0), "%s: misaligned lengths", fn);
+  SLU_REQUIRE(in_table || (const void*)out != in, "%s: out must not alias in", fn);
+  // every workgroup of a row reads lengths[b] and one of them stores len': in place that is a race
+  SLU_REQUIRE(!len || (const int32_t*)lengths_out != lengths, "%s: lengths_out must not alias lengths", fn);
+  TempoParams p;
+  p.in = in_table ? nullptr : in; p.in_tab = in_table; p.tab_rows = (int)(in_table ? table_rows : 1);
+  p.pcm16 = in_pcm16 ? 1 : 0; p.in_scale = in_pcm16 ? in_scale : 1.0f;
+  p.out = out; p.shifts = shifts; p.params = params; p.lens = lengths; p.lens_out = lengths_out;
+  p.B = (int)B; p.T = (int)T;
+  p.S = (int)segment; p.O = (int)overlap; p.R = (int)search; p.fixed = fixed_factor;
+  const int64_t H = segment - overlap;
+  p.nshift = (int)((T + H - 1) / H);
   p.split = B < 128 ? 4 : B < 256 ? 2 : 1;
   p.seed = seed; p.offset = offset; p.sub_stride = sub_stride; p.offset_dev = (const unsigned long long*)offset_dev;
   p.sub_batch = (int)sub_batch;
-  hipLaunchKernelGGL(wave_augment_kernel, dim3((unsigned)(B * p.split)), dim3(256), 0, (hipStream_t)stream, p);
-  SLU_CHECK_LAUNCH("wave_augment_kernel");
+  if (len)
+    hipLaunchKernelGGL(wave_tempo_kernel<true>, dim3((unsigned)(B * p.split)), dim3(256), 0, (hipStream_t)stream, p);
+  else
+    hipLaunchKernelGGL(wave_tempo_kernel<false>, dim3((unsigned)(B * p.split)), dim3(256), 0, (hipStream_t)stream, p);
+  SLU_CHECK_LAUNCH(len ? "wave_tempo_kernel<len>" : "wave_tempo_kernel");
   return SLU_OK;
 }
 
@@ -395,33 +490,17 @@ extern "C" int slu_wave_tempo(const void* in, const void* const* in_table, int64
                               int64_t segment, int64_t overlap, int64_t search, float fixed_factor,
                               uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
                               int64_t sub_batch, uint64_t sub_stride, void* stream) {
-  SLU_REQUIRE((in || in_table) && out && shifts, "slu_wave_tempo: null pointer");
-  SLU_REQUIRE(B > 0 && B < (1 << 29) && T > 0 && T <= (1 << 24), "slu_wave_tempo: needs 1 <= B < 2^29 and 1 <= T <= 2^24 (got %lld x %lld)",
-              (long long)B, (long long)T);
-  SLU_REQUIRE(overlap >= 1 && 2 * overlap <= segment, "slu_wave_tempo: needs 1 <= overlap and 2 overlap <= segment (got overlap %lld, segment %lld)",
-              (long long)overlap, (long long)segment);
-  SLU_REQUIRE(segment <= T, "slu_wave_tempo: segment %lld is longer than the rows (T = %lld)", (long long)segment, (long long)T);
-  SLU_REQUIRE(search >= 1 && search <= TEMPO_RMAX, "slu_wave_tempo: needs 1 <= search <= %d (got %lld)", TEMPO_RMAX, (long long)search);
-  SLU_REQUIRE(fixed_factor == 0.0f || (fixed_factor >= 0.5f && fixed_factor <= 2.0f),
-              "slu_wave_tempo: fixed_factor must be 0 (drawn per row) or in [0.5, 2]");
-  SLU_REQUIRE(!in_table || (table_rows >= 1 && table_rows <= B && B % table_rows == 0),
-              "slu_wave_tempo: bad table_rows (B must be a whole number of tables' rows)");
-  SLU_REQUIRE(sub_batch >= 0 && (sub_batch == 0 || B % sub_batch == 0), "slu_wave_tempo: B must be a multiple of sub_batch");
-  SLU_REQUIRE(in_table || ((uintptr_t)in & (in_pcm16 ? 1 : 3)) == 0, "slu_wave_tempo: misaligned input");
-  SLU_REQUIRE(((uintptr_t)out & 3) == 0 && ((uintptr_t)shifts & 3) == 0 && (!params || ((uintptr_t)params & 3) == 0),
-              "slu_wave_tempo: misaligned output");
-  SLU_REQUIRE(in_table || (const void*)out != in, "slu_wave_tempo: out must not alias in");
-  TempoParams p;
-  p.in = in_table ? nullptr : in; p.in_tab = in_table; p.tab_rows = (int)(in_table ? table_rows : 1);
-  p.pcm16 = in_pcm16 ? 1 : 0; p.in_scale = in_pcm16 ? in_scale : 1.0f;
-  p.out = out; p.shifts = shifts; p.params = params; p.B = (int)B; p.T = (int)T;
-  p.S = (int)segment; p.O = (int)overlap; p.R = (int)search; p.fixed = fixed_factor;
-  const int64_t H = segment - overlap;
-  p.nshift = (int)((T + H - 1) / H);
-  p.split = B < 128 ? 4 : B < 256 ? 2 : 1;
-  p.seed = seed; p.offset = offset; p.sub_stride = sub_stride; p.offset_dev = (const unsigned long long*)offset_dev;
-  p.sub_batch = (int)sub_batch;
-  hipLaunchKernelGGL(wave_tempo_kernel, dim3((unsigned)(B * p.split)), dim3(256), 0, (hipStream_t)stream, p);
-  SLU_CHECK_LAUNCH("wave_tempo_kernel");
-  return SLU_OK;
+  return wave_tempo_launch("slu_wave_tempo", false, in, in_table, table_rows, in_pcm16, in_scale, nullptr, out, nullptr, shifts,
+                           params, B, T, segment, overlap, search, fixed_factor, seed, offset, offset_dev, sub_batch, sub_stride,
+                           stream);
+}
+
+extern "C" int slu_wave_tempo_len(const void* in, const void* const* in_table, int64_t table_rows, int in_pcm16, float in_scale,
+                                  const int32_t* lengths, float* out, int32_t* lengths_out, int32_t* shifts, float* params,
+                                  int64_t B, int64_t T, int64_t segment, int64_t overlap, int64_t search, float fixed_factor,
+                                  uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
+                                  int64_t sub_batch, uint64_t sub_stride, void* stream) {
+  return wave_tempo_launch("slu_wave_tempo_len", true, in, in_table, table_rows, in_pcm16, in_scale, lengths, out, lengths_out,
+                           shifts, params, B, T, segment, overlap, search, fixed_factor, seed, offset, offset_dev, sub_batch,
+                           sub_stride, stream);
 }

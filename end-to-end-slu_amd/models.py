@@ -127,6 +127,23 @@ def _augment(x, training_augment):
         return _ops.wave_augment(x, flags, *stream)
 
 
+def _augment_len(x, host):
+    """_augment on a batch whose rows' lengths are known (SLU_MASK_AUGMENT=1; Model._forward_len): x (B, T) fp32 / PCM16
+    device tensor, host = its rows' sample counts -> (x_aug dense fp32, exactly zero from every row's new end on; the new
+    sample counts, computed on the host — ops.tempo_out_lengths / augment_out_lengths, no device read).  Same stream, order
+    and knobs as _augment; a device-resident step index has no host mirror and is refused by the caller."""
+    seed = ((_DropoutState.seed if _DropoutState.seed is not None else torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF) ^ AUGMENT_KEY
+    flags, offset, sub = _ops.augment_flags(), _DropoutState.current * 16, _DropoutState.sub_batch
+    T = x.shape[1]
+    with torch.no_grad():
+        n_dev = torch.tensor(host, dtype=torch.int32).to(x.device, non_blocking=True)
+        if _ops.tempo_enabled():
+            x, n_dev = _ops.wave_tempo_len(x, n_dev, seed, offset, None, sub)
+            host = _ops.tempo_out_lengths(host, T, seed, offset, sub)
+        x, _ = _ops.wave_augment_len(x, n_dev, flags, seed, offset, None, sub)
+        return x, _ops.augment_out_lengths(host, T, flags, seed, offset, sub)
+
+
 class _FrozenMath:
     """State of the frozen stages' arithmetic in the guarded mode (SLU_FROZEN_MATH=auto; slu_hip/guard.py)."""
     scope = None        # the RangeGuard watching the evaluation that is running now: only then auto = f16x2
@@ -236,6 +253,16 @@ def mask_seq2seq_enabled():
     v = os.environ.get("SLU_MASK_SEQ2SEQ", "0")
     if v not in ("0", "1"):
         raise ValueError("SLU_MASK_SEQ2SEQ=%r: expected 0 or 1" % (v,))
+    return v == "1"
+
+
+def mask_augment_enabled():
+    """SLU_MASK_AUGMENT: "0" (default) — a masked training step (Model.forward(lengths=...) in train() mode) refuses a model
+    with augment=True; "1" — its waveforms pass through the length-taking augmentation kernels (_augment_len) and the
+    stages run on the lengths behind them.  training.mask_augment_enabled adds the Trainer's rule: 1 needs SLU_MASK_TRAIN=1."""
+    v = os.environ.get("SLU_MASK_AUGMENT", "0")
+    if v not in ("0", "1"):
+        raise ValueError("SLU_MASK_AUGMENT=%r: expected 0 or 1" % (v,))
     return v == "1"
 
 
@@ -1929,16 +1956,23 @@ class Model(torch.nn.Module):
         host = _host_lengths(lengths, x.shape[0], x.shape[1])
         stages = pm._stages() + list(self._intent_stages)
         _check_len_stages(stages)
-        if self.augment and self.training:
+        augment = self.augment and self.training
+        if augment and not mask_augment_enabled():
             raise ValueError("lengths: augment=True is not supported (the augmentation moves the utterances' ends)")
         _refuse_trainable_cnn_lengths(pm._cnn_stages)
         (x,) = pm._to_device(x)
         pm._cnn_stages[-1].time_major = True
         _DropoutState.current = next_rng_step() if rng_step is None else rng_step
-        with torch.no_grad():
-            x = _ops.pcm16_to_f32(x) if x.dtype == torch.int16 else x.float()
-            dev_len = torch.tensor(host, dtype=torch.int32).to(x.device, non_blocking=True)
-            x = _ops.mask_rows_len(x, dev_len)
+        if augment:
+            # the kernels read the lengths, take a PCM16 batch as it is and leave the tail beyond the new ends zero
+            if x.dtype != torch.int16:
+                x = x.float()
+            x, host = _augment_len(x, host)
+        else:
+            with torch.no_grad():
+                x = _ops.pcm16_to_f32(x) if x.dtype == torch.int16 else x.float()
+                dev_len = torch.tensor(host, dtype=torch.int32).to(x.device, non_blocking=True)
+                x = _ops.mask_rows_len(x, dev_len)
         h, _, n_dev = _run_stages_len(stages, x, host, training=self.training)
         if self.seq2seq:
             # loss = -mean over the padded batch's rows of log p(y_b | x_b[:lengths[b]]); a host zero for the accuracy, as

@@ -84,6 +84,10 @@ SIGNATURES = {
     "slu_wave_augment": (c_int, [vp, vp, c_i64, c_int, c_f32, vp, vp, c_i64, c_i64, c_int, c_u64, c_u64, vp, c_i64, c_u64, vp]),
     "slu_wave_tempo": (c_int, [vp, vp, c_i64, c_int, c_f32, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_f32, c_u64, c_u64, vp,
                                c_i64, c_u64, vp]),
+    "slu_wave_augment_len": (c_int, [vp, vp, c_i64, c_int, c_f32, vp, vp, vp, vp, c_i64, c_i64, c_int, c_u64, c_u64, vp, c_i64,
+                                     c_u64, vp]),
+    "slu_wave_tempo_len": (c_int, [vp, vp, c_i64, c_int, c_f32, vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_f32, c_u64,
+                                   c_u64, vp, c_i64, c_u64, vp]),
     "slu_mask_rows_len": (c_int, [vp, vp, vp, c_i64, c_i64, vp]),
     "slu_pool_act_len_fwd": (c_int, [vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_int, c_f32, c_i64, c_i64, vp]),
     "slu_gru_seq_fwd_len": (c_int, [vp, vp, vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, vp]),

@@ -8,7 +8,9 @@ torch is plumbing here: it owns the device buffers, the stream and the autograd 
 arithmetic of the hot path happens in libslu_hip.so; there is no fallback path.
 """
 import contextlib
+import math
 import os
+import struct
 
 import torch
 
@@ -657,26 +659,44 @@ def augment_flags():
     return flags
 
 
+def _wave_input(x, who):
+    """The input forms of the waveform kernels -> (x kept alive, pointer, table, table rows, (pcm16, scale))."""
+    pcm = (1, PCM16_SCALE) if x.dtype == torch.int16 else (0, 1.0)
+    if isinstance(x, RowTable):
+        return x, None, x.ptrs.data_ptr(), x.rows, pcm
+    if x.dtype not in (torch.float32, torch.int16) or not x.is_cuda or x.dim() != 2:
+        raise TypeError("%s: x must be a float32 or int16 (B, T) CUDA tensor (got %s on %s)" % (who, x.dtype, x.device))
+    x = x.contiguous()
+    return x, x.data_ptr(), None, 0, pcm
+
+
+def _wave_augment(who, x, lengths, flags, seed, offset, offset_dev, sub_batch, want_params):
+    """The wrapper body of wave_augment (lengths None) and wave_augment_len -> (out, lengths_out or None, params or None)."""
+    L = _lib.load()
+    B, T = x.shape
+    if lengths is not None:
+        _len_ok(lengths, B)
+    x, x_ptr, tab, tab_rows, pcm = _wave_input(x, who)
+    out = torch.empty(B, T, dtype=torch.float32, device=x.device)
+    lengths_out = torch.empty(B, dtype=torch.int32, device=x.device) if lengths is not None else None
+    params = torch.empty(B, 8, dtype=torch.float32, device=x.device) if want_params else None
+    head = (x_ptr, tab, tab_rows, *pcm)
+    tail = (_ptr(params), B, T, int(flags), int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset), _ptr(offset_dev), int(sub_batch), 16,
+            _stream())
+    if lengths is None:
+        _lib.check(L.slu_wave_augment(*head, out.data_ptr(), *tail), "slu_wave_augment")
+    else:
+        _lib.check(L.slu_wave_augment_len(*head, lengths.data_ptr(), out.data_ptr(), lengths_out.data_ptr(), *tail),
+                   "slu_wave_augment_len")
+    return out, lengths_out, params
+
+
 def wave_augment(x, flags, seed, offset, offset_dev=None, sub_batch=0, want_params=False):
     """The waveform augmentation of reference data.py:276-316 on the device (slu_wave_augment; the row semantics are in
     include/slu_hip.h): x = dense fp32 or int16 (B, T) tensor, or a RowTable of either dtype -> dense fp32 (B, T), plus
     the (B, 8) tensor of what was drawn per row when want_params.  The kernel gathers the rows itself: a row-table
     super-batch or a PCM16 batch needs no copy or conversion pass in front of it.  Stream arguments as dropout_bits."""
-    L = _lib.load()
-    B, T = x.shape
-    pcm = (1, PCM16_SCALE) if x.dtype == torch.int16 else (0, 1.0)
-    if isinstance(x, RowTable):
-        x_ptr, tab, tab_rows = None, x.ptrs.data_ptr(), x.rows
-    else:
-        if x.dtype not in (torch.float32, torch.int16) or not x.is_cuda or x.dim() != 2:
-            raise TypeError("wave_augment: x must be a float32 or int16 (B, T) CUDA tensor (got %s on %s)" % (x.dtype, x.device))
-        x = x.contiguous()
-        x_ptr, tab, tab_rows = x.data_ptr(), None, 0
-    out = torch.empty(B, T, dtype=torch.float32, device=x.device)
-    params = torch.empty(B, 8, dtype=torch.float32, device=x.device) if want_params else None
-    _lib.check(L.slu_wave_augment(x_ptr, tab, tab_rows, *pcm, out.data_ptr(), _ptr(params), B, T, int(flags),
-                                  int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset), _ptr(offset_dev), int(sub_batch), 16, _stream()),
-               "slu_wave_augment")
+    out, _, params = _wave_augment("wave_augment", x, None, flags, seed, offset, offset_dev, sub_batch, want_params)
     return (out, params) if want_params else out
 
 
@@ -697,6 +717,32 @@ def tempo_defaults(fs=16000):
     return (fs * 82 + 500) // 1000, fs * 12 // 1000 // 8 * 8, (fs * 1468 + 50000) // 100000
 
 
+def _wave_tempo(who, x, lengths, seed, offset, offset_dev, sub_batch, segment, overlap, search, fs, fixed_factor, want_params):
+    """The wrapper body of wave_tempo (lengths None) and wave_tempo_len -> (out, lengths_out or None, shifts, params or None)."""
+    L = _lib.load()
+    B, T = x.shape
+    if lengths is not None:
+        _len_ok(lengths, B)
+    d_seg, d_ovl, d_search = tempo_defaults(fs)
+    segment, overlap, search = (int(d if v is None else v) for v, d in ((segment, d_seg), (overlap, d_ovl), (search, d_search)))
+    x, x_ptr, tab, tab_rows, pcm = _wave_input(x, who)
+    if not 1 <= overlap < segment:
+        raise ValueError("%s: needs 1 <= overlap < segment (got overlap %d, segment %d)" % (who, overlap, segment))
+    out = torch.empty(B, T, dtype=torch.float32, device=x.device)
+    lengths_out = torch.empty(B, dtype=torch.int32, device=x.device) if lengths is not None else None
+    shifts = torch.empty(B, -(-T // (segment - overlap)), dtype=torch.int32, device=x.device)
+    params = torch.empty(B, 4, dtype=torch.float32, device=x.device) if want_params else None
+    head = (x_ptr, tab, tab_rows, *pcm)
+    tail = (shifts.data_ptr(), _ptr(params), B, T, segment, overlap, search, float(fixed_factor), int(seed) & 0xFFFFFFFFFFFFFFFF,
+            int(offset), _ptr(offset_dev), int(sub_batch), 16, _stream())
+    if lengths is None:
+        _lib.check(L.slu_wave_tempo(*head, out.data_ptr(), *tail), "slu_wave_tempo")
+    else:
+        _lib.check(L.slu_wave_tempo_len(*head, lengths.data_ptr(), out.data_ptr(), lengths_out.data_ptr(), *tail),
+                   "slu_wave_tempo_len")
+    return out, lengths_out, shifts, params
+
+
 def wave_tempo(x, seed, offset, offset_dev=None, sub_batch=0, segment=None, overlap=None, search=None, fs=16000,
                fixed_factor=0.0, want_params=False):
     """The `tempo` effect of reference data.py:279-281 on the device: a WSOLA time stretch by a factor drawn per row from
@@ -704,27 +750,93 @@ def wave_tempo(x, seed, offset, offset_dev=None, sub_batch=0, segment=None, over
     it -> dense fp32 (B, T), or (y, shifts (B, ceil(T / hop)) int32, params (B, 4) = f, len, len', segments) when
     want_params.  segment / overlap / search default to tempo_defaults(fs).  Stream arguments as wave_augment: the factor
     is drawn from a Philox block of its own on the same stream."""
-    L = _lib.load()
-    B, T = x.shape
-    d_seg, d_ovl, d_search = tempo_defaults(fs)
-    segment, overlap, search = (int(d if v is None else v) for v, d in ((segment, d_seg), (overlap, d_ovl), (search, d_search)))
-    pcm = (1, PCM16_SCALE) if x.dtype == torch.int16 else (0, 1.0)
-    if isinstance(x, RowTable):
-        x_ptr, tab, tab_rows = None, x.ptrs.data_ptr(), x.rows
-    else:
-        if x.dtype not in (torch.float32, torch.int16) or not x.is_cuda or x.dim() != 2:
-            raise TypeError("wave_tempo: x must be a float32 or int16 (B, T) CUDA tensor (got %s on %s)" % (x.dtype, x.device))
-        x = x.contiguous()
-        x_ptr, tab, tab_rows = x.data_ptr(), None, 0
-    if not 1 <= overlap < segment:
-        raise ValueError("wave_tempo: needs 1 <= overlap < segment (got overlap %d, segment %d)" % (overlap, segment))
-    out = torch.empty(B, T, dtype=torch.float32, device=x.device)
-    shifts = torch.empty(B, -(-T // (segment - overlap)), dtype=torch.int32, device=x.device)
-    params = torch.empty(B, 4, dtype=torch.float32, device=x.device) if want_params else None
-    _lib.check(L.slu_wave_tempo(x_ptr, tab, tab_rows, *pcm, out.data_ptr(), shifts.data_ptr(), _ptr(params), B, T, segment, overlap,
-                                search, float(fixed_factor), int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset), _ptr(offset_dev),
-                                int(sub_batch), 16, _stream()), "slu_wave_tempo")
+    out, _, shifts, params = _wave_tempo("wave_tempo", x, None, seed, offset, offset_dev, sub_batch, segment, overlap, search, fs,
+                                         fixed_factor, want_params)
     return (out, shifts, params) if want_params else out
+
+
+# ---- the two waveform kernels on rows whose lengths the caller knows (Model._forward_len under SLU_MASK_AUGMENT=1) ----
+def wave_augment_len(x, lengths, flags, seed, offset, offset_dev=None, sub_batch=0, want_params=False):
+    """wave_augment on rows of known lengths (slu_wave_augment_len): lengths = int32 CUDA tensor (B), each in [1, T]; what x
+    holds at or beyond lengths[b] is never read.  -> (y dense fp32 (B, T), zero from L' on; lengths_out int32 (B) = L'
+    [, params]).  The host knows L' without reading lengths_out: augment_out_lengths."""
+    out, lengths_out, params = _wave_augment("wave_augment_len", x, lengths, flags, seed, offset, offset_dev, sub_batch, want_params)
+    return (out, lengths_out, params) if want_params else (out, lengths_out)
+
+
+def wave_tempo_len(x, lengths, seed, offset, offset_dev=None, sub_batch=0, segment=None, overlap=None, search=None, fs=16000,
+                   fixed_factor=0.0, want_params=False):
+    """wave_tempo on rows of known lengths (slu_wave_tempo_len), as wave_augment_len: -> (y, lengths_out int32 (B) = len'
+    [, shifts, params]).  The host knows len' without reading lengths_out: tempo_out_lengths."""
+    out, lengths_out, shifts, params = _wave_tempo("wave_tempo_len", x, lengths, seed, offset, offset_dev, sub_batch, segment,
+                                                   overlap, search, fs, fixed_factor, want_params)
+    return (out, lengths_out, shifts, params) if want_params else (out, lengths_out)
+
+
+def _philox_block(seed, offset, blk):
+    """Philox4x32-10 in Python integers (csrc/slu_philox.h: counter = (blk, offset), key = seed) -> the block's four words."""
+    c = [blk & 0xFFFFFFFF, (blk >> 32) & 0xFFFFFFFF, offset & 0xFFFFFFFF, (offset >> 32) & 0xFFFFFFFF]
+    k0, k1 = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c[0], 0xCD9E8D57 * c[2]
+        c = [(p1 >> 32) ^ c[1] ^ k0, p1 & 0xFFFFFFFF, (p0 >> 32) ^ c[3] ^ k1, p0 & 0xFFFFFFFF]
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return c
+
+
+def _out_lengths_rows(lengths, T, seed, offset, sub_batch, sub_stride):
+    """The checked arguments of the two mirrors below -> [(len, its Philox offset, its row on that stream)]."""
+    if torch.is_tensor(offset) or not isinstance(offset, int) or isinstance(offset, bool):
+        raise ValueError("lengths: the host can mirror the augmentation's new lengths for a host step index only (a "
+                         "device-resident offset — a captured step — is not known here)")
+    lengths, T, seed, sub_batch = [int(n) for n in lengths], int(T), int(seed) & 0xFFFFFFFFFFFFFFFF, int(sub_batch)
+    if sub_batch < 0 or (sub_batch and len(lengths) % sub_batch):
+        raise ValueError("lengths: %d rows are no whole number of sub-batches of %d" % (len(lengths), sub_batch))
+    rows = []
+    for b, n in enumerate(lengths):
+        if not 1 <= n <= T:
+            raise ValueError("lengths: %d outside [1, %d]" % (n, T))
+        k, bl = (b // sub_batch, b % sub_batch) if sub_batch else (0, b)
+        rows.append((n, (offset + k * int(sub_stride)) & 0xFFFFFFFFFFFFFFFF, bl))
+    return rows, T, seed
+
+
+def augment_out_lengths(lengths, T, flags, seed, offset, sub_batch=0, sub_stride=16):
+    """Host mirror of slu_wave_augment_len's lengths_out (integer arithmetic, no launch, no device read): the L' of every
+    row of a (len(lengths), T) batch on the stream (seed, offset) — w1 = word 1 of Philox block (1 << 63) | row,
+    Lmin = (9 len + 5) // 10, Lmax = (11 len + 5) // 10, L' = min(T, Lmin + ((w1 (Lmax - Lmin)) >> 32)); len itself without
+    the crop flag.  -> list of ints, each in [1, T]."""
+    rows, T, seed = _out_lengths_rows(lengths, T, seed, offset, sub_batch, sub_stride)
+    out = []
+    for n, off, bl in rows:
+        Lp = n
+        if int(flags) & AUGMENT_FLAGS["crop"]:
+            w1 = _philox_block(seed, off, (1 << 63) | bl)[1]
+            lmin, lmax = (9 * n + 5) // 10, (11 * n + 5) // 10
+            Lp = min(T, lmin + ((w1 * (lmax - lmin)) >> 32))
+        assert 1 <= Lp <= T, (n, T, Lp)
+        out.append(Lp)
+    return out
+
+
+def tempo_out_lengths(lengths, T, seed, offset, sub_batch=0, sub_stride=16, fixed_factor=0.0):
+    """Host mirror of slu_wave_tempo_len's lengths_out: len' = min(T, floor(len / f + 0.5)) with f = the fp32 fixed_factor
+    when > 0, else 0.9 + 0.2 u, u = (w0 >> 8) 2^-24, w0 = word 0 of Philox block (1 << 63) | (1 << 62) | row — float64, one
+    rounding per operation, as the kernel.  -> list of ints, each in [1, T]."""
+    rows, T, seed = _out_lengths_rows(lengths, T, seed, offset, sub_batch, sub_stride)
+    fixed = struct.unpack("f", struct.pack("f", float(fixed_factor)))[0]
+    if fixed != 0.0 and not 0.5 <= fixed <= 2.0:
+        raise ValueError("lengths: fixed_factor must be 0 (drawn per row) or in [0.5, 2]")
+    out = []
+    for n, off, bl in rows:
+        f = fixed
+        if not fixed > 0.0:
+            w0 = _philox_block(seed, off, (1 << 63) | (1 << 62) | bl)[0]
+            f = 0.9 + 0.2 * ((w0 >> 8) * 2.0 ** -24)
+        Lp = min(T, int(math.floor(n / f + 0.5)))
+        assert 1 <= Lp <= T, (n, T, f, Lp)
+        out.append(Lp)
+    return out
 
 
 def gru_pool_fused_ok(H, D, T, p, mask, method, factor):

@@ -25,7 +25,7 @@ from tqdm import tqdm
 
 from data import SLUDataset, ASRDataset, mask_padding_enabled as data_mask_padding_enabled
 from data import mask_asr_enabled
-from models import PretrainedModel, Model, next_rng_step
+from models import PretrainedModel, Model, next_rng_step, mask_augment_enabled as models_mask_augment_enabled
 from slu_hip import dp, ops, pipeline
 
 
@@ -166,6 +166,15 @@ def mask_train_enabled():
     return v == "1"
 
 
+def mask_augment_enabled():
+    """SLU_MASK_AUGMENT: "0" (default) — a masked step refuses a model with augment=True; "1" — the masked steps augment
+    (models.mask_augment_enabled; Model._forward_len).  Needs SLU_MASK_TRAIN=1: without it the training loops drop the lengths."""
+    on = models_mask_augment_enabled()
+    if on and not mask_train_enabled():
+        raise ValueError("SLU_MASK_AUGMENT=1 needs SLU_MASK_TRAIN=1: only the masked training steps carry lengths")
+    return on
+
+
 class _drop_lengths:
     """SLU batches of the training loops: (x, y) whatever the loader yields.  With SLU_MASK_PADDING=1 the collate function
     adds the utterances' sample counts as a third element (data.CollateWavsSLU); evaluation uses them
@@ -278,6 +287,7 @@ class Trainer:
         self.config = config
         mask_train_enabled()                     # SLU_MASK_TRAIN=1 without SLU_MASK_PADDING=1 fails here, not at the first step
         mask_asr_enabled()                       # and so does SLU_MASK_ASR=1
+        mask_augment_enabled()                   # and SLU_MASK_AUGMENT=1 without SLU_MASK_TRAIN=1
         if isinstance(self.model, PretrainedModel):
             self.lr = config.pretraining_lr
             self.checkpoint_path = os.path.join(self.config.folder, "pretraining")

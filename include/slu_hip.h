@@ -393,6 +393,25 @@ int slu_dropout_bits(uint32_t* bits, float p, uint64_t seed, uint64_t offset, co
 int slu_wave_augment(const void* in, const void* const* in_table, int64_t table_rows, int in_pcm16, float in_scale,
                      float* out, float* params, int64_t B, int64_t T, int flags, uint64_t seed, uint64_t offset,
                      const uint64_t* offset_dev, int64_t sub_batch, uint64_t sub_stride, void* stream);
+/* slu_wave_augment on rows whose lengths the caller knows (ABI 10, added without a version step; the lengths family of
+ * "padding-invariant inference" / "masked training" below): lengths (B) int32 on the device, required.
+ *   len    = clamp(lengths[b], 1, T): bad values are the host's to reject (models._host_lengths), the kernel only never
+ *          indexes out of bounds.  No last-non-zero scan: an utterance that ends in digital silence keeps its length.
+ *   x      = 0 at and beyond len WHATEVER THE BUFFER HOLDS: those samples are never loaded, so NaN or garbage there
+ *          reaches no output bit, not the energy, not params.
+ *   Every other rule is slu_wave_augment's, bit for bit: the draws, the Philox blocks (the noise block index keeps the
+ *   buffer's ceil(T / 4)), the sub-batch rule, the crop window, sigma, the split over workgroups, no atomics.  On a
+ *   zero-padded batch whose rows end in a non-zero sample at lengths[b] - 1 both entry points give identical bits.
+ *   out    y[i] = 0.0f exactly for L' <= i < T: no slu_mask_rows_len pass is needed in front of or behind the call.
+ *   lengths_out: NULL, or (B) int32 = L' (in [1, T]), one plain store per row.  It MAY alias lengths (in place): the
+ *          rows are then not split over workgroups (same bits, one workgroup per row), and a workgroup barrier
+ *          separates every wave's load of lengths[b] from the store, whatever the flags.
+ *   params[b][0] = len as given.  Input forms (dense / in_table, fp32 / PCM16) and argument checks as slu_wave_augment;
+ *   lengths == NULL is SLU_ERR_INVALID_ARG.  The host knows L' without reading it back: ops.augment_out_lengths.    */
+int slu_wave_augment_len(const void* in, const void* const* in_table, int64_t table_rows, int in_pcm16, float in_scale,
+                         const int32_t* lengths, float* out, int32_t* lengths_out, float* params, int64_t B, int64_t T,
+                         int flags, uint64_t seed, uint64_t offset, const uint64_t* offset_dev, int64_t sub_batch,
+                         uint64_t sub_stride, void* stream);
 /* Tempo perturbation in front of slu_wave_augment (ABI 10, added without a version step as the beam-search and
  * augmentation entry points were; reference data.py:279-281, the `tempo` effect of the chain): a duration change of
  * +-10 % without a pitch change, by WSOLA (waveform-similarity overlap-add).  out (B, T) dense fp32 = the stretched rows of
@@ -427,6 +446,18 @@ int slu_wave_tempo(const void* in, const void* const* in_table, int64_t table_ro
                    int64_t segment, int64_t overlap, int64_t search, float fixed_factor,
                    uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
                    int64_t sub_batch, uint64_t sub_stride, void* stream);
+/* slu_wave_tempo on rows whose lengths the caller knows (ABI 10, added without a version step), as slu_wave_augment_len:
+ * len = clamp(lengths[b], 1, T), no scan; x = 0 at and beyond len whatever the buffer holds — nothing there is loaded, so
+ * it reaches neither a search cost D(delta) nor an output bit; f, len', the positions, the search, the synthesis, shifts,
+ * params and the split are slu_wave_tempo's, bit for bit (identical results on a zero-padded batch whose rows end in a
+ * non-zero sample).  y[i] = 0.0f exactly for len' <= i < T.  lengths_out: NULL, or (B) int32 = len' (in [1, T]), one plain
+ * store per row; it must NOT alias lengths.  lengths == NULL is SLU_ERR_INVALID_ARG; the other checks are
+ * slu_wave_tempo's.  The host knows len' without reading it back: ops.tempo_out_lengths.                            */
+int slu_wave_tempo_len(const void* in, const void* const* in_table, int64_t table_rows, int in_pcm16, float in_scale,
+                       const int32_t* lengths, float* out, int32_t* lengths_out, int32_t* shifts, float* params,
+                       int64_t B, int64_t T, int64_t segment, int64_t overlap, int64_t search, float fixed_factor,
+                       uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
+                       int64_t sub_batch, uint64_t sub_stride, void* stream);
 /* dx (T,B,C) from dy (T_out,B,C); x and y (forward input/output) are needed for method 2 only. */
 int slu_dropout_pool_bwd(const float* dy, const float* x, const float* y, const float* mask,
                          int64_t m_st, int64_t m_sb, float p, uint64_t seed, uint64_t offset,
