@@ -827,16 +827,17 @@ def get_ASR_datasets(config):
     import glob
     base_path = config.asr_path
     wavs = lambda tgs: [p.replace("text", "audio").replace(".TextGrid", ".wav") for p in tgs]
-    train_tg = glob.glob(base_path + "/text/train*/*/*/*.TextGrid")
-    valid_tg = glob.glob(base_path + "/text/dev*/*/*/*.TextGrid")
-    test_tg = glob.glob(base_path + "/text/test*/*/*/*.TextGrid")
+    # sorted: glob returns the directory order of the file system, which differs from machine to machine — and with it the
+    # ties of the vocabulary count below, which utterances share a batch under a given seed, and (under data parallelism,
+    # where DistributedSampler indexes into the list) which rank gets which file
+    train_tg = sorted(glob.glob(base_path + "/text/train*/*/*/*.TextGrid"))
+    valid_tg = sorted(glob.glob(base_path + "/text/dev*/*/*/*.TextGrid"))
+    test_tg = sorted(glob.glob(base_path + "/text/test*/*/*/*.TextGrid"))
     ph_file = os.path.join(config.folder, "pretraining", "phonemes.txt")
     wd_file = os.path.join(config.folder, "pretraining", "words.txt")
     rank, world = _world()
     if world > 1:
-        # identical file order on every rank (DistributedSampler indexes into it); one rank builds the
-        # vocabulary files, the others read them
-        train_tg, valid_tg, test_tg = sorted(train_tg), sorted(valid_tg), sorted(test_tg)
+        # one rank builds the vocabulary files, the others read them
         import torch.distributed as dist
         if rank != 0:
             dist.barrier()

@@ -355,8 +355,11 @@ int slu_dropout_pool_fwd_planes(const float* x, const float* mask, int64_t m_st,
  * as above (row = t*B + b, or t*sub_batch + b % sub_batch on the stream of sub-batch b / sub_batch).  Random bits are used
  * economically: for p == 0.5 and C % 128 == 0 (every layer of the reference cfgs) the four words of block
  * (row * C/128 + c/128) ARE the 128 keep bits of channels [128 (c/128), +128); otherwise element e = row*C + c is kept iff
- * the 16-bit draw e%2 of word (e/2)%4 of block e/8 is below round((1-p) 2^16).  (The trainable layers' kernels above draw one
- * 24-bit uniform per element; the two streams are unrelated.)  C % 32 == 0, T <= 65535, bits 16-byte aligned.           */
+ * the 16-bit draw e%2 (0 = the low half) of word (e/2)%4 of block e/8 is below round((1-p) 2^16), i.e.
+ * min(65536, (unsigned)((1.0 - (double)p) * 65536.0 + 0.5)) on the float p: at p <= 2^-17 every bit is set.  (The
+ * trainable layers' kernels above draw one 24-bit uniform per element, kept iff (float)(w >> 8) * 2^-24 < 1.0f - p and
+ * then scaled by 1.0f / (1.0f - p); the two streams are unrelated.)  C % 32 == 0, T <= 65535, bits 16-byte aligned.
+ * tests/dropout_ref.py restates both rules on the host; every kernel that draws a mask is pinned to it bit for bit.    */
 int slu_dropout_bits(uint32_t* bits, float p, uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
                      int64_t sub_batch, uint64_t sub_stride, int64_t T, int64_t B, int64_t C, void* stream);
 /* Waveform augmentation in front of stage 0 (ABI 10, added without a version step as the beam-search entry points were;
