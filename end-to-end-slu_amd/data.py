@@ -24,6 +24,8 @@ from collections import Counter
 import numpy as np
 import torch
 
+from slu_hip import knobs as _knobs
+
 
 class Config:
     def __init__(self):
@@ -229,21 +231,16 @@ def one_hot(letters, S):
 
 def mask_padding_enabled():
     """SLU_MASK_PADDING: "0" (default) — batches are (x, y); "1" — CollateWavsSLU adds the per-utterance sample counts."""
-    v = os.environ.get("SLU_MASK_PADDING", "0")
-    if v not in ("0", "1"):
-        raise ValueError("SLU_MASK_PADDING=%r: expected 0 or 1" % (v,))
-    return v == "1"
+    return _knobs.flag("SLU_MASK_PADDING")
 
 
 def mask_asr_enabled():
     """SLU_MASK_ASR: "0" (default) — ASR batches are (x, y_phoneme, y_word), also under SLU_MASK_PADDING=1; "1" —
     CollateWavsASR adds the snippets' own sample counts.  Needs SLU_MASK_PADDING=1."""
-    v = os.environ.get("SLU_MASK_ASR", "0")
-    if v not in ("0", "1"):
-        raise ValueError("SLU_MASK_ASR=%r: expected 0 or 1" % (v,))
-    if v == "1" and not mask_padding_enabled():
+    on = _knobs.flag("SLU_MASK_ASR")
+    if on and not mask_padding_enabled():
         raise ValueError("SLU_MASK_ASR=1 needs SLU_MASK_PADDING=1: the lengths come from the collate function")
-    return v == "1"
+    return on
 
 
 class CollateWavsSLU:

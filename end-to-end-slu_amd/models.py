@@ -22,6 +22,7 @@ and `predict_intents` run the fused stage plan.  There is no CPU path: without a
 the forward methods raise.  The seq2seq head (models.py:381-651: Seq2SeqEncoder, Attention, DecoderRNN,
 Seq2SeqDecoder with beam search) is provided on the same kernels (ops.Seq2SeqDecoderFn).
 """
+import collections
 import contextlib
 import os
 import sys
@@ -31,6 +32,7 @@ import torch
 
 from slu_hip import ops as _ops
 from slu_hip import lib as _lib
+from slu_hip import knobs as _knobs
 
 
 # ------------------------------------------------------------------------------------------------
@@ -127,23 +129,6 @@ def _augment(x, training_augment):
         return _ops.wave_augment(x, flags, *stream)
 
 
-def _augment_len(x, host):
-    """_augment on a batch whose rows' lengths are known (SLU_MASK_AUGMENT=1; Model._forward_len): x (B, T) fp32 / PCM16
-    device tensor, host = its rows' sample counts -> (x_aug dense fp32, exactly zero from every row's new end on; the new
-    sample counts, computed on the host — ops.tempo_out_lengths / augment_out_lengths, no device read).  Same stream, order
-    and knobs as _augment; a device-resident step index has no host mirror and is refused by the caller."""
-    seed = ((_DropoutState.seed if _DropoutState.seed is not None else torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF) ^ AUGMENT_KEY
-    flags, offset, sub = _ops.augment_flags(), _DropoutState.current * 16, _DropoutState.sub_batch
-    T = x.shape[1]
-    with torch.no_grad():
-        n_dev = torch.tensor(host, dtype=torch.int32).to(x.device, non_blocking=True)
-        if _ops.tempo_enabled():
-            x, n_dev = _ops.wave_tempo_len(x, n_dev, seed, offset, None, sub)
-            host = _ops.tempo_out_lengths(host, T, seed, offset, sub)
-        x, _ = _ops.wave_augment_len(x, n_dev, flags, seed, offset, None, sub)
-        return x, _ops.augment_out_lengths(host, T, flags, seed, offset, sub)
-
-
 class _FrozenMath:
     """State of the frozen stages' arithmetic in the guarded mode (SLU_FROZEN_MATH=auto; slu_hip/guard.py)."""
     scope = None        # the RangeGuard watching the evaluation that is running now: only then auto = f16x2
@@ -212,17 +197,11 @@ def guarded_frozen_nsplit(model=None):
     return 2 if (pm is None or pm.f16x2_allowed()) else 3
 
 
-_BEAM_SEARCH = ("device", "host")
-
-
 def beam_search_mode():
     """SLU_BEAM_SEARCH: where the seq2seq decoder's beam search keeps its books when Model.predict_intents / decode_intents
     decode: "device" (default) — Seq2SeqDecoder.search, slu_beam_select after every step and one slu_beam_backtrack;
     "host" — Seq2SeqDecoder.infer, torch bookkeeping as in the reference.  Same hypotheses, same scores."""
-    mode = os.environ.get("SLU_BEAM_SEARCH", "device")
-    if mode not in _BEAM_SEARCH:
-        raise ValueError("SLU_BEAM_SEARCH=%r: expected one of %s" % (mode, sorted(_BEAM_SEARCH)))
-    return mode
+    return _knobs.one_of("SLU_BEAM_SEARCH", "device", ("device", "host"))
 
 
 def beam_eos_enabled():
@@ -230,43 +209,28 @@ def beam_eos_enabled():
     expanded for all U steps and the log-probabilities of what follows <eos> count; "1" — hypotheses that have emitted
     <eos> are finished (the rule in Seq2SeqDecoder.infer): Model.predict_intents / decode_intents / decode_nbest pass
     eos = Sy_intent.index("<eos>") to the search SLU_BEAM_SEARCH selects, which stops once every utterance is done."""
-    v = os.environ.get("SLU_BEAM_EOS", "0")
-    if v not in ("0", "1"):
-        raise ValueError("SLU_BEAM_EOS=%r: expected 0 or 1" % (v,))
-    return v == "1"
+    return _knobs.flag("SLU_BEAM_EOS")
 
 
 def mask_train_cnn_enabled():
     """SLU_MASK_TRAIN_CNN: "0" (default) — Model.forward(lengths=...) refuses a trainable CNN block; "1" — such a block
     runs length-aware inside autograd (ops.SincBlockLenFn / ConvBlockLenFn), so masked training goes on when the unfreezing
     reaches the convolutions, or with nothing frozen."""
-    v = os.environ.get("SLU_MASK_TRAIN_CNN", "0")
-    if v not in ("0", "1"):
-        raise ValueError("SLU_MASK_TRAIN_CNN=%r: expected 0 or 1" % (v,))
-    return v == "1"
+    return _knobs.flag("SLU_MASK_TRAIN_CNN")
 
 
 def mask_seq2seq_enabled():
     """SLU_MASK_SEQ2SEQ: "0" (default) — every lengths=... call refuses a seq2seq model; "1" — the intent encoder runs
     length-aware and the decoder's attention ranges over every utterance's own frames (ops.attention_len_fwd / _bwd):
     Model.forward(lengths=...), eval_group, predict_intents, decode_intents and decode_nbest take lengths for seq2seq models."""
-    v = os.environ.get("SLU_MASK_SEQ2SEQ", "0")
-    if v not in ("0", "1"):
-        raise ValueError("SLU_MASK_SEQ2SEQ=%r: expected 0 or 1" % (v,))
-    return v == "1"
+    return _knobs.flag("SLU_MASK_SEQ2SEQ")
 
 
 def mask_augment_enabled():
     """SLU_MASK_AUGMENT: "0" (default) — a masked training step (Model.forward(lengths=...) in train() mode) refuses a model
-    with augment=True; "1" — its waveforms pass through the length-taking augmentation kernels (_augment_len) and the
+    with augment=True; "1" — its waveforms pass through the length-taking augmentation kernels (_enter_len) and the
     stages run on the lengths behind them.  training.mask_augment_enabled adds the Trainer's rule: 1 needs SLU_MASK_TRAIN=1."""
-    v = os.environ.get("SLU_MASK_AUGMENT", "0")
-    if v not in ("0", "1"):
-        raise ValueError("SLU_MASK_AUGMENT=%r: expected 0 or 1" % (v,))
-    return v == "1"
-
-
-_MASK_FROZEN_MATH = ("fp32", "bf16x3")
+    return _knobs.flag("SLU_MASK_AUGMENT")
 
 
 def mask_frozen_math_mode():
@@ -275,10 +239,7 @@ def mask_frozen_math_mode():
     gradient runs its convolution / input projection / recurrence on the split-precision kernels (ops.wconv_fwd_bf16,
     ops.gemm_a32, ops.gru_seq_fwd_len_bf16) where they take its shape, else its fp32 form.  A knob of its own: it does not
     follow SLU_FROZEN_MATH, and f16x2 / auto are refused (the range guard is not wired through the length-aware path)."""
-    mode = os.environ.get("SLU_MASK_FROZEN_MATH", "fp32")
-    if mode not in _MASK_FROZEN_MATH:
-        raise ValueError("SLU_MASK_FROZEN_MATH=%r: expected one of %s" % (mode, sorted(_MASK_FROZEN_MATH)))
-    return mode
+    return _knobs.one_of("SLU_MASK_FROZEN_MATH", "fp32", ("fp32", "bf16x3"))
 
 
 def _refuse_seq2seq_lengths():
@@ -1034,10 +995,64 @@ def _check_len_stages(stages):
                                 ", ".join(map(str, _ops.LEN_HIDDEN_SIZES))))
 
 
+def _enter_len(pm, x, lengths, stages, train_ok=False, rng_step=None, augment=False, labels=()):
+    """The one way into a lengths=... call of `pm` (a PretrainedModel) that runs `stages`: every host-side refusal, then —
+    the first launches — the waveform preamble.  -> (x on the device, fp32, exactly zero from every row's end on; the rows'
+    sample counts on the host).
+    train_ok: a forward entry (Model / PretrainedModel.forward): train() mode is allowed, the dropout step `rng_step` (None
+    = the next one; a device-resident one is refused: it has no host mirror) is reserved and a trainable CNN block needs
+    SLU_MASK_TRAIN_CNN=1; else the call is inference only.  labels: (y, name, index of the stage whose output frames y
+    labels) — each y (or None) must have the dense call's (B, T') int64 shape.  augment: the waveforms pass through
+    _augment's effects on the length-taking kernels (SLU_MASK_AUGMENT=1) instead of the tail mask: same stream, order and
+    knobs, a PCM16 batch taken as it is; the new sample counts come from the host mirrors (ops.tempo_out_lengths /
+    augment_out_lengths, no device read)."""
+    if train_ok and torch.is_tensor(rng_step):
+        raise ValueError("lengths: captured steps (a device-resident rng_step) are not supported")
+    if x.dim() != 2:
+        raise ValueError("lengths: expected a (B, T) waveform batch")
+    if pm.training and not train_ok:
+        raise ValueError("lengths: the length-aware path is inference only (dropout is not applied): call eval() first")
+    B, T = x.shape
+    host = _host_lengths(lengths, B, T)
+    _check_len_stages(stages)
+    frames = _stage_lengths(stages, [T]) if labels else None
+    for y, name, k in labels:
+        t_out = frames[k][0]
+        if y is not None and (y.dim() != 2 or y.shape[0] != B or y.shape[1] != t_out or y.dtype != torch.int64):
+            raise ValueError("lengths: %s must be int64 of shape (%d, %d), the dense call's, got %s %s"
+                             % (name, B, t_out, y.dtype, tuple(y.shape)))
+    if augment and not mask_augment_enabled():
+        raise ValueError("lengths: augment=True is not supported (the augmentation moves the utterances' ends)")
+    if train_ok:
+        _refuse_trainable_cnn_lengths(pm._cnn_stages)
+    (x,) = pm._to_device(x)
+    pm._cnn_stages[-1].time_major = True
+    if train_ok:
+        _DropoutState.current = next_rng_step() if rng_step is None else rng_step
+    with torch.no_grad():
+        if not (augment and x.dtype == torch.int16):
+            x = _ops.pcm16_to_f32(x) if x.dtype == torch.int16 else x.float()
+        n_dev = torch.tensor(host, dtype=torch.int32).to(x.device, non_blocking=True)
+        if not augment:
+            return _ops.mask_rows_len(x, n_dev), host                # the first stage's input tail
+        seed = ((_DropoutState.seed if _DropoutState.seed is not None else torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF) ^ AUGMENT_KEY
+        flags, offset, sub = _ops.augment_flags(), _DropoutState.current * 16, _DropoutState.sub_batch
+        if _ops.tempo_enabled():
+            x, n_dev = _ops.wave_tempo_len(x, n_dev, seed, offset, None, sub)
+            host = _ops.tempo_out_lengths(host, T, seed, offset, sub)
+        x, _ = _ops.wave_augment_len(x, n_dev, flags, seed, offset, None, sub)
+        return x, _ops.augment_out_lengths(host, T, flags, seed, offset, sub)
+
+
+# what _run_stages_len returns: the last stage's output, its valid lengths on the host and on the device (a row of the
+# table), and — pack — (the exclusive prefix sum of those lengths on the device, N = their sum), else None
+_LenRun = collections.namedtuple("_LenRun", "out n_host n_dev pack")
+
+
 def _run_stages_len(stages, h, lengths, training=None, pack=False):
     """Length-aware evaluation of `stages` (no dropout, no autograd): h = the first stage's input, whose frames at or
-    beyond lengths[b] are zero; -> (output, its valid lengths).  The host computes every stage's valid lengths
-    (_stage_lengths) and sends them to the device in ONE int32 table.  By default the exact fp32 kernels — slu_wconv_fwd,
+    beyond lengths[b] are zero; -> _LenRun.  The host computes every stage's valid lengths and sends them to the device in
+    ONE int32 table.  By default the exact fp32 kernels — slu_wconv_fwd,
     slu_gemm_f32, slu_gru_seq_fwd_len — whatever SLU_FROZEN_MATH says: both sides of the invariant (an utterance in a
     padded batch / alone) then differ by summation order only.  SLU_MASK_FROZEN_MATH=bf16x3 (mask_frozen_math_mode) moves
     the frozen stages' contractions to the split-precision kernels, stage by stage (_ConvStage / _RnnStage._len_split).
@@ -1046,39 +1061,34 @@ def _run_stages_len(stages, h, lengths, training=None, pack=False):
     table then also carries, behind the stages' rows, one row of input frames * channels for every conv block that follows
     a stage with a trainable parameter (what ops.ConvBlockLenFn masks the gradient of its input with).
     pack: a frame head follows (ops.FrameHeadLenFn) — the table's last row is the exclusive prefix sum of the output's
-    valid lengths (ops.frame_pack_plan) and the result gains a fourth entry, (that row on the device, N = their sum)."""
+    valid lengths (ops.frame_pack_plan)."""
     mask_frozen_math_mode()          # a bad value of the knob is an error before any launch
-    rows = [list(lengths)]
-    for st in stages:
-        if isinstance(st, _ConvStage):
-            rows.append([st.conv_len(n) for n in rows[-1]])      # valid frames of the raw convolution
-            rows.append([st.out_len(n) for n in rows[-2]])
-        else:
-            rows.append([st.out_len(n) for n in rows[-1]])
-    n_rows, k, flat, grad_above = len(rows), 0, {}, False
-    for st in stages:
+    # one pass: the stages' rows (a conv block has two: the raw convolution's valid frames, then the block's), the flat rows,
+    # and per stage the rows it reads: (its own lengths, its flat row among `flat` or None)
+    rows, flat, plan, k = [list(lengths)], [], [], 0
+    for i, st in enumerate(stages):
+        conv = isinstance(st, _ConvStage)
+        if conv:
+            rows.append([st.conv_len(n) for n in rows[k]])
+        rows.append([st.out_len(n) for n in rows[k]])
         # a conv block behind a trainable stage masks the gradient of its input: input frames * channels (the row table of
-        # slu_mask_rows_len on the (B, L * C) view), appended to the same table behind the stages' rows
-        if training is not None and isinstance(st, _ConvStage) and grad_above:
-            flat[k] = len(rows)
-            rows.append([n * st.in_channels() for n in rows[k]])
-        grad_above = grad_above or any(q.requires_grad for q in st.parameters())
-        k += 2 if isinstance(st, _ConvStage) else 1
-    if pack:
-        offsets, n_total = _ops.frame_pack_plan(rows[n_rows - 1])
-        rows.append(offsets)
-    table = torch.tensor(rows, dtype=torch.int32).to(h.device, non_blocking=True)
-    k = 0
-    for st in stages:
-        if isinstance(st, _ConvStage):
-            h = (st.run_len(h, table[k + 1]) if training is None
-                 else st.run_len_train(h, table[k + 1], training, table[flat[k]] if k in flat else None))
+        # slu_mask_rows_len on the (B, L * C) view).  Asked at the conv blocks only: the parameter walks are host time
+        masks_dx = (conv and training is not None
+                    and any(q.requires_grad for above in stages[:i] for q in above.parameters()))
+        if masks_dx:
+            flat.append([n * st.in_channels() for n in rows[k]])
+        plan.append((k + 1 if conv else k, len(flat) - 1 if masks_dx else None))
+        k += 2 if conv else 1
+    offsets, n_total = _ops.frame_pack_plan(rows[k]) if pack else (None, None)
+    table = torch.tensor(rows + flat + ([offsets] if pack else []), dtype=torch.int32).to(h.device, non_blocking=True)
+    for st, (own, dx) in zip(stages, plan):
+        if training is None:
+            h = st.run_len(h, table[own])
+        elif isinstance(st, _ConvStage):
+            h = st.run_len_train(h, table[own], training, None if dx is None else table[len(rows) + dx])
         else:
-            h = st.run_len(h, table[k]) if training is None else st.run_len_train(h, table[k], training)
-        k += 2 if isinstance(st, _ConvStage) else 1
-    if pack:
-        return h, rows[n_rows - 1], table[k], (table[len(rows) - 1], n_total)
-    return h, rows[n_rows - 1], table[k]
+            h = st.run_len_train(h, table[own], training)
+    return _LenRun(h, rows[k], table[k], (table[-1], n_total) if pack else None)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1146,9 +1156,9 @@ class _ConvStage:
         a gradient), runs as ops.SincBlockLenFn / ConvBlockLenFn with the dropout inside autograd; n_in_flat = the int32
         device lengths of h times its channels (what the gradient of h is masked with).  A frozen one runs the same
         kernels outside autograd, without route bytes."""
+        drop = self.drop > 0.0 and training
+        tm = self.time_major and not drop
         if any(q.requires_grad for q in self.parameters()) or h.requires_grad:
-            drop = self.drop > 0.0 and training
-            tm = self.time_major and not drop
             if self.is_sinc:
                 h = _ops.SincBlockLenFn.apply(h, self.conv.filt_b1, self.conv.filt_band, n_conv, self.conv.Filt_dim,
                                               self.conv.fs, self.conv.stride, self.pool, self.slope, tm, self.do_abs)
@@ -1157,17 +1167,21 @@ class _ConvStage:
                     h = h.unsqueeze(2)
                 h = _ops.ConvBlockLenFn.apply(h, self.conv.weight, self.conv.bias, n_conv, n_in_flat, self.conv.stride,
                                               self.do_abs, self.pool, self.slope, tm)
-            if drop:
-                p, mask, seed, offset = _dropout_args(self.drop_name, self.site, self.drop, training, cnn=True)
-                h = _DropOnlyFn.apply(h.contiguous(), p, mask, seed, offset)
-            return h.transpose(0, 1).contiguous() if self.time_major and not tm else h
-        if not (self.drop > 0.0 and training):
-            return self.run_len(h, n_conv)
-        h = self.run_len(h, n_conv, time_major=False)
-        p, mask, seed, offset = _dropout_args(self.drop_name, self.site, self.drop, training, cnn=True)
+            return self._drop_tail(h, training, tm)
+        h = self.run_len(h, n_conv, time_major=tm)
+        if not drop:                             # run_len has written the layout the next stage reads
+            return h
         with torch.no_grad():
+            return self._drop_tail(h, training, tm)
+
+    def _drop_tail(self, h, training, tm):
+        """What follows a block's kernels: its nn.Dropout (reference models.py:217-220) when it has one and `training` — on
+        the channels-last tensor, from the same step-indexed Philox stream as the RNN sites (or the injected mask, given in
+        the reference's (B,C,L) shape) — then the hand-over to time-major where the kernels did not write it (tm)."""
+        if self.drop > 0.0 and training:
+            p, mask, seed, offset = _dropout_args(self.drop_name, self.site, self.drop, training, cnn=True)
             h = _DropOnlyFn.apply(h.contiguous(), p, mask, seed, offset)
-        return h.transpose(0, 1).contiguous() if self.time_major else h
+        return h.transpose(0, 1).contiguous() if self.time_major and not tm else h
 
     def _frozen_cache(self, nsplit):
         """What a FROZEN block recomputed per call in round 2: the Sinc filterbank and the filters packed in MFMA
@@ -1201,9 +1215,8 @@ class _ConvStage:
         """h: (B,T) for the first block, else channels-last (B,L,C).
         out_planes: the consumer is a frozen split-precision GRU layer — hand over bf16 planes (SplitAct) when this
         block runs on the split-precision kernel itself, time-major and without dropout (else plain fp32)."""
-        time_major = self.time_major
         fused_pool = self.pool in (1, 2)
-        tm = time_major and fused_pool and self.drop == 0.0
+        tm = self.time_major and fused_pool and self.drop == 0.0
         pool = self.pool if fused_pool else 1
         slope = self.slope if fused_pool else 1.0
         # FROZEN block with nothing to differentiate: the convolution on the split-precision kernels, outside
@@ -1231,12 +1244,7 @@ class _ConvStage:
                                         absmax=scope.word(self.idx) if (scope is not None and nsplit == 2) else None)
                 if planes:
                     return h
-            if self.drop > 0.0 and training:
-                p, mask, seed, offset = _dropout_args(self.drop_name, self.site, self.drop, training, cnn=True)
-                h = _DropOnlyFn.apply(h.contiguous(), p, mask, seed, offset)
-            if time_major and not tm:
-                h = h.transpose(0, 1).contiguous()
-            return h
+            return self._drop_tail(h, training, tm)
         if isinstance(h, _ops.RowTable):
             raise _lib.SluHipError("a row-pointer table can only be read by the split-precision first block")
         if h.dtype == torch.int16:             # PCM16 batch, first block on the exact fp32 kernels: sample / 32768
@@ -1252,14 +1260,7 @@ class _ConvStage:
                                        self.do_abs and fused_pool, pool, slope, tm)
         if not fused_pool:          # pool widths the convolution's epilogue does not fuse (> 2): slu_pool_act_*
             h = _ops.PoolActFn.apply(h, self.pool, self.do_abs, self.slope, False)
-        if self.drop > 0.0 and training:
-            # nn.Dropout of the CNN block (models.py:217-220) on the same step-indexed Philox stream as
-            # the RNN sites (or the injected mask, given in the reference's (B,C,L) shape)
-            p, mask, seed, offset = _dropout_args(self.drop_name, self.site, self.drop, training, cnn=True)
-            h = _DropOnlyFn.apply(h.contiguous(), p, mask, seed, offset)
-        if time_major and not tm:
-            h = h.transpose(0, 1).contiguous()
-        return h
+        return self._drop_tail(h, training, tm)
 
 
 class _RnnStage:
@@ -1300,25 +1301,29 @@ class _RnnStage:
             g._packed_ih = (key, _ops.gemm_bf16_pack(w_ih.detach(), 3))
         return _ops.gemm_a32(x2, g._packed_ih[1], b_ih.detach(), N, 3)
 
+    def _recur_len(self, xt, n_in, reserve_op):
+        """Projection + recurrence of the layer outside autograd (the caller holds no_grad): xt time-major (T, B, I), n_in
+        int32 device lengths -> (T, B, D*H).  slu_gemm_f32 (the padded rows' projections are b_ih: never read) and the exact
+        length-aware recurrence — slu_gru_seq_fwd_len, or the masked step's slu_gru_seq_fwd_len_rsv without a reserve
+        (reserve_op) — or (_len_split) both on bf16x3: slu_gemm_bf16_a32, slu_gru_seq_fwd_len_bf16."""
+        g = self.gru
+        xt = xt.contiguous()
+        T, B, I = xt.shape
+        w_ih, b_ih = g._stacked_ih()
+        rev = (g.weight_hh_l0_reverse.detach(), g.bias_hh_l0_reverse.detach()) if g.bidirectional else (None, None)
+        hh = (g.weight_hh_l0.detach(), rev[0], g.bias_hh_l0.detach(), rev[1], n_in, T, B, g.hidden_size,
+              2 if g.bidirectional else 1)
+        if self._len_split(xt):
+            return _ops.gru_seq_fwd_len_bf16(self._gx_len_split(xt.view(T * B, I), w_ih, b_ih), *hh)
+        gx = _ops.gemm(xt.view(T * B, I), w_ih.detach().t(), b_ih.detach())
+        return _ops.gru_seq_fwd_len_rsv(gx, *hh, False)[0] if reserve_op else _ops.gru_seq_fwd_len(gx, *hh)
+
     def run_len(self, xt, n_in):
         """Length-aware evaluation (no dropout): xt time-major (T, B, I) with zero rows at t >= n_in[b],
-        n_in int32 device lengths -> (ceil(T / factor), B, D*H), zero beyond ceil(n / factor).  slu_gemm_f32 (the padded
-        rows' projections are b_ih: never read), slu_gru_seq_fwd_len, slu_seq_pool_len_fwd — or (_len_split) the projection
-        and the recurrence of a frozen layer on bf16x3: slu_gemm_bf16_a32, slu_gru_seq_fwd_len_bf16."""
-        g = self.gru
+        n_in int32 device lengths -> (ceil(T / factor), B, D*H), zero beyond ceil(n / factor): _recur_len, then
+        slu_seq_pool_len_fwd."""
         with torch.no_grad():
-            xt = xt.contiguous()
-            T, B, I = xt.shape
-            H, D = g.hidden_size, 2 if g.bidirectional else 1
-            w_ih, b_ih = g._stacked_ih()
-            rev = (g.weight_hh_l0_reverse.detach(), g.bias_hh_l0_reverse.detach()) if g.bidirectional else (None, None)
-            if self._len_split(xt):
-                gx = self._gx_len_split(xt.view(T * B, I), w_ih, b_ih)
-                out = _ops.gru_seq_fwd_len_bf16(gx, g.weight_hh_l0.detach(), rev[0], g.bias_hh_l0.detach(), rev[1], n_in, T, B,
-                                                H, D)
-            else:
-                gx = _ops.gemm(xt.view(T * B, I), w_ih.detach().t(), b_ih.detach())
-                out = _ops.gru_seq_fwd_len(gx, g.weight_hh_l0.detach(), rev[0], g.bias_hh_l0.detach(), rev[1], n_in, T, B, H, D)
+            out = self._recur_len(xt, n_in, False)
             if self.factor > 1:
                 out = _ops.seq_pool_len_fwd(out, n_in, self.method, self.factor)
             return out
@@ -1330,8 +1335,8 @@ class _RnnStage:
         run_len, its projection and recurrence on bf16x3 (the dropout + pooling launch, and so every draw, is the same)."""
         g = self.gru
         p, mask, seed, offset = _dropout_args(self.drop_name, self.site, self.p, training)
-        w_ih, b_ih = g._stacked_ih()
         if any(q.requires_grad for q in g.parameters()) or xt.requires_grad:
+            w_ih, b_ih = g._stacked_ih()
             if g.bidirectional:
                 ih = (g.weight_ih_l0, g.weight_ih_l0_reverse, g.bias_ih_l0, g.bias_ih_l0_reverse)
                 rev = (g.weight_hh_l0_reverse, g.bias_hh_l0_reverse)
@@ -1340,18 +1345,7 @@ class _RnnStage:
             return _ops.GRULayerLenFn.apply(xt, w_ih.detach(), b_ih.detach(), *ih, g.weight_hh_l0, g.bias_hh_l0, rev[0],
                                             rev[1], n_in, p, mask, seed, offset, self.method, self.factor)
         with torch.no_grad():
-            xt = xt.contiguous()
-            T, B, I = xt.shape
-            H, D = g.hidden_size, 2 if g.bidirectional else 1
-            rev = (g.weight_hh_l0_reverse.detach(), g.bias_hh_l0_reverse.detach()) if g.bidirectional else (None, None)
-            if self._len_split(xt):
-                gx = self._gx_len_split(xt.view(T * B, I), w_ih, b_ih)
-                out = _ops.gru_seq_fwd_len_bf16(gx, g.weight_hh_l0.detach(), rev[0], g.bias_hh_l0.detach(), rev[1], n_in, T, B,
-                                                H, D)
-            else:
-                gx = _ops.gemm(xt.view(T * B, I), w_ih.detach().t(), b_ih.detach())
-                out, _ = _ops.gru_seq_fwd_len_rsv(gx, g.weight_hh_l0.detach(), rev[0], g.bias_hh_l0.detach(), rev[1], n_in, T,
-                                                  B, H, D, False)
+            out = self._recur_len(xt, n_in, True)
             if p > 0.0 or self.factor > 1:
                 offset, offset_dev, sub_batch = offset if isinstance(offset, tuple) else (offset, None, 0)
                 assert sub_batch == 0
@@ -1612,52 +1606,27 @@ class PretrainedModel(torch.nn.Module):
         finally:
             _DropoutState.current_dev = None
 
-    def _len_plan(self, x, lengths, y_phoneme=None, y_word=None):
-        """Host side of a lengths=... call of this model, before any launch: -> (host lengths, phoneme-side stages, word
-        stages — none for pretraining_type 1 in a training call).  Refuses a bad batch shape, bad lengths, a hidden size
-        without a length-aware recurrence and labels that do not have the dense call's (B, T') / (B, T'') shapes."""
-        if x.dim() != 2:
-            raise ValueError("lengths: expected a (B, T) waveform batch")
-        B, T = x.shape
-        host = _host_lengths(lengths, B, T)
-        first = self._cnn_stages + self._phone_stages
-        word = list(self._word_stages) if (y_phoneme is None or self.pretraining_type != 1) else []
-        _check_len_stages(first + word)
-        frames = _stage_lengths(first + word, [T])
-        for y, name, t_out in ((y_phoneme, "y_phoneme", frames[len(first) - 1][0]),
-                               (y_word if word else None, "y_word", frames[-1][0])):
-            if y is not None and (y.dim() != 2 or y.shape[0] != B or y.shape[1] != t_out or y.dtype != torch.int64):
-                raise ValueError("lengths: %s must be int64 of shape (%d, %d), the dense call's, got %s %s"
-                                 % (name, B, t_out, y.dtype, tuple(y.shape)))
-        return host, first, word
-
     def _forward_len(self, x, y_phoneme, y_word, lengths, rng_step):
         """forward with per-utterance lengths (DESIGN.md section 7 "Lengths through ASR pre-training"): the waveform tail
         is zeroed, the CNN blocks and the phoneme layers run length-aware (_run_stages_len, as Model._forward_len: frozen
         stages outside autograd, trainable ones as ops.*LenFn), the phoneme head is ops.FrameHeadLenFn on the packed valid
-        frames; the phoneme features then feed the word layers and their head the same way, and autograd sums the two
-        gradients of the phoneme features.  In train() mode every dropout site draws the dense batch's masks.  Everything
-        that can be refused is refused here, on the host, before the first launch."""
-        if torch.is_tensor(rng_step):
-            raise ValueError("lengths: captured steps (a device-resident rng_step) are not supported")
-        host, first, word = self._len_plan(x, lengths, y_phoneme, y_word)
-        _refuse_trainable_cnn_lengths(self._cnn_stages)
-        x, y_phoneme, y_word = self._to_device(x, y_phoneme, y_word)
-        self._cnn_stages[-1].time_major = True
-        _DropoutState.current = next_rng_step() if rng_step is None else rng_step
-        with torch.no_grad():
-            x = _ops.pcm16_to_f32(x) if x.dtype == torch.int16 else x.float()
-            dev_len = torch.tensor(host, dtype=torch.int32).to(x.device, non_blocking=True)
-            x = _ops.mask_rows_len(x, dev_len)
-        ph_tm, n_p, n_p_dev, (off_p, rows_p) = _run_stages_len(first, x, host, training=self.training, pack=True)
+        frames; the phoneme features then feed the word layers (none for pretraining_type 1) and their head the same way,
+        and autograd sums the two gradients of the phoneme features.  In train() mode every dropout site draws the dense
+        batch's masks.  Everything that can be refused is refused on the host, before the first launch (_enter_len)."""
+        first = self._cnn_stages + self._phone_stages
+        word = list(self._word_stages) if (y_phoneme is None or self.pretraining_type != 1) else []
+        labels = ((y_phoneme, "y_phoneme", len(first) - 1), (y_word if word else None, "y_word", len(first + word) - 1))
+        x, host = _enter_len(self, x, lengths, first + word, train_ok=True, rng_step=rng_step, labels=labels)
+        y_phoneme, y_word = self._to_device(y_phoneme, y_word)
+        ph = _run_stages_len(first, x, host, training=self.training, pack=True)
         pl = self.phoneme_linear
-        phoneme_loss, phoneme_acc = _ops.FrameHeadLenFn.apply(ph_tm, n_p_dev.contiguous(), off_p.contiguous(), rows_p,
-                                                              pl.weight, pl.bias, y_phoneme)
+        phoneme_loss, phoneme_acc = _ops.FrameHeadLenFn.apply(ph.out, ph.n_dev.contiguous(), ph.pack[0].contiguous(),
+                                                              ph.pack[1], pl.weight, pl.bias, y_phoneme)
         if self.pretraining_type == 1:
             return phoneme_loss, torch.tensor([0.]), phoneme_acc, torch.tensor([0.])
-        wd_tm, _, n_w_dev, (off_w, rows_w) = _run_stages_len(word, ph_tm, n_p, training=self.training, pack=True)
+        wd = _run_stages_len(word, ph.out, ph.n_host, training=self.training, pack=True)
         wl = self.word_linear
-        word_loss, word_acc = _ops.FrameHeadLenFn.apply(wd_tm, n_w_dev.contiguous(), off_w.contiguous(), rows_w,
+        word_loss, word_acc = _ops.FrameHeadLenFn.apply(wd.out, wd.n_dev.contiguous(), wd.pack[0].contiguous(), wd.pack[1],
                                                         wl.weight, wl.bias, y_word)
         return phoneme_loss, word_loss, phoneme_acc, word_acc
 
@@ -1666,23 +1635,19 @@ class PretrainedModel(torch.nn.Module):
         Linear layers on the packed valid frames only, and one scatter each that writes the zeros beyond them."""
         if self.training:
             raise ValueError("lengths: the length-aware path is inference only (dropout is not applied): call eval() first")
-        host, first, word = self._len_plan(x, lengths)
-        (x,) = self._to_device(x)
-        self._cnn_stages[-1].time_major = True
+        first = self._cnn_stages + self._phone_stages
+        x, host = _enter_len(self, x, lengths, self._stages())
         with torch.no_grad():
-            x = _ops.pcm16_to_f32(x) if x.dtype == torch.int16 else x.float()
-            dev_len = torch.tensor(host, dtype=torch.int32).to(x.device, non_blocking=True)
-            x = _ops.mask_rows_len(x, dev_len)
-            ph_tm, n_p, n_p_dev, pack_p = _run_stages_len(first, x, host, pack=True)
-            wd_tm, _, n_w_dev, pack_w = _run_stages_len(word, ph_tm, n_p, pack=True)
+            ph = _run_stages_len(first, x, host, pack=True)
+            wd = _run_stages_len(self._word_stages, ph.out, ph.n_host, pack=True)
 
-            def head(lin, h_tm, n_dev, pack):
-                T, B, _ = h_tm.shape
-                n_dev, off = n_dev.contiguous(), pack[0].contiguous()
-                hp, _ = _ops.frame_pack_len(h_tm, None, n_dev, off, pack[1])
+            def head(lin, run):
+                T, B, _ = run.out.shape
+                n_dev, off = run.n_dev.contiguous(), run.pack[0].contiguous()
+                hp, _ = _ops.frame_pack_len(run.out, None, n_dev, off, run.pack[1])
                 out = _ops.gemm(hp, lin.weight.detach().t(), lin.bias.detach())
                 return _ops.frame_unpack_len(out, n_dev, off, T, B).transpose(0, 1)
-            return head(self.phoneme_linear, ph_tm, n_p_dev, pack_p), head(self.word_linear, wd_tm, n_w_dev, pack_w)
+            return head(self.phoneme_linear, ph), head(self.word_linear, wd)
 
     def compute_posteriors(self, x, lengths=None):
         """(B,T) waveform -> (phoneme logits (B,T',num_phonemes), word logits (B,T'',vocabulary_size)).
@@ -1711,29 +1676,18 @@ class PretrainedModel(torch.nn.Module):
         return [r[0] for r in out] if single else out
 
     def _features_tm_len(self, x, lengths, more_stages=()):
-        """Length-aware evaluation of the encoder (+ more_stages): -> (time-major features, host lengths, device lengths).
-        Everything that can be refused is refused before the first launch, on the host."""
-        if x.dim() != 2:
-            raise ValueError("lengths: expected a (B, T) waveform batch")
-        if self.training:
-            raise ValueError("lengths: the length-aware path is inference only (dropout is not applied): call eval() first")
-        host = _host_lengths(lengths, x.shape[0], x.shape[1])
+        """Length-aware evaluation of the encoder (+ more_stages) -> _LenRun (time-major features, their host and device
+        lengths).  Everything that can be refused is refused before the first launch, on the host (_enter_len)."""
         stages = self._stages() + list(more_stages)
-        _check_len_stages(stages)
-        (x,) = self._to_device(x)
-        self._cnn_stages[-1].time_major = True
-        with torch.no_grad():
-            x = _ops.pcm16_to_f32(x) if x.dtype == torch.int16 else x.float()
-            dev_len = torch.tensor(host, dtype=torch.int32).to(x.device, non_blocking=True)
-            x = _ops.mask_rows_len(x, dev_len)                       # the first stage's input tail
-            return _run_stages_len(stages, x, host)
+        x, host = _enter_len(self, x, lengths, stages)
+        return _run_stages_len(stages, x, host)
 
     def compute_features(self, x, lengths=None):
         """(B,T) waveform -> (B,T',C) encoder features (reference models.py:349-361).
         lengths (not in the reference; None: the call above): the utterances' sample counts -> the features of every
         utterance as if it were run alone, zero at frames at or beyond stage_lengths(lengths)[-1] (eval mode only)."""
         if lengths is not None:
-            return self._features_tm_len(x, lengths)[0].transpose(0, 1)
+            return self._features_tm_len(x, lengths).out.transpose(0, 1)
         (x,) = self._to_device(x)
         _DropoutState.current = next_rng_step()
         return self._features_tm(x).transpose(0, 1)
@@ -1855,6 +1809,24 @@ class Model(torch.nn.Module):
             h = st.run(h, self.training)
         return h                                                 # (T,B,C) time-major
 
+    def _intent_features_tm_len(self, x, lengths):
+        """Length-aware encoder + intent layers (a seq2seq model's intent encoder, under SLU_MASK_SEQ2SEQ=1) -> (h
+        time-major, host lengths, device lengths of h)."""
+        if self.seq2seq:
+            _refuse_seq2seq_lengths()
+        run = self.pretrained_model._features_tm_len(x, lengths, self._intent_stages)
+        return run.out, run.n_host, run.n_dev
+
+    def _encode(self, x, lengths=None):
+        """What predict_intents, decode_intents and decode_nbest run in front of their head -> (h time-major, host lengths,
+        device lengths of h's valid frames; both None without lengths).  The call's dropout-stream index is reserved where
+        it always was: in front of the dense encoder, behind the length-aware one (which draws nothing)."""
+        if lengths is None:
+            return self._intent_features_tm(x), None, None
+        out = self._intent_features_tm_len(x, lengths)
+        _DropoutState.current = next_rng_step()
+        return out
+
     # -- split execution for the trainer's encoder look-ahead pipeline ---------------------------
     def frozen_prefix_len(self):
         """Leading encoder stages with no trainable parameter (the whole encoder for
@@ -1943,37 +1915,16 @@ class Model(torch.nn.Module):
         the teacher-forced decoder on the frame counts behind them.  In train() mode every dropout site draws the masks it
         draws without lengths (the dense batch's Philox stream or the injected masks), so with p = 0 or injected masks the gradients equal the
         mean of the alone runs' exactly, with Philox masks in distribution.  Everything that can be refused is refused
-        here, on the host, before the first launch."""
+        on the host, before the first launch (here and in _enter_len)."""
         if n_prefix > 0:
             raise ValueError("lengths: the look-ahead pipeline (n_prefix > 0) has no masked steps")
         if self.seq2seq:
             _refuse_seq2seq_lengths()
-        if torch.is_tensor(rng_step):
-            raise ValueError("lengths: captured steps (a device-resident rng_step) are not supported")
-        if x.dim() != 2:
-            raise ValueError("lengths: expected a (B, T) waveform batch")
         pm = self.pretrained_model
-        host = _host_lengths(lengths, x.shape[0], x.shape[1])
         stages = pm._stages() + list(self._intent_stages)
-        _check_len_stages(stages)
-        augment = self.augment and self.training
-        if augment and not mask_augment_enabled():
-            raise ValueError("lengths: augment=True is not supported (the augmentation moves the utterances' ends)")
-        _refuse_trainable_cnn_lengths(pm._cnn_stages)
-        (x,) = pm._to_device(x)
-        pm._cnn_stages[-1].time_major = True
-        _DropoutState.current = next_rng_step() if rng_step is None else rng_step
-        if augment:
-            # the kernels read the lengths, take a PCM16 batch as it is and leave the tail beyond the new ends zero
-            if x.dtype != torch.int16:
-                x = x.float()
-            x, host = _augment_len(x, host)
-        else:
-            with torch.no_grad():
-                x = _ops.pcm16_to_f32(x) if x.dtype == torch.int16 else x.float()
-                dev_len = torch.tensor(host, dtype=torch.int32).to(x.device, non_blocking=True)
-                x = _ops.mask_rows_len(x, dev_len)
-        h, _, n_dev = _run_stages_len(stages, x, host, training=self.training)
+        x, host = _enter_len(pm, x, lengths, stages, train_ok=True, rng_step=rng_step, augment=self.augment and self.training)
+        run = _run_stages_len(stages, x, host, training=self.training)
+        h, n_dev = run.out, run.n_dev
         if self.seq2seq:
             # loss = -mean over the padded batch's rows of log p(y_b | x_b[:lengths[b]]); a host zero for the accuracy, as
             # the dense branch (forward_from)
@@ -1989,7 +1940,7 @@ class Model(torch.nn.Module):
     def one_hot_to_string(self, input, S):
         """input (T, |S|) one-hot rows, S list of labels -> the string (reference models.py:731-737; the strips are
         character-set strips, as the reference applies them)."""
-        return "".join([S[c] for c in input.max(dim=1)[1]]).lstrip("<sos>").rstrip("<eos>")
+        return _labels_to_string(input.max(dim=1)[1], S)
 
     def stage_lengths(self, lengths):
         """PretrainedModel.stage_lengths continued through the intent layers: one entry per fused stage, the last one
@@ -1998,13 +1949,6 @@ class Model(torch.nn.Module):
         out = _stage_lengths(self.pretrained_model._stages() + list(self._intent_stages),
                              [lengths] if single else _as_int_list(lengths))
         return [r[0] for r in out] if single else out
-
-    def _intent_features_tm_len(self, x, lengths):
-        """Length-aware encoder + intent layers (a seq2seq model's intent encoder, under SLU_MASK_SEQ2SEQ=1) -> (h
-        time-major, host lengths, device lengths of h)."""
-        if self.seq2seq:
-            _refuse_seq2seq_lengths()
-        return self.pretrained_model._features_tm_len(x, lengths, self._intent_stages)
 
     def eval_group(self, xs, ys, lengths=None):
         """Evaluation (no dropout, no autograd) of several equally-shaped batches in ONE pass through the
@@ -2015,80 +1959,78 @@ class Model(torch.nn.Module):
         evaluation: every utterance contributes the loss / correctness of the utterance run alone.  A seq2seq model
         (SLU_MASK_SEQ2SEQ=1) is evaluated batch by batch: the (loss, host zero) of forward(lengths=...) without autograd."""
         assert not self.training
-        pm = self.pretrained_model
+        pm, host = self.pretrained_model, None
         if lengths is not None:
             if len(lengths) != len(xs):
                 raise ValueError("lengths: %d entries for %d batches" % (len(lengths), len(xs)))
             if self.seq2seq:
                 with torch.no_grad():
                     return [self._forward_len(x, y, l, None, 0) for x, y, l in zip(xs, ys, lengths)]
-            B = xs[0].shape[0]
             host = []
             for x, l in zip(xs, lengths):
                 host += _host_lengths(l, x.shape[0], x.shape[1])
-            dev = next(self.parameters()).device if next(self.parameters()).is_cuda else None
-            x_cat = torch.cat([x.to(dev, non_blocking=True) if dev is not None else x for x in xs]) if len(xs) > 1 else xs[0]
-            h, _, n_dev = self._intent_features_tm_len(x_cat, host)
-            cls = self.intent_layers[-2]
-            out = []
-            for k, y in enumerate(ys):
-                hk = h[:, k * B:(k + 1) * B].contiguous() if len(xs) > 1 else h.contiguous()
-                la, _, _, _ = _ops.cls_maxpool_len_fwd(hk, cls.weight.detach(), cls.bias.detach(),
-                                                       n_dev[k * B:(k + 1) * B].contiguous(),
-                                                       y.to(h.device).contiguous(), tuple(self.values_per_slot))
-                out.append((la[0], la[1]))
-            return out
         with torch.no_grad():
             dev = next(self.parameters()).device
             B = xs[0].shape[0]
-            x_cat = torch.cat([x.to(dev, non_blocking=True) for x in xs]) if len(xs) > 1 else pm._to_device(xs[0])[0]
-            h = pm.run_stages(x_cat, 0, len(pm._stages()))
-            for st in self._intent_stages:
-                h = st.run(h, False)
-            cls = self.intent_layers[-2]
+            x_cat = torch.cat([x.to(dev, non_blocking=True) for x in xs]) if len(xs) > 1 else xs[0]
+            if host is None:                         # (an evaluation reserves no dropout step: it draws nothing)
+                h, n_dev = pm._features_tm(pm._to_device(x_cat)[0]), None
+                for st in self._intent_stages:
+                    h = st.run(h, False)
+            else:
+                h, _, n_dev = self._intent_features_tm_len(x_cat, host)
+            cls, slots = self.intent_layers[-2], tuple(self.values_per_slot)
             out = []
             for k, y in enumerate(ys):
-                hk = h[:, k * B:(k + 1) * B].contiguous() if len(xs) > 1 else h.contiguous()
-                la, _, _, _, _ = _ops.cls_maxpool_ce_fwd(hk, cls.weight, cls.bias, y.to(dev).contiguous(),
-                                                         tuple(self.values_per_slot), False)
+                rows = slice(k * B, (k + 1) * B)
+                hk, y = h[:, rows].contiguous() if len(xs) > 1 else h.contiguous(), y.to(h.device).contiguous()
+                if n_dev is None:
+                    la = _ops.cls_maxpool_ce_fwd(hk, cls.weight, cls.bias, y, slots, False)[0]
+                else:
+                    la = _ops.cls_maxpool_len_fwd(hk, cls.weight.detach(), cls.bias.detach(), n_dev[rows].contiguous(), y,
+                                                  slots)[0]
                 out.append((la[0], la[1]))
         return out
 
     def predict_intents(self, x, lengths=None):
-        """-> (intent_logits (B, num_values_total), predicted_intent (B, num_slots)) (models.py:830-846)
+        """-> (intent_logits (B, num_values_total), predicted_intent (B, num_slots)) (models.py:830-846); a seq2seq model:
+        (scores (4, B), beam (4, B, U, |Sy|) one-hot) of the beam search, width 4 (models.py:848-851).
         lengths (not in the reference; None: the call as it was): the utterances' sample counts, each in [1, T] ->
         padding-invariant inference: row b's logits are those of x[b:b+1, :lengths[b]] run alone (eval mode, fixed-slot
         models, GRU hidden sizes 16 / 32 / 64 / 128; exact fp32 kernels whatever SLU_FROZEN_MATH says).  A seq2seq model
-        (SLU_MASK_SEQ2SEQ=1): the beam search below on the lengths — utterance b's hypotheses and scores are those of
+        (SLU_MASK_SEQ2SEQ=1): the beam search on the lengths — utterance b's hypotheses and scores are those of
         x[b:b+1, :lengths[b]] searched alone."""
-        if lengths is not None:
-            h, n_host, n_dev = self._intent_features_tm_len(x, lengths)
-            _DropoutState.current = next_rng_step()
-            if self.seq2seq:
-                enc = h.contiguous().transpose(0, 1)
-                if beam_search_mode() == "host":
-                    return self.decoder.infer(enc, self.Sy_intent, B=4, enc_lengths=n_host, **self._beam_eos())
-                scores, _, beam = self.decoder.search(enc, self.Sy_intent, B=4, want_beam=True, enc_lengths=n_host,
-                                                      **self._beam_eos())
-                return scores, beam
-            cls = self.intent_layers[-2]
-            _, logits, pred, _ = _ops.cls_maxpool_len_fwd(h.contiguous(), cls.weight.detach(), cls.bias.detach(), n_dev,
-                                                          None, tuple(self.values_per_slot))
-            return logits, pred
-        h = self._intent_features_tm(x).contiguous()
-        if self.seq2seq:                                         # beam search, width 4 (models.py:848-851)
-            if beam_search_mode() == "host":
-                return self.decoder.infer(h.transpose(0, 1), self.Sy_intent, B=4, **self._beam_eos())
-            scores, _, beam = self.decoder.search(h.transpose(0, 1), self.Sy_intent, B=4, want_beam=True, **self._beam_eos())
+        h, n_host, n_dev = self._encode(x, lengths)
+        h = h.contiguous()
+        if self.seq2seq:
+            scores, _, beam = self._search(h, n_host, want_beam=True)
             return scores, beam
-        cls = self.intent_layers[-2]
-        _, logits, pred, _, _ = _ops.cls_maxpool_ce_fwd(h.detach(), cls.weight.detach(), cls.bias.detach(), None,
-                                                        tuple(self.values_per_slot), False)
+        cls, slots = self.intent_layers[-2], tuple(self.values_per_slot)
+        if n_dev is None:
+            _, logits, pred, _, _ = _ops.cls_maxpool_ce_fwd(h.detach(), cls.weight.detach(), cls.bias.detach(), None, slots, False)
+        else:
+            _, logits, pred, _ = _ops.cls_maxpool_len_fwd(h, cls.weight.detach(), cls.bias.detach(), n_dev, None, slots)
         return logits, pred
 
     def _beam_eos(self):
         """The search's eos argument under SLU_BEAM_EOS (nothing when the knob is off: the calls are today's)."""
         return {"eos": self.Sy_intent.index("<eos>")} if beam_eos_enabled() else {}
+
+    def _search(self, h, enc_lengths, want_beam):
+        """The width-4 beam search over h (time-major encoder states; enc_lengths: their valid frames, or None) with the
+        books where SLU_BEAM_SEARCH keeps them -> (scores, labels (4, B, U), beam one-hot): "host" (Seq2SeqDecoder.infer)
+        gives no labels, "device" (Seq2SeqDecoder.search) the beam only when want_beam."""
+        mode, enc = beam_search_mode(), h.transpose(0, 1)
+        kw = dict(self._beam_eos(), B=4)                 # the dense calls' arguments are what they always were
+        if enc_lengths is not None:
+            kw["enc_lengths"] = enc_lengths
+        if mode == "host":
+            scores, beam = self.decoder.infer(enc, self.Sy_intent, **kw)
+            return scores, None, beam
+        if want_beam:
+            kw["want_beam"] = True
+        out = self.decoder.search(enc, self.Sy_intent, **kw)
+        return out[0], out[1], out[2] if want_beam else None
 
     def decode_nbest(self, x, n=4, lengths=None):
         """seq2seq: -> list (batch) of lists of (string, score): the n <= 4 best hypotheses of the width-4 device search
@@ -2102,60 +2044,43 @@ class Model(torch.nn.Module):
         if not 1 <= n <= W:
             raise ValueError("decode_nbest: n = %r outside [1, %d]" % (n, W))
         fin = self._beam_eos()
-        if lengths is not None:
-            h, n_host, _ = self._intent_features_tm_len(x, lengths)
-            _DropoutState.current = next_rng_step()
+        h, n_host, _ = self._encode(x, lengths)
+        if n_host is not None:
             fin = dict(fin, enc_lengths=n_host)
-        else:
-            h = self._intent_features_tm(x)
-        h = h.contiguous()
-        out = self.decoder.search(h.transpose(0, 1), self.Sy_intent, B=W, want_lengths="eos" in fin, **fin)
+        out = self.decoder.search(h.contiguous().transpose(0, 1), self.Sy_intent, B=W, want_lengths="eos" in fin, **fin)
         scores, labels = out[0], out[1]
         U = labels.shape[2]
         lengths = out[2] if "eos" in fin else torch.full_like(scores, U, dtype=torch.int32)
         # float64 holds all three exactly
         packed = torch.cat([labels[:n].double(), lengths[:n].double().unsqueeze(2), scores[:n].double().unsqueeze(2)],
                            dim=2).cpu()
-        S = self.Sy_intent
         res = []
         for b in range(packed.shape[1]):
-            rows = []
-            for w in range(n):
-                row = packed[w, b].tolist()
-                text = "".join(S[int(c)] for c in row[:int(row[U])]).lstrip("<sos>").rstrip("<eos>")
-                rows.append((text, row[U + 1]))
-            res.append(rows)
+            rows = [packed[w, b].tolist() for w in range(n)]
+            res.append([(_labels_to_string(row[:int(row[U])], self.Sy_intent), row[U + 1]) for row in rows])
         return res
 
     def decode_intents(self, x, lengths=None):
-        """-> list (batch) of lists (slots) of slot-value strings (reference models.py:853-865).
-        lengths: as predict_intents; a seq2seq model (SLU_MASK_SEQ2SEQ=1) -> list (batch) of the best hypotheses' strings."""
-        if lengths is not None and self.seq2seq:
-            if beam_search_mode() == "device":
-                h, n_host, _ = self._intent_features_tm_len(x, lengths)
-                _DropoutState.current = next_rng_step()
-                _, labels = self.decoder.search(h.contiguous().transpose(0, 1), self.Sy_intent, B=4, enc_lengths=n_host,
-                                                **self._beam_eos())
-                S = self.Sy_intent
-                return ["".join([S[c] for c in row]).lstrip("<sos>").rstrip("<eos>") for row in labels[0].cpu().tolist()]
-            pred = self.predict_intents(x, lengths)[1].cpu()
-            return [self.one_hot_to_string(pred[0, i], self.Sy_intent) for i in range(pred.shape[1])]
-        if lengths is not None:
-            pred = self.predict_intents(x, lengths)[1].cpu()
+        """-> list (batch) of lists (slots) of slot-value strings (reference models.py:853-865).  A seq2seq model: list
+        (batch) of the best hypotheses' strings (models.py:866-874) — under SLU_BEAM_SEARCH=device from their labels
+        (batch, U): the string one_hot_to_string builds, without the one-hot beam crossing to the host.
+        lengths: as predict_intents (a seq2seq model: SLU_MASK_SEQ2SEQ=1)."""
+        if not self.seq2seq:
+            # (the dense call keeps its one-argument form: callers and tests replace predict_intents by a function of x)
+            pred = (self.predict_intents(x) if lengths is None else self.predict_intents(x, lengths))[1].cpu()
             inverse = [{idx: value for value, idx in self.Sy_intent[slot].items()} for slot in self.Sy_intent]
             return [[inverse[s][int(row[s])] for s in range(len(inverse)) if int(row[s]) in inverse[s]]
                     for row in pred]
-        if self.seq2seq and beam_search_mode() == "device":
-            # best hypothesis of every utterance (models.py:866-874) from its labels (batch, U): the string
-            # one_hot_to_string builds, without the one-hot beam crossing to the host
-            h = self._intent_features_tm(x).contiguous()
-            _, labels = self.decoder.search(h.transpose(0, 1), self.Sy_intent, B=4, **self._beam_eos())
-            S = self.Sy_intent
-            return ["".join([S[c] for c in row]).lstrip("<sos>").rstrip("<eos>") for row in labels[0].cpu().tolist()]
-        _, pred = self.predict_intents(x)
-        pred = pred.cpu()
-        if self.seq2seq:                                         # SLU_BEAM_SEARCH=host
-            return [self.one_hot_to_string(pred[0, i], self.Sy_intent) for i in range(pred.shape[1])]
-        inverse = [{idx: value for value, idx in self.Sy_intent[slot].items()} for slot in self.Sy_intent]
-        return [[inverse[s][int(row[s])] for s in range(len(inverse)) if int(row[s]) in inverse[s]]
-                for row in pred]
+        beam_search_mode()               # a bad value of the knob is an error before any launch
+        h, n_host, _ = self._encode(x, lengths)
+        _, labels, beam = self._search(h.contiguous(), n_host, want_beam=False)
+        if labels is not None:
+            return [_labels_to_string(row, self.Sy_intent) for row in labels[0].cpu().tolist()]
+        beam = beam.cpu()
+        return [self.one_hot_to_string(beam[0, i], self.Sy_intent) for i in range(beam.shape[1])]
+
+
+def _labels_to_string(labels, S):
+    """labels (a sequence of indices into S, the list of output labels) -> the string, cleaned as the reference cleans it
+    (models.py:731-737: character-set strips)."""
+    return "".join(S[int(c)] for c in labels).lstrip("<sos>").rstrip("<eos>")

@@ -27,6 +27,7 @@ from data import SLUDataset, ASRDataset, mask_padding_enabled as data_mask_paddi
 from data import mask_asr_enabled
 from models import PretrainedModel, Model, next_rng_step, mask_augment_enabled as models_mask_augment_enabled
 from slu_hip import dp, ops, pipeline
+from slu_hip import knobs as _knobs
 
 
 def models_masks_injected():
@@ -158,12 +159,10 @@ def mask_train_enabled():
     """SLU_MASK_TRAIN: "0" (default) — the training loops drop the lengths (_drop_lengths); "1" — they train on them
     (Model.forward(lengths=...)): every step's loss and gradients are the mean of what its utterances give alone, whatever
     the batch was padded to.  Needs SLU_MASK_PADDING=1 (the collate function supplies the lengths)."""
-    v = os.environ.get("SLU_MASK_TRAIN", "0")
-    if v not in ("0", "1"):
-        raise ValueError("SLU_MASK_TRAIN=%r: expected 0 or 1" % (v,))
-    if v == "1" and not data_mask_padding_enabled():
+    on = _knobs.flag("SLU_MASK_TRAIN")
+    if on and not data_mask_padding_enabled():
         raise ValueError("SLU_MASK_TRAIN=1 needs SLU_MASK_PADDING=1: the lengths come from the collate function")
-    return v == "1"
+    return on
 
 
 def mask_augment_enabled():
