@@ -3,17 +3,18 @@
 // frame equals what the stage computes on the row truncated to n_b — so an utterance's result does not depend on what
 // it was batched with.  The reference has no counterpart (its collate functions pad and pass no lengths, data.py:244).
 //
-// The first group is forward / inference only: no route bytes, no reserve, no dropout.  The second group (masked
-// training) adds Dropout + Downsample with windows clipped to the lengths, forward and backward, and the head's
-// cross-entropy gradient; the reserve and the BPTT are flags of the persistent kernels (slu_gru_seq_fwd_len_rsv,
-// slu_gru_seq_bwd_len).  The third group is the masked pooling / activation pass of a TRAINABLE conv block with its route
-// bytes, and its backward (slu_pool_act_len_fwd_route, slu_pool_act_len_bwd).  The convolution itself and the GRU input projection
-// need no new kernel: on a zero tail the existing slu_wconv_fwd (pool 1, slope 1, no abs) and slu_gemm_f32 compute, at a
-// valid frame, what they compute on the truncated row; the kernels here put the zero tail back behind them.  The
-// length-aware recurrence is a flag of the persistent kernels in slu_gru.hip (slu_gru_seq_fwd_len).
+// One set of stages serves inference and masked training; what training needs on top is an optional output or argument of
+// the same stage: the pool / activation pass writes its route bytes where the caller hands a buffer over
+// (slu_pool_act_len_fwd_route; slu_pool_act_len_bwd differentiates it), Dropout + Downsample is the plain Downsample at
+// p = 0 (slu_seq_pool_len_fwd), the head adds d loss / d logits (slu_cls_maxpool_len_ce_fwd), and the reserve and the BPTT
+// are flags of the persistent kernels in slu_gru.hip (slu_gru_seq_fwd_len / _len_rsv, slu_gru_seq_bwd_len).  Each pair of
+// entry points is two thin wrappers around one static launch function.  The convolution itself and the GRU input
+// projection need no kernel here: on a zero tail the existing slu_wconv_fwd (pool 1, slope 1, no abs) and slu_gemm_f32
+// compute, at a valid frame, what they compute on the truncated row; the kernels here put the zero tail back behind them.
 //
 // All kernels clamp n_b to [1, frames of the buffer]: a bad length cannot index out of bounds (the host rejects it).
-// These are memory-bound passes over activations that are small next to the waveform: one thread per output element.
+// These are memory-bound passes over activations that are small next to the waveform: one thread per output element, or
+// per four channels (float4) where the channel count and the buffers' alignment allow.
 #include "slu_common.h"
 #include "slu_philox.h"
 
@@ -32,62 +33,6 @@ mask_rows_len_kernel(const float* in, float* out, const int* __restrict__ length
   const long long t = e - (long long)b * T;
   const long long n = min(max((long long)lengths[b], 1ll), T);
   out[e] = t < n ? in[e] : 0.0f;
-}
-
-// [abs ->] MaxPool1d(pool, ceil_mode) over the valid frames -> LeakyReLU(slope), zero beyond: pool_act_fwd_kernel
-// (slu_pool.hip) with the window clipped to n_b instead of L.  x channels-last (B, L, C); y as slu_pool_act_fwd.
-__global__ void __launch_bounds__(256)
-pool_act_len_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, const int* __restrict__ lengths, int B, int L,
-                        int C, int L_out, int pool, int do_abs, float slope, long long out_sb, long long out_sl) {
-  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= (long long)B * L_out * C) return;
-  const int c = (int)(e % C);
-  const long long bl = e / C;
-  const int lo = (int)(bl % L_out), b = (int)(bl / L_out);
-  const int n = clamp_len(lengths, b, L);
-  const int l0 = lo * pool, l1 = min(n, l0 + pool);
-  float out = 0.0f;
-  if (l0 < n) {                                 // lo < ceil(n / pool)
-    float best = -INFINITY;
-    for (int l = l0; l < l1; ++l) {
-      const float v = x[((size_t)b * L + l) * C + c];
-      const float u = do_abs ? fabsf(v) : v;
-      if (u > best) best = u;
-    }
-    out = best > 0.0f ? best : best * slope;
-  }
-  y[(size_t)b * out_sb + (size_t)lo * out_sl + c] = out;
-}
-
-// Downsample of a time-major (T, B, C) activation with per-sequence lengths: method 0 x[to * factor], 1 mean, 2 max of
-// the window [to * factor, min(n_b, (to + 1) * factor)); zero for to >= ceil(n_b / factor).  The mean adds the frames in
-// order and divides by their count (avg_pool1d with ceil_mode at the end of a tensor).
-__global__ void __launch_bounds__(256)
-seq_pool_len_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, const int* __restrict__ lengths, int method,
-                        int factor, int T, int B, int C, int T_out) {
-  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= (long long)T_out * B * C) return;
-  const int c = (int)(e % C);
-  const long long tb = e / C;
-  const int b = (int)(tb % B), to = (int)(tb / B);
-  const int n = clamp_len(lengths, b, T);
-  const long long t0 = (long long)to * factor;
-  const int t1 = (int)min((long long)n, t0 + factor);
-  const size_t row = (size_t)B * C, col = (size_t)b * C + c;
-  float out = 0.0f;
-  if (t0 < n) {
-    if (method == 0) {
-      out = x[(size_t)t0 * row + col];
-    } else {
-      float acc = method == 1 ? 0.0f : -INFINITY;
-      for (int t = (int)t0; t < t1; ++t) {
-        const float v = x[(size_t)t * row + col];
-        acc = method == 1 ? __fadd_rn(acc, v) : fmaxf(acc, v);
-      }
-      out = method == 1 ? acc / (float)(t1 - (int)t0) : acc;
-    }
-  }
-  y[e] = out;
 }
 
 // ---- intent head over the valid frames: logits[b][v] = max_{t < n_b} (h[t][b][:] . W[v][:] + bias[v]) ----
@@ -209,13 +154,15 @@ head_len_reduce_kernel(const float* __restrict__ row_stats, float* __restrict__ 
   if (threadIdx.x == 0) { loss_acc[0] = r0[0] / (float)B; loss_acc[1] = r1[0] / (float)B; }
 }
 
-
-// ---- Dropout -> Downsample over the valid frames, forward and backward (masked training) ----------------------------
-// slu_dropout_pool_fwd / _bwd (slu_pool.hip) with every window clipped to t < n_b: y is 0 at to >= ceil(n_b / factor), the
-// mean divides by the number of valid frames of its window, dx is 0 at t >= n_b whatever dy holds beyond the valid outputs
-// (it is not read there).  The dropout stream is the dense batch's: element (t, b, c) takes the keep factor it takes in
-// slu_dropout_pool_fwd — injected mask, or Philox (seed, offset [+ *offset_dev]) at index (t * B + b) * C + c — so a
-// stage keeps its masks when the lengths are switched on.  x and the mask are never read at t >= n_b.
+// ---- [Dropout ->] Downsample of a time-major (T, B, C) activation over the valid frames, forward and backward ---------
+// slu_dropout_pool_fwd / _bwd (slu_pool.hip) with every window clipped to t < n_b: method 0 x[to * factor], 1 mean, 2 max of
+// the window [to * factor, min(n_b, (to + 1) * factor)); y is 0 at to >= ceil(n_b / factor), the mean adds the frames in
+// order and divides by the number of valid frames of its window (avg_pool1d with ceil_mode at the end of a tensor), dx
+// is 0 at t >= n_b whatever dy holds beyond the valid outputs (it is not read there).  The dropout stream is the dense
+// batch's: element (t, b, c) takes the keep factor it takes in slu_dropout_pool_fwd — injected mask, or Philox (seed,
+// offset [+ *offset_dev]) at index (t * B + b) * C + c — so a stage keeps its masks when the lengths are switched on.
+// x and the mask are never read at t >= n_b.  Inference (slu_seq_pool_len_fwd) is p = 0: the keep factor is exactly
+// 1.0f, and __fmul_rn(v, 1.0f) is v, so the plain Downsample needs no kernel of its own.
 struct PoolLenParams {
   const float* mask; long long m_st, m_sb;
   float p, scale;
@@ -390,12 +337,13 @@ dropout_pool_len_bwd4_kernel(const float* __restrict__ dy, const float* __restri
   for (int t = max(t0, t1); t < tend; ++t) *reinterpret_cast<float4*>(dx + (size_t)t * row + col) = zero;
 }
 
-// ---- [abs ->] MaxPool(ceil) over the valid frames -> LeakyReLU with route bytes, and its backward (masked training ----
-// through a trainable CNN block).  The forward is pool_act_len_fwd_kernel that also records, per output, the route byte of
-// pool_act_fwd_kernel (slu_pool.hip): arg-max offset inside the window | negative-before-abs << 7, 0 at a padded output.
-// The backward is pool_act_bwd_kernel with every window clipped to n_b: dx is exactly 0 at l >= n_b (selected, never a
-// product), dy / y are not read at lo >= ceil(n_b / pool), and the activation's derivative is that kernel's
-// (y > 0 ? 1 : slope).  x / dx channels-last (B, L, C); y / dy at b * out_sb + lo * out_sl + c.
+// ---- [abs ->] MaxPool1d(pool, ceil_mode) over the valid frames -> LeakyReLU(slope), zero beyond, and its backward ------
+// The forward is pool_act_fwd_kernel (slu_pool.hip) with the window clipped to n_b instead of L.  With ROUTE (a trainable
+// CNN block under masked training) it also records, per output, that kernel's route byte: arg-max offset inside the
+// window | negative-before-abs << 7, 0 at a padded output; without, it takes no route pointer, keeps no route bookkeeping
+// and stores the same y.  The backward is pool_act_bwd_kernel with every window clipped to n_b: dx is exactly 0 at
+// l >= n_b (selected, never a product), dy / y are not read at lo >= ceil(n_b / pool), and the activation's derivative is
+// that kernel's (y > 0 ? 1 : slope).  x / dx channels-last (B, L, C); y / dy at b * out_sb + lo * out_sl + c.
 struct PoolActLenParams {
   const int* lengths;
   int B, L, C, L_out, pool, do_abs;
@@ -403,14 +351,23 @@ struct PoolActLenParams {
   long long out_sb, out_sl;
 };
 
+// the forward kernels' route argument: a pointer with ROUTE, nothing without
+template <bool ROUTE> struct RouteOut { unsigned char* bytes; };
+template <> struct RouteOut<false> {};
+
+template <bool ROUTE>
 __device__ __forceinline__ void route_take(float v, int do_abs, int off, float& best, unsigned& r) {
   const float u = do_abs ? fabsf(v) : v;
-  if (u > best) { best = u; r = (unsigned)off | ((do_abs && v < 0.0f) ? 0x80u : 0u); }      // first maximum wins
+  if (u > best) {                                                                           // first maximum wins
+    best = u;
+    if constexpr (ROUTE) r = (unsigned)off | ((do_abs && v < 0.0f) ? 0x80u : 0u);
+  }
 }
 
 // scalar path: one thread per output element
+template <bool ROUTE>
 __global__ void __launch_bounds__(256)
-pool_act_len_fwd_route_kernel(const float* __restrict__ x, float* __restrict__ y, unsigned char* __restrict__ route,
+pool_act_len_fwd_route_kernel(const float* __restrict__ x, float* __restrict__ y, const RouteOut<ROUTE> route,
                               const PoolActLenParams q) {
   const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
   if (e >= (long long)q.B * q.L_out * q.C) return;
@@ -423,11 +380,11 @@ pool_act_len_fwd_route_kernel(const float* __restrict__ x, float* __restrict__ y
   unsigned r = 0;
   if (l0 < n) {
     float best = -INFINITY;
-    for (int l = l0; l < l1; ++l) route_take(x[((size_t)b * q.L + l) * q.C + c], q.do_abs, l - l0, best, r);
+    for (int l = l0; l < l1; ++l) route_take<ROUTE>(x[((size_t)b * q.L + l) * q.C + c], q.do_abs, l - l0, best, r);
     out = best > 0.0f ? best : best * q.slope;
   }
   y[(size_t)b * q.out_sb + (size_t)lo * q.out_sl + c] = out;
-  route[e] = (unsigned char)r;
+  if constexpr (ROUTE) route.bytes[e] = (unsigned char)r;
 }
 
 // scalar path: one thread per input element
@@ -456,8 +413,9 @@ pool_act_len_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ 
 // vector path (C % 4 == 0, 16-byte aligned rows): four channels per thread, one thread per OUTPUT frame and quad — a wave
 // reads and writes whole 16-byte pieces of contiguous channel rows; the four route bytes travel as one word.  The
 // backward thread writes dx for every frame of its dense window [lo * pool, min(L, lo * pool + pool)), zeros included.
+template <bool ROUTE>
 __global__ void __launch_bounds__(256)
-pool_act_len_fwd_route4_kernel(const float* __restrict__ x, float* __restrict__ y, unsigned char* __restrict__ route,
+pool_act_len_fwd_route4_kernel(const float* __restrict__ x, float* __restrict__ y, const RouteOut<ROUTE> route,
                                const PoolActLenParams q) {
   const int C4 = q.C >> 2;
   const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -473,16 +431,16 @@ pool_act_len_fwd_route4_kernel(const float* __restrict__ x, float* __restrict__ 
     float4 best = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
     for (int l = l0; l < l1; ++l) {
       const float4 v = *reinterpret_cast<const float4*>(x + ((size_t)b * q.L + l) * q.C + c);
-      route_take(v.x, q.do_abs, l - l0, best.x, rx);
-      route_take(v.y, q.do_abs, l - l0, best.y, ry);
-      route_take(v.z, q.do_abs, l - l0, best.z, rz);
-      route_take(v.w, q.do_abs, l - l0, best.w, rw);
+      route_take<ROUTE>(v.x, q.do_abs, l - l0, best.x, rx);
+      route_take<ROUTE>(v.y, q.do_abs, l - l0, best.y, ry);
+      route_take<ROUTE>(v.z, q.do_abs, l - l0, best.z, rz);
+      route_take<ROUTE>(v.w, q.do_abs, l - l0, best.w, rw);
     }
     out = make_float4(best.x > 0.0f ? best.x : best.x * q.slope, best.y > 0.0f ? best.y : best.y * q.slope,
                       best.z > 0.0f ? best.z : best.z * q.slope, best.w > 0.0f ? best.w : best.w * q.slope);
   }
   *reinterpret_cast<float4*>(y + (size_t)b * q.out_sb + (size_t)lo * q.out_sl + c) = out;
-  *reinterpret_cast<unsigned*>(route + (size_t)bl * q.C + c) = rx | (ry << 8) | (rz << 16) | (rw << 24);
+  if constexpr (ROUTE) *reinterpret_cast<unsigned*>(route.bytes + (size_t)bl * q.C + c) = rx | (ry << 8) | (rz << 16) | (rw << 24);
 }
 
 __device__ __forceinline__ float route_grad(float dy, float y, unsigned r, float slope) {
@@ -573,38 +531,42 @@ extern "C" int slu_mask_rows_len(const float* in, float* out, const int32_t* len
   return SLU_OK;
 }
 
+// float4 kernel where pool_act_len_vec_ok allows, one thread per output element otherwise
+template <bool ROUTE>
+static void pool_act_len_fwd_go(const float* x, float* y, RouteOut<ROUTE> route, const PoolActLenParams& q, bool vec,
+                                hipStream_t st) {
+  const dim3 grid((unsigned)cdiv((int64_t)q.B * q.L_out * (vec ? q.C / 4 : q.C), 256));
+  if (vec) hipLaunchKernelGGL(pool_act_len_fwd_route4_kernel<ROUTE>, grid, dim3(256), 0, st, x, y, route, q);
+  else hipLaunchKernelGGL(pool_act_len_fwd_route_kernel<ROUTE>, grid, dim3(256), 0, st, x, y, route, q);
+}
+
+// route: (B, L_out, C) bytes, or null for y alone
+static int pool_act_len_fwd_launch(const char* who, const float* x, float* y, uint8_t* route, const int32_t* lengths,
+                                   int64_t B, int64_t L, int64_t C, int64_t pool, int do_abs, float slope, int64_t out_sb,
+                                   int64_t out_sl, void* stream) {
+  SLU_REQUIRE(x && y, "%s: null pointer", who);
+  PoolActLenParams q;
+  int rc = pool_act_len_fill(q, who, lengths, B, L, C, pool, do_abs, slope, out_sb, out_sl);
+  if (rc) return rc;
+  const bool vec = pool_act_len_vec_ok(q, x, y, nullptr, route);
+  if (route) pool_act_len_fwd_go<true>(x, y, RouteOut<true>{route}, q, vec, (hipStream_t)stream);
+  else pool_act_len_fwd_go<false>(x, y, RouteOut<false>{}, q, vec, (hipStream_t)stream);
+  SLU_CHECK_LAUNCH(vec ? "pool_act_len_fwd_route4_kernel" : "pool_act_len_fwd_route_kernel");
+  return SLU_OK;
+}
+
 extern "C" int slu_pool_act_len_fwd(const float* x, float* y, const int32_t* lengths, int64_t B, int64_t L, int64_t C,
                                     int64_t pool, int do_abs, float slope, int64_t out_sb, int64_t out_sl, void* stream) {
-  SLU_REQUIRE(x && y, "slu_pool_act_len_fwd: null pointer");
-  SLU_REQUIRE(lengths, "slu_pool_act_len_fwd: null lengths");
-  SLU_REQUIRE(B > 0 && L > 0 && C > 0 && pool >= 1 && pool <= 127, "slu_pool_act_len_fwd: bad size (pool width 1..127)");
-  const int64_t L_out = cdiv(L, pool);
-  SLU_REQUIRE(B < (1ll << 31) && L < (1ll << 31) && C < (1ll << 31) && cdiv(B * L_out * C, 256) < (1ll << 31),
-              "slu_pool_act_len_fwd: tensor too large");
-  hipLaunchKernelGGL(pool_act_len_fwd_kernel, dim3((unsigned)cdiv(B * L_out * C, 256)), dim3(256), 0, (hipStream_t)stream,
-                     x, y, (const int*)lengths, (int)B, (int)L, (int)C, (int)L_out, (int)pool, do_abs, slope,
-                     (long long)out_sb, (long long)out_sl);
-  SLU_CHECK_LAUNCH("pool_act_len_fwd_kernel");
-  return SLU_OK;
+  return pool_act_len_fwd_launch("slu_pool_act_len_fwd", x, y, nullptr, lengths, B, L, C, pool, do_abs, slope, out_sb, out_sl,
+                                 stream);
 }
 
 extern "C" int slu_pool_act_len_fwd_route(const float* x, float* y, uint8_t* route, const int32_t* lengths, int64_t B,
                                           int64_t L, int64_t C, int64_t pool, int do_abs, float slope, int64_t out_sb,
                                           int64_t out_sl, void* stream) {
-  SLU_REQUIRE(x && y && route, "slu_pool_act_len_fwd_route: null pointer");
-  PoolActLenParams q;
-  int rc = pool_act_len_fill(q, "slu_pool_act_len_fwd_route", lengths, B, L, C, pool, do_abs, slope, out_sb, out_sl);
-  if (rc) return rc;
-  if (pool_act_len_vec_ok(q, x, y, nullptr, route)) {
-    hipLaunchKernelGGL(pool_act_len_fwd_route4_kernel, dim3((unsigned)cdiv(B * q.L_out * (C / 4), 256)), dim3(256), 0,
-                       (hipStream_t)stream, x, y, route, q);
-    SLU_CHECK_LAUNCH("pool_act_len_fwd_route4_kernel");
-    return SLU_OK;
-  }
-  hipLaunchKernelGGL(pool_act_len_fwd_route_kernel, dim3((unsigned)cdiv(B * q.L_out * C, 256)), dim3(256), 0,
-                     (hipStream_t)stream, x, y, route, q);
-  SLU_CHECK_LAUNCH("pool_act_len_fwd_route_kernel");
-  return SLU_OK;
+  SLU_REQUIRE(route, "slu_pool_act_len_fwd_route: null pointer");
+  return pool_act_len_fwd_launch("slu_pool_act_len_fwd_route", x, y, route, lengths, B, L, C, pool, do_abs, slope, out_sb,
+                                 out_sl, stream);
 }
 
 extern "C" int slu_pool_act_len_bwd(const float* dy, const float* y, const uint8_t* route, const int32_t* lengths, float* dx,
@@ -626,19 +588,30 @@ extern "C" int slu_pool_act_len_bwd(const float* dy, const float* y, const uint8
   return SLU_OK;
 }
 
+// [Dropout ->] Downsample forward: float4 kernel where pool_len_vec_ok allows, one thread per output element otherwise
+static int pool_len_fwd_launch(const char* who, const float* x, float* y, const int32_t* lengths, const float* mask,
+                               int64_t m_st, int64_t m_sb, float p, uint64_t seed, uint64_t offset, const uint64_t* offset_dev,
+                               int method, int64_t factor, int64_t T, int64_t B, int64_t C, void* stream) {
+  SLU_REQUIRE(x && y, "%s: null pointer", who);
+  PoolLenParams q;
+  int rc = pool_len_fill(q, who, mask, m_st, m_sb, p, seed, offset, offset_dev, lengths, method, factor, T, B, C);
+  if (rc) return rc;
+  if (pool_len_vec_ok(q, x, y, nullptr)) {
+    hipLaunchKernelGGL(dropout_pool_len_fwd4_kernel, dim3((unsigned)cdiv(B * (C / 4), 256), (unsigned)q.T_out), dim3(256), 0,
+                       (hipStream_t)stream, x, y, q);
+    SLU_CHECK_LAUNCH("dropout_pool_len_fwd4_kernel");
+    return SLU_OK;
+  }
+  hipLaunchKernelGGL(dropout_pool_len_fwd_kernel, dim3((unsigned)cdiv((int64_t)q.T_out * B * C, 256)), dim3(256), 0,
+                     (hipStream_t)stream, x, y, q);
+  SLU_CHECK_LAUNCH("dropout_pool_len_fwd_kernel");
+  return SLU_OK;
+}
+
 extern "C" int slu_seq_pool_len_fwd(const float* x, float* y, const int32_t* lengths, int method, int64_t factor, int64_t T,
                                     int64_t B, int64_t C, void* stream) {
-  SLU_REQUIRE(x && y, "slu_seq_pool_len_fwd: null pointer");
-  SLU_REQUIRE(lengths, "slu_seq_pool_len_fwd: null lengths");
-  SLU_REQUIRE(T > 0 && B > 0 && C > 0 && factor > 0, "slu_seq_pool_len_fwd: non-positive size");
-  SLU_REQUIRE(method >= 0 && method <= 2, "slu_seq_pool_len_fwd: downsampling method must be 0 (none), 1 (avg) or 2 (max)");
-  const int64_t T_out = cdiv(T, factor);
-  SLU_REQUIRE(T < (1ll << 31) && B < (1ll << 31) && C < (1ll << 31) && factor < (1ll << 31) &&
-              cdiv(T_out * B * C, 256) < (1ll << 31), "slu_seq_pool_len_fwd: tensor too large");
-  hipLaunchKernelGGL(seq_pool_len_fwd_kernel, dim3((unsigned)cdiv(T_out * B * C, 256)), dim3(256), 0, (hipStream_t)stream,
-                     x, y, (const int*)lengths, method, (int)factor, (int)T, (int)B, (int)C, (int)T_out);
-  SLU_CHECK_LAUNCH("seq_pool_len_fwd_kernel");
-  return SLU_OK;
+  return pool_len_fwd_launch("slu_seq_pool_len_fwd", x, y, lengths, nullptr, 0, 0, 0.0f, 0, 0, nullptr, method, factor, T, B, C,
+                             stream);
 }
 
 static int head_len_launch(const char* who, const float* h, const float* weight, const float* bias, const int32_t* lengths,
@@ -695,21 +668,8 @@ extern "C" int slu_cls_maxpool_len_ce_fwd(const float* h, const float* weight, c
 extern "C" int slu_dropout_pool_len_fwd(const float* x, const int32_t* lengths, const float* mask, int64_t m_st, int64_t m_sb,
                                         float p, uint64_t seed, uint64_t offset, const uint64_t* offset_dev, int method,
                                         int64_t factor, float* y, int64_t T, int64_t B, int64_t C, void* stream) {
-  SLU_REQUIRE(x && y, "slu_dropout_pool_len_fwd: null pointer");
-  PoolLenParams q;
-  int rc = pool_len_fill(q, "slu_dropout_pool_len_fwd", mask, m_st, m_sb, p, seed, offset, offset_dev, lengths, method, factor,
-                         T, B, C);
-  if (rc) return rc;
-  if (pool_len_vec_ok(q, x, y, nullptr)) {
-    hipLaunchKernelGGL(dropout_pool_len_fwd4_kernel, dim3((unsigned)cdiv(B * (C / 4), 256), (unsigned)q.T_out), dim3(256), 0,
-                       (hipStream_t)stream, x, y, q);
-    SLU_CHECK_LAUNCH("dropout_pool_len_fwd4_kernel");
-    return SLU_OK;
-  }
-  hipLaunchKernelGGL(dropout_pool_len_fwd_kernel, dim3((unsigned)cdiv((int64_t)q.T_out * B * C, 256)), dim3(256), 0,
-                     (hipStream_t)stream, x, y, q);
-  SLU_CHECK_LAUNCH("dropout_pool_len_fwd_kernel");
-  return SLU_OK;
+  return pool_len_fwd_launch("slu_dropout_pool_len_fwd", x, y, lengths, mask, m_st, m_sb, p, seed, offset, offset_dev, method,
+                             factor, T, B, C, stream);
 }
 
 extern "C" int slu_dropout_pool_len_bwd(const float* dy, const float* x, const int32_t* lengths, const float* mask,

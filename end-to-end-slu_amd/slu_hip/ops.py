@@ -8,6 +8,7 @@ torch is plumbing here: it owns the device buffers, the stream and the autograd 
 arithmetic of the hot path happens in libslu_hip.so; there is no fallback path.
 """
 import contextlib
+import ctypes
 import math
 import os
 import struct
@@ -274,7 +275,6 @@ def gemm_small_batched(problems):
     """problems: [(A (M, K), B, bias or None, C (M, N), mode, accumulate)] — mode 0: B is (N, K) (C = A B^T + bias), mode 1:
     B is (K, N) (C = A B + bias); row-strided fp32 views with unit column stride.  Up to four problems per launch of
     slu_gemm_small_batched (latency-bound small-M products); shapes the kernel does not take go through gemm()."""
-    import ctypes
     L = _lib.load()
     batch = []
 
@@ -309,7 +309,6 @@ def gemm_small_batched(problems):
 def stage_inputs(pairs, set_tensor=None, set_value=0):
     """One launch refreshing static input buffers: pairs = [(dst contiguous, src)] with src contiguous or strided
     along dim 0 only; optionally set_tensor[0] = set_value (int64).  Returns the pairs it could not take."""
-    import ctypes
     L = _lib.load()
     segs, rest = [], []
     for dst, src in pairs:
@@ -334,7 +333,6 @@ def stage_inputs(pairs, set_tensor=None, set_value=0):
 
 def copy_multi(pairs):
     """[(dst, src)] contiguous same-sized tensors (whole 4-byte words): all copies in ceil(n / 32) launches."""
-    import ctypes
     L = _lib.load()
     step = L.slu_multi_max()
     for i in range(0, len(pairs), step):
@@ -350,7 +348,6 @@ def copy_multi(pairs):
 
 def scale_multi(tensors, scale_dev):
     """x *= scale_dev[0] for every contiguous fp32 tensor of the list (one launch per 32 tensors)."""
-    import ctypes
     if not tensors:
         return
     L = _lib.load()
@@ -531,7 +528,6 @@ def pcm16_to_f32(x):
 
 def store_u64(dst, values):
     """dst (int64 device tensor)[:len(values)] = values, in one launch with the values in the kernel arguments."""
-    import ctypes
     L = _lib.load()
     n = len(values)
     assert 1 <= n <= 64 and dst.dtype == torch.int64 and dst.numel() >= n and dst.is_contiguous()
@@ -942,7 +938,6 @@ def gru_layer_frozen(x, w_ih, b_ih, packed_ih, w_hh_f, b_hh_f, w_hh_r, b_hh_r, p
 def absmax_into(t, word_ptr):
     """atomicMax of the IEEE bit pattern of max |t| into the uint32 device word at `word_ptr` (the f16x2 range guard's
     words, slu_hip/guard.py): one small launch on the current stream."""
-    import ctypes
     t = t.detach()
     if not t.is_contiguous():
         t = t.contiguous()
@@ -1004,7 +999,6 @@ TN_SMALL_ROWS = 4096      # weight gradients of a GRU layer with T*B up to this 
 def _tn_args(problems, rowsum):
     """The checks and ctypes arguments the two batched TN launches share: the nine per-problem host arrays (A, lda, B, ldb,
     C, ldc, M, N, K), the count and the row-sum job (src, rows, cols, dst)."""
-    import ctypes
     for A, B, C in problems:
         assert A.stride(1) == 1 and B.stride(1) == 1 and C.stride(1) == 1 and A.shape[0] == B.shape[0]
         assert C.shape == (A.shape[1], B.shape[1])
@@ -1285,7 +1279,6 @@ def cls_maxpool_ce_fwd(h, weight, bias, y, values_per_slot, want_grad, epoch_sum
     epoch_sums: optional float64 (2) device tensor; B * (loss, acc) is added to it by the same launch.
     drop: None, or (p, seed, offset, offset_dev) — the Dropout in front of the classifier fused into this launch (h is
     then the raw GRU output; the dropped activations are returned as a sixth value)."""
-    import ctypes
     L = _lib.load()
     T, B, C = h.shape
     S = len(values_per_slot)
@@ -1318,17 +1311,35 @@ def cls_maxpool_ce_fwd(h, weight, bias, y, values_per_slot, want_grad, epoch_sum
 LEN_HIDDEN_SIZES = (16, 32, 64, 128)       # hidden sizes slu_gru_seq_fwd_len takes (the persistent recurrence kernels)
 
 
-def _len_check(lengths, B, *tensors):
-    """The length-aware calls are forward evaluations outside autograd: a tensor that requires a gradient is refused
-    instead of being silently detached.  lengths: int32 CUDA tensor of B entries (values are the caller's to validate —
+def _len_ok(lengths, B):
+    if not torch.is_tensor(lengths) or lengths.dtype != torch.int32 or not lengths.is_cuda:
+        raise TypeError("lengths must be an int32 CUDA tensor")
+    if lengths.dim() != 1 or lengths.numel() != B or not lengths.is_contiguous():
+        raise ValueError("lengths: expected %d contiguous entries, got shape %s" % (B, tuple(lengths.shape)))
+    return lengths
+
+
+def _len_check(lengths, B, *tensors, grad_ok=False):
+    """The calls without a backward pass are forward evaluations outside autograd: a tensor that requires a gradient is
+    refused instead of being silently detached (grad_ok: the masked-training form of the call, which an autograd Function
+    differentiates — _len_ok alone).  lengths: int32 CUDA tensor of B entries (values are the caller's to validate —
     models._host_lengths does, on the host; the kernels clamp)."""
     for t in tensors:
-        if t is not None and t.requires_grad:
+        if not grad_ok and t is not None and t.requires_grad:
             raise RuntimeError("the length-aware kernels are inference only (no backward): call them under torch.no_grad() "
                                "with detached tensors")
     _len_ok(lengths, B)
 
 
+def _len_hidden_ok(H):
+    if H not in LEN_HIDDEN_SIZES:
+        raise ValueError("lengths: hidden size %d has no length-aware recurrence kernel (supported: %s)"
+                         % (H, ", ".join(map(str, LEN_HIDDEN_SIZES))))
+
+
+# A stage with two public callers is one private body: the inference form refuses tensors that require a gradient and has
+# no optional output; the masked-training form adds the output its backward pass needs (route bytes, reserve, d_logits).
+# Each form launches its own library entry point (include/slu_hip.h), so a step's launch names tell the two apart.
 def mask_rows_len(x, lengths):
     """x (B, T) fp32 waveforms -> a copy with x[b, lengths[b]:] = 0."""
     L = _lib.load()
@@ -1340,11 +1351,9 @@ def mask_rows_len(x, lengths):
     return out
 
 
-def pool_act_len_fwd(x, lengths, pool, do_abs, slope, time_major):
-    """x channels-last (B, L, C), lengths = valid frames of x -> [abs ->] max-pool(pool, ceil) over the valid frames ->
-    LeakyReLU(slope), zero beyond ceil(n / pool): (B, L_out, C), or time-major (L_out, B, C)."""
+def _pool_act_len(x, lengths, pool, do_abs, slope, time_major, want_route):
     L = _lib.load()
-    _len_check(lengths, x.shape[0], x)
+    _len_check(lengths, x.shape[0], x, grad_ok=want_route)
     x = _f32c(x, "x")
     B, Lin, C = x.shape
     l_out = -(-Lin // pool)
@@ -1354,29 +1363,25 @@ def pool_act_len_fwd(x, lengths, pool, do_abs, slope, time_major):
     else:
         y = torch.empty(B, l_out, C, dtype=torch.float32, device=x.device)
         sb, sl = l_out * C, C
-    _lib.check(L.slu_pool_act_len_fwd(x.data_ptr(), y.data_ptr(), lengths.data_ptr(), B, Lin, C, pool, int(do_abs),
-                                      float(slope), sb, sl, _stream()), "slu_pool_act_len_fwd")
-    return y
+    args = (lengths.data_ptr(), B, Lin, C, pool, int(do_abs), float(slope), sb, sl, _stream())
+    if not want_route:
+        _lib.check(L.slu_pool_act_len_fwd(x.data_ptr(), y.data_ptr(), *args), "slu_pool_act_len_fwd")
+        return y, None
+    route = torch.empty(B, l_out, C, dtype=torch.uint8, device=x.device)
+    _lib.check(L.slu_pool_act_len_fwd_route(x.data_ptr(), y.data_ptr(), route.data_ptr(), *args), "slu_pool_act_len_fwd_route")
+    return y, route
+
+
+def pool_act_len_fwd(x, lengths, pool, do_abs, slope, time_major):
+    """x channels-last (B, L, C), lengths = valid frames of x -> [abs ->] max-pool(pool, ceil) over the valid frames ->
+    LeakyReLU(slope), zero beyond ceil(n / pool): (B, L_out, C), or time-major (L_out, B, C)."""
+    return _pool_act_len(x, lengths, pool, do_abs, slope, time_major, False)[0]
 
 
 def pool_act_len_fwd_route(x, lengths, pool, do_abs, slope, time_major):
     """pool_act_len_fwd (the same y, bit for bit) -> (y, route (B, L_out, C) uint8: PoolActFn's route bytes, 0 at padded
     outputs) — the forward of a conv block that pool_act_len_bwd differentiates."""
-    L = _lib.load()
-    x = _f32c(x, "x")
-    B, Lin, C = x.shape
-    _len_ok(lengths, B)
-    l_out = -(-Lin // pool)
-    if time_major:
-        y = torch.empty(l_out, B, C, dtype=torch.float32, device=x.device)
-        sb, sl = C, B * C
-    else:
-        y = torch.empty(B, l_out, C, dtype=torch.float32, device=x.device)
-        sb, sl = l_out * C, C
-    route = torch.empty(B, l_out, C, dtype=torch.uint8, device=x.device)
-    _lib.check(L.slu_pool_act_len_fwd_route(x.data_ptr(), y.data_ptr(), route.data_ptr(), lengths.data_ptr(), B, Lin, C, pool,
-                                            int(do_abs), float(slope), sb, sl, _stream()), "slu_pool_act_len_fwd_route")
-    return y, route
+    return _pool_act_len(x, lengths, pool, do_abs, slope, time_major, True)
 
 
 def pool_act_len_bwd(dy, y, route, lengths, Lin, pool, slope, time_major):
@@ -1407,17 +1412,27 @@ def mask_frames_len_(x, lengths_flat):
     return x
 
 
+def _gru_seq_fwd_len(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lengths, T, B, H, D, rsv, want_reserve=False):
+    """rsv: the masked-training form (slu_gru_seq_fwd_len_rsv, with or without a reserve)."""
+    L = _lib.load()
+    _len_check(lengths, B, gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, grad_ok=rsv)
+    _len_hidden_ok(H)
+    out = torch.empty(T, B, D * H, dtype=torch.float32, device=gx.device)
+    io = (gx.data_ptr(), w_hh_f.data_ptr(), _ptr(w_hh_r), b_hh_f.data_ptr(), _ptr(b_hh_r), out.data_ptr())
+    sizes = (lengths.data_ptr(), T, B, H, D, _stream())
+    if not rsv:
+        _lib.check(L.slu_gru_seq_fwd_len(*io, *sizes), "slu_gru_seq_fwd_len")
+        return out, None
+    reserve = None
+    if want_reserve:
+        reserve = torch.empty(L.slu_gru_reserve_bytes(T, B, H, D) // 4, dtype=torch.float32, device=gx.device)
+    _lib.check(L.slu_gru_seq_fwd_len_rsv(*io, _ptr(reserve), *sizes), "slu_gru_seq_fwd_len_rsv")
+    return out, reserve
+
+
 def gru_seq_fwd_len(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lengths, T, B, H, D):
     """gru_seq_fwd (no reserve) with per-sequence lengths -> out (T, B, D*H), zero at t >= lengths[b]."""
-    L = _lib.load()
-    _len_check(lengths, B, gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r)
-    if H not in LEN_HIDDEN_SIZES:
-        raise ValueError("lengths: hidden size %d has no length-aware recurrence kernel (supported: %s)"
-                         % (H, ", ".join(map(str, LEN_HIDDEN_SIZES))))
-    out = torch.empty(T, B, D * H, dtype=torch.float32, device=gx.device)
-    _lib.check(L.slu_gru_seq_fwd_len(gx.data_ptr(), w_hh_f.data_ptr(), _ptr(w_hh_r), b_hh_f.data_ptr(), _ptr(b_hh_r),
-                                     out.data_ptr(), lengths.data_ptr(), T, B, H, D, _stream()), "slu_gru_seq_fwd_len")
-    return out
+    return _gru_seq_fwd_len(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lengths, T, B, H, D, False)[0]
 
 
 LEN_BF16_HIDDEN_SIZES = (64, 128)          # hidden sizes slu_gru_seq_fwd_len_bf16 takes (the split-precision recurrence)
@@ -1439,24 +1454,34 @@ def gru_seq_fwd_len_bf16(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lengths, T, B, H, D
     return out
 
 
-def seq_pool_len_fwd(x, lengths, method, factor):
-    """Downsample(method, factor) of a time-major (T, B, C) activation with per-sequence lengths."""
+def _seq_pool_len(x, lengths, method, factor, drop=None):
+    """drop: None (slu_seq_pool_len_fwd), or (mask, p, seed, offset, offset_dev) of the masked-training form."""
     L = _lib.load()
-    _len_check(lengths, x.shape[1], x)
+    _len_check(lengths, x.shape[1], x, grad_ok=drop is not None)
     x = _f32c(x, "x")
     T, B, C = x.shape
     y = torch.empty(-(-T // factor), B, C, dtype=torch.float32, device=x.device)
-    _lib.check(L.slu_seq_pool_len_fwd(x.data_ptr(), y.data_ptr(), lengths.data_ptr(), METHODS[method], factor, T, B, C,
-                                      _stream()), "slu_seq_pool_len_fwd")
+    if drop is None:
+        _lib.check(L.slu_seq_pool_len_fwd(x.data_ptr(), y.data_ptr(), lengths.data_ptr(), METHODS[method], factor, T, B, C,
+                                          _stream()), "slu_seq_pool_len_fwd")
+        return y
+    mask, p, seed, offset, offset_dev = drop
+    mp, mst, msb = _mask_args(mask, T, B, C)
+    _lib.check(L.slu_dropout_pool_len_fwd(x.data_ptr(), lengths.data_ptr(), mp, mst, msb, float(p), int(seed), int(offset),
+                                          _ptr(offset_dev), METHODS[method], factor, y.data_ptr(), T, B, C, _stream()),
+               "slu_dropout_pool_len_fwd")
     return y
 
 
-def cls_maxpool_len_fwd(h, weight, bias, lengths, y, values_per_slot):
-    """-> (loss_acc (2) or None, logits (B, V), pred (B, S), argmax_t (B, V) int32): cls_maxpool_ce_fwd with the max over
-    time taken over t < lengths[b]."""
-    import ctypes
+def seq_pool_len_fwd(x, lengths, method, factor):
+    """Downsample(method, factor) of a time-major (T, B, C) activation with per-sequence lengths."""
+    return _seq_pool_len(x, lengths, method, factor)
+
+
+def _cls_maxpool_len(h, weight, bias, lengths, y, values_per_slot, want_grad):
+    """want_grad: the masked-training form (slu_cls_maxpool_len_ce_fwd: labels required, d_logits written)."""
     L = _lib.load()
-    _len_check(lengths, h.shape[1], h, weight, bias)
+    _len_check(lengths, h.shape[1], h, weight, bias, grad_ok=want_grad)
     h, weight, bias = _f32c(h, "h"), _f32c(weight, "weight"), _f32c(bias, "bias")
     T, B, C = h.shape
     S = len(values_per_slot)
@@ -1465,44 +1490,31 @@ def cls_maxpool_len_fwd(h, weight, bias, lengths, y, values_per_slot):
     logits = torch.empty(B, V, dtype=torch.float32, device=dev)
     argmax_t = torch.empty(B, V, dtype=torch.int32, device=dev)
     pred = torch.empty(B, S, dtype=torch.int64, device=dev)
+    d_logits = torch.empty(B, V, dtype=torch.float32, device=dev) if want_grad else None
     row_stats = torch.empty(B, 2, dtype=torch.float32, device=dev) if y is not None else None
     loss_acc = torch.empty(2, dtype=torch.float32, device=dev) if y is not None else None
     vps = (ctypes.c_int64 * S)(*[int(v) for v in values_per_slot])
-    _lib.check(L.slu_cls_maxpool_len_fwd(h.data_ptr(), weight.data_ptr(), bias.data_ptr(), lengths.data_ptr(), _ptr(y), vps,
-                                         S, logits.data_ptr(), argmax_t.data_ptr(), pred.data_ptr(), _ptr(row_stats),
-                                         _ptr(loss_acc), T, B, C, _stream()), "slu_cls_maxpool_len_fwd")
-    return loss_acc, logits, pred, argmax_t
+    head = (h.data_ptr(), weight.data_ptr(), bias.data_ptr(), lengths.data_ptr(), _ptr(y), vps, S, logits.data_ptr(),
+            argmax_t.data_ptr(), pred.data_ptr())
+    tail = (_ptr(row_stats), _ptr(loss_acc), T, B, C, _stream())
+    if want_grad:
+        _lib.check(L.slu_cls_maxpool_len_ce_fwd(*head, d_logits.data_ptr(), *tail), "slu_cls_maxpool_len_ce_fwd")
+    else:
+        _lib.check(L.slu_cls_maxpool_len_fwd(*head, *tail), "slu_cls_maxpool_len_fwd")
+    return loss_acc, logits, pred, argmax_t, d_logits
 
 
-# ---- masked training (include/slu_hip.h "masked training"): the same stages with a reserve, a BPTT and dropout ----------
-def _len_ok(lengths, B):
-    if not torch.is_tensor(lengths) or lengths.dtype != torch.int32 or not lengths.is_cuda:
-        raise TypeError("lengths must be an int32 CUDA tensor")
-    if lengths.dim() != 1 or lengths.numel() != B or not lengths.is_contiguous():
-        raise ValueError("lengths: expected %d contiguous entries, got shape %s" % (B, tuple(lengths.shape)))
-    return lengths
+def cls_maxpool_len_fwd(h, weight, bias, lengths, y, values_per_slot):
+    """-> (loss_acc (2) or None, logits (B, V), pred (B, S), argmax_t (B, V) int32): cls_maxpool_ce_fwd with the max over
+    time taken over t < lengths[b]."""
+    return _cls_maxpool_len(h, weight, bias, lengths, y, values_per_slot, False)[:4]
 
 
-def _len_hidden_ok(H):
-    if H not in LEN_HIDDEN_SIZES:
-        raise ValueError("lengths: hidden size %d has no length-aware recurrence kernel (supported: %s)"
-                         % (H, ", ".join(map(str, LEN_HIDDEN_SIZES))))
-
-
+# ---- masked training (include/slu_hip.h "masked training"): the training forms of the bodies above, and the backward passes
 def gru_seq_fwd_len_rsv(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lengths, T, B, H, D, want_reserve):
     """gru_seq_fwd with per-sequence lengths -> (out (T, B, D*H), zero at t >= lengths[b]; reserve or None).  The reserve
     has gru_seq_fwd's layout; at t >= lengths[b] its contents are unspecified (gru_seq_bwd_len does not use them)."""
-    L = _lib.load()
-    _len_ok(lengths, B)
-    _len_hidden_ok(H)
-    out = torch.empty(T, B, D * H, dtype=torch.float32, device=gx.device)
-    reserve = None
-    if want_reserve:
-        reserve = torch.empty(L.slu_gru_reserve_bytes(T, B, H, D) // 4, dtype=torch.float32, device=gx.device)
-    _lib.check(L.slu_gru_seq_fwd_len_rsv(gx.data_ptr(), w_hh_f.data_ptr(), _ptr(w_hh_r), b_hh_f.data_ptr(), _ptr(b_hh_r),
-                                         out.data_ptr(), _ptr(reserve), lengths.data_ptr(), T, B, H, D, _stream()),
-               "slu_gru_seq_fwd_len_rsv")
-    return out, reserve
+    return _gru_seq_fwd_len(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lengths, T, B, H, D, True, want_reserve)
 
 
 def gru_seq_bwd_len(d_out, reserve, w_hh_f, w_hh_r, lengths, T, B, H, D):
@@ -1526,16 +1538,7 @@ def gru_seq_bwd_len(d_out, reserve, w_hh_f, w_hh_r, lengths, T, B, H, D):
 def dropout_pool_len_fwd(x, lengths, mask, p, seed, offset, method, factor, offset_dev=None):
     """dropout_pool_fwd with windows clipped to t < lengths[b]: zero at to >= ceil(lengths[b] / factor).  The keep factor of
     element (t, b, c) is dropout_pool_fwd's (the dense batch's stream)."""
-    L = _lib.load()
-    x = _f32c(x, "x")
-    T, B, C = x.shape
-    _len_ok(lengths, B)
-    y = torch.empty(-(-T // factor), B, C, dtype=torch.float32, device=x.device)
-    mp, mst, msb = _mask_args(mask, T, B, C)
-    _lib.check(L.slu_dropout_pool_len_fwd(x.data_ptr(), lengths.data_ptr(), mp, mst, msb, float(p), int(seed), int(offset),
-                                          _ptr(offset_dev), METHODS[method], factor, y.data_ptr(), T, B, C, _stream()),
-               "slu_dropout_pool_len_fwd")
-    return y
+    return _seq_pool_len(x, lengths, method, factor, (mask, p, seed, offset, offset_dev))
 
 
 def dropout_pool_len_bwd(dy, x, lengths, mask, p, seed, offset, method, factor, offset_dev=None):
@@ -1554,26 +1557,7 @@ def dropout_pool_len_bwd(dy, x, lengths, mask, p, seed, offset, method, factor, 
 
 def cls_maxpool_len_ce_fwd(h, weight, bias, lengths, y, values_per_slot):
     """cls_maxpool_len_fwd with labels -> (loss_acc (2), logits (B, V), pred (B, S), argmax_t (B, V) int32, d_logits (B, V))"""
-    import ctypes
-    L = _lib.load()
-    h, weight, bias = _f32c(h, "h"), _f32c(weight, "weight"), _f32c(bias, "bias")
-    T, B, C = h.shape
-    _len_ok(lengths, B)
-    S = len(values_per_slot)
-    V = int(sum(values_per_slot))
-    dev = h.device
-    logits = torch.empty(B, V, dtype=torch.float32, device=dev)
-    argmax_t = torch.empty(B, V, dtype=torch.int32, device=dev)
-    pred = torch.empty(B, S, dtype=torch.int64, device=dev)
-    d_logits = torch.empty(B, V, dtype=torch.float32, device=dev)
-    row_stats = torch.empty(B, 2, dtype=torch.float32, device=dev)
-    loss_acc = torch.empty(2, dtype=torch.float32, device=dev)
-    vps = (ctypes.c_int64 * S)(*[int(v) for v in values_per_slot])
-    _lib.check(L.slu_cls_maxpool_len_ce_fwd(h.data_ptr(), weight.data_ptr(), bias.data_ptr(), lengths.data_ptr(),
-                                            y.data_ptr(), vps, S, logits.data_ptr(), argmax_t.data_ptr(), pred.data_ptr(),
-                                            d_logits.data_ptr(), row_stats.data_ptr(), loss_acc.data_ptr(), T, B, C,
-                                            _stream()), "slu_cls_maxpool_len_ce_fwd")
-    return loss_acc, logits, pred, argmax_t, d_logits
+    return _cls_maxpool_len(h, weight, bias, lengths, y, values_per_slot, True)
 
 
 def head_dropout_fusable(weight, p, mask, method, factor, h=None):
@@ -1593,6 +1577,24 @@ def head_dropout_fusable(weight, p, mask, method, factor, h=None):
 # ------------------------------------------------------------------------------------------------
 # autograd Functions (one per fused stage of the encoder)
 # ------------------------------------------------------------------------------------------------
+def _intent_head_bwd(saved, d_loss, need_h, need_w, drop=None):
+    """The backward pass of both intent heads (slu_cls_maxpool_ce_bwd): saved = (h, weight, argmax_t, d_logits) of the
+    forward pass, drop = IntentHeadFn's (p, seed, offset, offset_dev) or None -> (dh, dW, db), None where not needed."""
+    L = _lib.load()
+    h, weight, argmax_t, d_logits = saved
+    p, seed, offset, offset_dev = drop if drop else (0.0, 0, 0, None)
+    T, B, C = h.shape
+    V = weight.shape[0]
+    g = d_loss.contiguous().float()
+    dh = torch.empty_like(h) if need_h else None
+    dW = torch.empty_like(weight) if need_w else None
+    db = torch.empty(V, dtype=torch.float32, device=h.device) if need_w else None
+    _lib.check(L.slu_cls_maxpool_ce_bwd(d_logits.data_ptr(), argmax_t.data_ptr(), h.data_ptr(), weight.data_ptr(),
+                                        g.data_ptr(), _ptr(dh), _ptr(dW), _ptr(db), float(p), int(seed), int(offset),
+                                        _ptr(offset_dev), T, B, C, V, _stream()), "slu_cls_maxpool_ce_bwd")
+    return dh, dW, db
+
+
 class IntentHeadFn(torch.autograd.Function):
     """final_classifier Linear -> FinalPool (max over time) -> per-slot cross-entropy / accuracy
     (reference models.py:709, :112-123, :811-821).  h time-major (T,B,C), y (B,S) int64.
@@ -1624,22 +1626,10 @@ class IntentHeadFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_loss, _d_acc, _d_logits, _d_pred):
-        L = _lib.load()
         if d_loss is None:
             return None, None, None, None, None, None
-        h, weight, argmax_t, d_logits = ctx.saved_tensors
-        p, seed, offset, offset_dev = ctx.drop if ctx.drop else (0.0, 0, 0, None)
-        T, B, C = h.shape
-        V = weight.shape[0]
-        g = d_loss.contiguous().float()
-        dh = torch.empty_like(h) if ctx.needs_input_grad[0] else None
-        need_w = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        dW = torch.empty_like(weight) if need_w else None
-        db = torch.empty(V, dtype=torch.float32, device=h.device) if need_w else None
-        _lib.check(L.slu_cls_maxpool_ce_bwd(d_logits.data_ptr(), argmax_t.data_ptr(), h.data_ptr(),
-                                            weight.data_ptr(), g.data_ptr(), _ptr(dh), _ptr(dW), _ptr(db),
-                                            float(p), int(seed), int(offset), _ptr(offset_dev),
-                                            T, B, C, V, _stream()), "slu_cls_maxpool_ce_bwd")
+        need = ctx.needs_input_grad
+        dh, dW, db = _intent_head_bwd(ctx.saved_tensors, d_loss, need[0], need[1] or need[2], ctx.drop)
         return dh, dW, db, None, None, None
 
 
@@ -1664,21 +1654,37 @@ class IntentHeadLenFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_loss, _d_acc, _d_logits, _d_pred):
-        L = _lib.load()
         if d_loss is None:
             return None, None, None, None, None, None
-        h, weight, argmax_t, d_logits = ctx.saved_tensors
-        T, B, C = h.shape
-        V = weight.shape[0]
-        g = d_loss.contiguous().float()
-        dh = torch.empty_like(h) if ctx.needs_input_grad[0] else None
-        need_w = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
-        dW = torch.empty_like(weight) if need_w else None
-        db = torch.empty(V, dtype=torch.float32, device=h.device) if need_w else None
-        _lib.check(L.slu_cls_maxpool_ce_bwd(d_logits.data_ptr(), argmax_t.data_ptr(), h.data_ptr(), weight.data_ptr(),
-                                            g.data_ptr(), _ptr(dh), _ptr(dW), _ptr(db), 0.0, 0, 0, 0, T, B, C, V, _stream()),
-                   "slu_cls_maxpool_ce_bwd")
+        need = ctx.needs_input_grad
+        dh, dW, db = _intent_head_bwd(ctx.saved_tensors, d_loss, need[0], need[2] or need[3])
         return dh, None, dW, db, None, None
+
+
+def _frame_head_fwd(rows, weight, bias, y_rows, need):
+    """rows (N, C), y_rows (N) int64 labels (-1: ignored) -> (logits (N, V), overwritten with d loss / d logits where
+    `need`; out3 = [loss, acc, ...]): the Linear and the cross-entropy of both frame heads."""
+    L = _lib.load()
+    N, V = rows.shape[0], weight.shape[0]
+    logits = gemm_nt(rows, weight, bias, bf16_ok=False)        # train_nsplit arithmetic (fp32 in bf16 mode)
+    row_stats = torch.empty(2 * N, dtype=torch.float32, device=rows.device)
+    out3 = torch.empty(3, dtype=torch.float32, device=rows.device)
+    _lib.check(L.slu_frame_ce_fwd(logits.data_ptr(), y_rows.data_ptr(), N, V, -1, int(need), row_stats.data_ptr(),
+                                  out3.data_ptr(), _stream()), "slu_frame_ce_fwd")
+    return logits, out3
+
+
+def _frame_head_bwd(rows, weight, d_logits, d_loss, need_rows, need_w, need_b):
+    """-> (d rows (N, C), dW, db), None where not needed: the backward GEMMs of both frame heads."""
+    d_rows = dW = db = None
+    if need_rows:
+        d_rows = gemm_nt(d_logits, weight.t(), grad=True, bf16_ok=False)
+    if need_w:
+        dW = _wgrad(d_logits, rows, None, bf16_ok=False)
+    if need_b:
+        db = colsum(d_logits)
+    scale_multi([t for t in (d_rows, dW, db) if t is not None], d_loss.float())     # d loss upstream (a device scalar), one launch
+    return d_rows, dW, db
 
 
 class FrameHeadFn(torch.autograd.Function):
@@ -1689,19 +1695,13 @@ class FrameHeadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, weight, bias, y):
-        L = _lib.load()
         T, B, C = h.shape
-        V = weight.shape[0]
         hn = _f32c(h, "h").reshape(T * B, C)
         y_tm = y.t().contiguous().reshape(-1)                       # row t*B + b, like hn
         if y_tm.dtype != torch.int64 or y_tm.numel() != T * B:
             raise TypeError("FrameHeadFn: y must be int64 of shape (B, T)")
         need = any(ctx.needs_input_grad[:3])
-        logits = gemm_nt(hn, weight, bias, bf16_ok=False)          # train_nsplit arithmetic (fp32 in bf16 mode)
-        row_stats = torch.empty(2 * T * B, dtype=torch.float32, device=h.device)
-        out3 = torch.empty(3, dtype=torch.float32, device=h.device)
-        _lib.check(L.slu_frame_ce_fwd(logits.data_ptr(), y_tm.data_ptr(), T * B, V, -1, int(need),
-                                      row_stats.data_ptr(), out3.data_ptr(), _stream()), "slu_frame_ce_fwd")
+        logits, out3 = _frame_head_fwd(hn, weight, bias, y_tm, need)
         if need:
             ctx.save_for_backward(hn, weight, logits)
         ctx.set_materialize_grads(False)
@@ -1715,16 +1715,9 @@ class FrameHeadFn(torch.autograd.Function):
         if d_loss is None:
             return None, None, None, None
         hn, weight, d_logits = ctx.saved_tensors
-        T, B, C = ctx.shape
-        g = d_loss.float()
-        dh = dW = db = None
-        if ctx.needs_input_grad[0]:
-            dh = gemm_nt(d_logits, weight.t(), grad=True, bf16_ok=False).view(T, B, C)
-        if ctx.needs_input_grad[1]:
-            dW = _wgrad(d_logits, hn, None, bf16_ok=False)
-        if ctx.needs_input_grad[2]:
-            db = colsum(d_logits)
-        scale_multi([t for t in (dh, dW, db) if t is not None], g)      # d loss upstream (a device scalar), one launch
+        dh, dW, db = _frame_head_bwd(hn, weight, d_logits, d_loss, *ctx.needs_input_grad[:3])
+        if dh is not None:
+            dh = dh.view(ctx.shape)
         return dh, dW, db, None
 
 
@@ -1794,20 +1787,13 @@ class FrameHeadLenFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, lengths, offsets, n_total, weight, bias, y):
-        L = _lib.load()
-        T, B, C = h.shape
-        V = weight.shape[0]
         hp, yp = frame_pack_len(h, y, lengths, offsets, n_total)
         need = ctx.needs_input_grad[0] or ctx.needs_input_grad[4] or ctx.needs_input_grad[5]
-        logits = gemm_nt(hp, weight, bias, bf16_ok=False)          # (N, V): valid frames only
-        row_stats = torch.empty(2 * n_total, dtype=torch.float32, device=h.device)
-        out3 = torch.empty(3, dtype=torch.float32, device=h.device)
-        _lib.check(L.slu_frame_ce_fwd(logits.data_ptr(), yp.data_ptr(), n_total, V, -1, int(need),
-                                      row_stats.data_ptr(), out3.data_ptr(), _stream()), "slu_frame_ce_fwd")
+        logits, out3 = _frame_head_fwd(hp, weight, bias, yp, need)          # (N, V): valid frames only
         if need:
             ctx.save_for_backward(hp, weight, logits, lengths, offsets)
         ctx.set_materialize_grads(False)
-        ctx.shape = (T, B, C)
+        ctx.shape = tuple(h.shape)
         acc = out3[1]
         ctx.mark_non_differentiable(acc)
         return out3[0], acc
@@ -1817,16 +1803,9 @@ class FrameHeadLenFn(torch.autograd.Function):
         if d_loss is None:
             return None, None, None, None, None, None, None
         hp, weight, d_logits, lengths, offsets = ctx.saved_tensors
-        T, B, C = ctx.shape
-        g = d_loss.float()
-        dhp = dW = db = None
-        if ctx.needs_input_grad[0]:
-            dhp = gemm_nt(d_logits, weight.t(), grad=True, bf16_ok=False)
-        if ctx.needs_input_grad[4]:
-            dW = _wgrad(d_logits, hp, None, bf16_ok=False)
-        if ctx.needs_input_grad[5]:
-            db = colsum(d_logits)
-        scale_multi([t for t in (dhp, dW, db) if t is not None], g)     # d loss upstream (a device scalar), one launch
+        T, B, _ = ctx.shape
+        need = ctx.needs_input_grad
+        dhp, dW, db = _frame_head_bwd(hp, weight, d_logits, d_loss, need[0], need[4], need[5])
         dh = frame_unpack_len(dhp, lengths, offsets, T, B) if dhp is not None else None
         return dh, None, None, None, dW, db, None
 

@@ -619,7 +619,9 @@ int slu_beam_backtrack(const int32_t* backptr, const int32_t* labels, int64_t* o
  *   frames only (the average divides by their count, as avg_pool1d(ceil_mode=True) does at the end of a tensor); GRU
  *   direction 0 runs t = 0 .. n - 1, direction 1 starts at t = n - 1 from h = 0; the head's max over time and its
  *   argmax_t range over t < n only.  So an utterance's logits in a padded batch are its logits when it is run alone.
- * These five are forward / inference only: no route, no reserve, no dropout (masked training: the next block).  NULL
+ * These five are the plain forms of the stages: no route, no reserve, no dropout, no gradient.  The masked-training entry
+ * points of the next blocks are the same stages — the same kernels and the same size checks — with that one output or
+ * argument added, so a plain form equals its training form bit for bit where both are defined.  NULL
  * lengths: SLU_ERR_INVALID_ARG.  A length outside
  * [1, frames] is the HOST's to reject (slu_hip/ops.py raises ValueError before any launch); the kernels clamp it into
  * that range, so a bad value cannot index out of bounds.  The convolution and the GRU input projection need no entry
@@ -630,14 +632,17 @@ int slu_beam_backtrack(const int32_t* backptr, const int32_t* labels, int64_t* o
  *   slu_pool_act_len_fwd     slu_pool_act_fwd over the valid frames: x channels-last (B, L, C) with lengths = valid frames
  *                            of x (n_conv), [abs ->] max over the window clipped to the valid range -> LeakyReLU(slope),
  *                            0 for lo >= ceil(n / pool); y[b, lo, c] at b * out_sb + lo * out_sl + c (channels-last or
- *                            time-major); any pool in [1, 127] (pool = 1: activation + zero tail).
+ *                            time-major); any pool in [1, 127] (pool = 1: activation + zero tail).  Sizes as
+ *                            slu_pool_act_len_fwd_route (L < 2^31 - 128); one thread per element, or per four channels
+ *                            where C % 4 == 0 and the buffers are 16-byte aligned.
  *   slu_gru_seq_fwd_len      slu_gru_seq_fwd with reserve = NULL and per-sequence lengths: out[t, b] = 0 for
  *                            t >= lengths[b]; no gx value at t >= lengths[b] reaches any result (NaN there is harmless).
  *                            Persistent hidden sizes H = 16 / 32 / 64 / 128 only, both workgroup geometries, D = 1 / 2;
  *                            any other H (the step-wise path of slu_gru_seq_fwd): SLU_ERR_UNSUPPORTED — the host mirror
  *                            raises ValueError("lengths: hidden size ...") before it gets here.
  *   slu_seq_pool_len_fwd     Downsample on time-major x (T, B, C) -> y (ceil(T / factor), B, C): method 0 / 1 / 2 as
- *                            slu_dropout_pool_fwd, windows clipped to t < lengths[b], 0 for to >= ceil(n / factor).
+ *                            slu_dropout_pool_fwd, windows clipped to t < lengths[b], 0 for to >= ceil(n / factor):
+ *                            slu_dropout_pool_len_fwd at p = 0 without a mask (its kernels, its size checks).
  *   slu_cls_maxpool_len_fwd  slu_cls_maxpool_ce_fwd's logits (B, V) = max over t < lengths[b] of h_t W^T + b, argmax_t,
  *                            pred (B, S); y (NULL, or (B, S) labels): loss_acc (2) by slu_cls_maxpool_ce_fwd's
  *                            definitions (row_stats (B, 2) scratch and loss_acc then required).  No gradient, no dropout.
@@ -734,8 +739,9 @@ int slu_cls_maxpool_len_ce_fwd(const float* h, const float* weight, const float*
  * (channels-last or time-major); route (B, ceil(L / pool), C) bytes in slu_pool_act_fwd's format.  One thread per element,
  * or per four channels where C % 4 == 0 and the buffers are 16-byte aligned.  NULL lengths or pointers, pool outside
  * [1, 127]: SLU_ERR_INVALID_ARG.
- *   slu_pool_act_len_fwd_route   slu_pool_act_len_fwd (y bit-equal) that also writes the route bytes: arg-max offset
- *                            inside the window | negative-before-abs << 7; 0 at lo >= ceil(n_b / pool).
+ *   slu_pool_act_len_fwd_route   slu_pool_act_len_fwd (the same kernels with the route store compiled in: y bit-equal) that
+ *                            also writes the route bytes: arg-max offset inside the window | negative-before-abs << 7; 0 at
+ *                            lo >= ceil(n_b / pool).
  *   slu_pool_act_len_bwd     dx (B, L, C), every element written, by the definition of d_conv above.                    */
 int slu_pool_act_len_fwd_route(const float* x, float* y, uint8_t* route, const int32_t* lengths, int64_t B, int64_t L,
                                int64_t C, int64_t pool, int do_abs, float slope, int64_t out_sb, int64_t out_sl,
