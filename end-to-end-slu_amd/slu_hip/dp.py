@@ -453,7 +453,7 @@ def make_comm(rank, world_size, device):
         dist.all_gather_object(sigs, mine)
         if len(set(sigs)) != 1:
             raise RuntimeError("data parallel: the ranks disagree on arithmetic / weight-gradient settings (SLU_WGRAD_BRANCH, "
-                               "SLU_WGRAD_WGS, SLU_TRAIN_MATH, SLU_FROZEN_MATH, SLU_DTYPE, SLU_AUGMENT, SLU_AUGMENT_TEMPO): %s" % sigs)
+                               "SLU_WGRAD_WGS, SLU_TRAIN_MATH, SLU_FROZEN_MATH, SLU_DTYPE, SLU_AUGMENT, SLU_AUGMENT_TEMPO, SLU_CLIP_GRAD_NORM): %s" % sigs)
     if mode == "torch" or device.type != "cuda" or not dist.is_initialized():
         return None
     if mode == "auto" and dist.get_backend() == "nccl":

@@ -143,6 +143,10 @@ SIGNATURES = {
     "slu_adam_max_tensors": (c_int, []),
     "slu_adam_multi": (c_int, [vp, vp, vp, vp, vp, c_i64, c_int, vp, c_f64, c_f64, c_f64, c_f64, c_f64, vp, vp]),
     "slu_adam_advance_step": (c_int, [vp, c_u64, vp]),
+    "slu_grad_sumsq_chunk": (c_i64, []),
+    "slu_grad_sumsq_workspace_bytes": (c_sz, [vp, c_i64]),
+    "slu_grad_sumsq_multi": (c_int, [vp, vp, c_i64, c_int, vp, c_sz, c_i64, c_int, c_f64, c_f64, vp, vp, vp]),
+    "slu_adam_multi_clip": (c_int, [vp, vp, vp, vp, vp, c_i64, c_int, vp, c_f64, c_f64, c_f64, c_f64, c_f64, vp, vp, vp]),
     "slu_gru_seq_fwd": (c_int, [vp, vp, vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, vp]),
     "slu_gru_seq_bwd": (c_int, [vp, vp, vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, vp]),
     "slu_dropout_pool_fwd": (c_int, [vp, vp, c_i64, c_i64, vp, c_f32, c_u64, c_u64, vp, c_i64, c_u64, c_int,

@@ -1084,12 +1084,12 @@ def resolve_wgrad():
 
 def wgrad_signature():
     """What must be EQUAL on every data-parallel rank for the replicas to stay bit-identical: the weight-gradient launch's
-    (mode, workgroup budget), the arithmetic modes, the augmentation components and the tempo knob (SLU_AUGMENT and
-    SLU_AUGMENT_TEMPO as written: compared, not parsed here)."""
+    (mode, workgroup budget), the arithmetic modes, the augmentation components, the tempo knob and the gradient-clipping
+    threshold (SLU_AUGMENT, SLU_AUGMENT_TEMPO and SLU_CLIP_GRAD_NORM as written: compared, not parsed here)."""
     mode, budget = wgrad_branch()
-    return "%s/%d/%s/%s/%s/%s/%s" % (mode, budget, os.environ.get("SLU_TRAIN_MATH", "fp32"), os.environ.get("SLU_FROZEN_MATH", "bf16x3"),
-                                     os.environ.get("SLU_DTYPE", "f32"), os.environ.get("SLU_AUGMENT", "gain,crop,noise"),
-                                     os.environ.get("SLU_AUGMENT_TEMPO", "0"))
+    return "%s/%d/%s/%s/%s/%s/%s/%s" % (mode, budget, os.environ.get("SLU_TRAIN_MATH", "fp32"), os.environ.get("SLU_FROZEN_MATH", "bf16x3"),
+                                        os.environ.get("SLU_DTYPE", "f32"), os.environ.get("SLU_AUGMENT", "gain,crop,noise"),
+                                        os.environ.get("SLU_AUGMENT_TEMPO", "0"), os.environ.get("SLU_CLIP_GRAD_NORM", "off"))
 
 
 def gemm_tn_splitk_ok(operands):

@@ -174,6 +174,19 @@ def mask_augment_enabled():
     return on
 
 
+def clip_grad_norm_knob():
+    """SLU_CLIP_GRAD_NORM: unset (default) — plain Adam, launch for launch; a positive number or "inf" — every optimisation
+    step clips its gradients to that global 2-norm (torch.nn.utils.clip_grad_norm_'s rule) and a step with a non-finite
+    gradient is dropped, inside optimizer.step() on the device (slu_hip/optim.py; "inf" never clips but still measures and
+    skips).  -> None or the threshold; anything else is a ValueError.  An environment knob, not a cfg key: read_config
+    mirrors the reference's parse."""
+    v = os.environ.get("SLU_CLIP_GRAD_NORM")
+    if v is None:
+        return None
+    from slu_hip.optim import check_max_grad_norm
+    return check_max_grad_norm(v, "SLU_CLIP_GRAD_NORM")
+
+
 class _drop_lengths:
     """SLU batches of the training loops: (x, y) whatever the loader yields.  With SLU_MASK_PADDING=1 the collate function
     adds the utterances' sample counts as a third element (data.CollateWavsSLU); evaluation uses them
@@ -296,10 +309,15 @@ class Trainer:
         # same optimiser and defaults as the reference (training.py:19); on a GPU the update runs as one
         # launch per dtype on the HIP kernel (slu_hip/optim.py: same rule and per-parameter step counts)
         on_gpu = self._on_gpu()
+        self.clip_grad_norm = clip_grad_norm_knob()     # None, or the threshold of SLU_CLIP_GRAD_NORM (read once, here)
+        self._clip_cpu = {"sumsq": 0.0, "norm": 0.0, "coef": 1.0, "seen": 0, "clipped": 0, "skipped": 0}     # the CPU path's statistics
         if on_gpu:
             self.wgrad = ops.resolve_wgrad()       # (mode, workgroup budget) of the weight-gradient launches, fixed for this trainer
             from slu_hip.optim import HipAdam
-            self.optimizer = HipAdam(model.parameters(), lr=self.lr)
+            if self.clip_grad_norm is None:
+                self.optimizer = HipAdam(model.parameters(), lr=self.lr)
+            else:
+                self.optimizer = HipAdam(model.parameters(), lr=self.lr, max_grad_norm=self.clip_grad_norm)
         else:
             self.optimizer = torch.optim.Adam(model.parameters(), lr=self.lr)
         self.epoch = 0
@@ -361,7 +379,26 @@ class Trainer:
             ops._Fork.join(loss.device)          # branches left open by the backward pass (ops._Fork.defer): one join
         if self.bucket is not None:
             self.bucket.allreduce_mean()
-        self.optimizer.step()
+        if self.clip_grad_norm is not None and not self._hip_adam and not self._clip_on_host():
+            return                               # a non-finite gradient: the step is dropped
+        self.optimizer.step()                    # HipAdam clips inside its own launches (captured steps included)
+
+    def _clip_on_host(self):
+        """SLU_CLIP_GRAD_NORM on the CPU path (torch.optim.Adam): the definition HipAdam applies on the device, by the
+        float64 helper.  The bucket has already taken the data-parallel mean there.  -> False: skip this step."""
+        from slu_hip.optim import clip_gradients_
+        st = self._clip_cpu
+        st["sumsq"], st["norm"], st["coef"], skipped = clip_gradients_(self._parameters(), self.clip_grad_norm)
+        st["seen"] += 1
+        st["skipped"] += int(skipped)
+        st["clipped"] += int(not skipped and st["coef"] < 1.0)
+        return not skipped
+
+    def clip_stats(self):
+        """The gradient-clipping statistics of this trainer (HipAdam.clip_stats's keys), None with the knob unset."""
+        if self.clip_grad_norm is None:
+            return None
+        return self.optimizer.clip_stats() if self._hip_adam else dict(self._clip_cpu)
 
     def _is_asr(self, dataset):
         return isinstance(dataset, ASRDataset)
@@ -865,6 +902,11 @@ class Trainer:
                 warnings.warn("non-finite epoch metrics with SLU_FROZEN_MATH=f16x2 (the UNGUARDED form of the scheme: "
                               "operands must stay below 65504 in magnitude) — the default mode guards the range and falls "
                               "back to bf16x3 by itself")
+        if train and self.clip_grad_norm is not None:
+            cs = self.clip_stats()                   # one read of the device record per epoch, with the device idle
+            self._say("gradient clipping (max norm %g): last norm %.6g, last coefficient %.6g; %d steps so far, %d clipped, "
+                      "%d skipped (non-finite)" % (self.clip_grad_norm, cs["norm"], cs["coef"], cs["seen"], cs["clipped"],
+                                                   cs["skipped"]))
         if seq2seq and not train:
             means[1] = means[1] + means[-1]          # intent_acc += string accuracy (the model's own acc is 0)
         return means[:len(names)]

@@ -826,6 +826,56 @@ int slu_adam_multi(void* const* params, const void* const* grads, void* const* e
                    double grad_div, uint32_t* ticket, void* stream);
 int slu_adam_advance_step(int64_t* step_dev, uint64_t cohort_mask, void* stream);
 
+/* -------- global-norm gradient clipping and non-finite step skipping (no counterpart in the reference) --------
+ * Definition — torch.nn.utils.clip_grad_norm_ with norm_type = 2, its 1e-6 included — for one optimisation step with
+ * threshold c (0 < c <= inf) and grad_div = d:
+ *   S    = sum of g_e^2 over every element of every tensor the step updates, accumulated in float64.  The tensors
+ *          counted are exactly those of the step's plan: a parameter without a gradient is not counted, as in torch.
+ *   n    = sqrt(S) / d: the norm of the MEAN gradient (under data parallelism the bucket holds the sum over ranks).
+ *   S not finite: the step is SKIPPED — no parameter, exp_avg or exp_avg_sq element changes by a bit, no step counter
+ *          advances (the bias corrections continue as if the step had never been taken), steps_skipped goes up by one;
+ *          the record then holds coef = 0.
+ *   else coef = min(1, c / (n + 1e-6)) in float64; float32 tensors use (g / d) * (float)coef, float64 tensors
+ *          (g / d) * coef, and Adam proceeds as in slu_adam_multi.  c = inf never clips (coef == 1 exactly) but
+ *          measures the norm and skips non-finite steps.
+ * slu_grad_sumsq_multi: the sum of squares of up to slu_adam_max_tensors() gradient tensors of one dtype, one workgroup
+ * per slu_grad_sumsq_chunk() elements of a tensor; workgroup w writes its float64 partial sum to workspace slot
+ * slot_offset + w (no floating-point atomics: the result is deterministic).  A step whose plan needs several lists
+ * (two dtypes, 32 tensors each) launches them on ONE stream at consecutive slot offsets (offset of the next list =
+ * this list's offset + sum of ceil(numel / chunk)); the LAST list passes finalize = 1: its last workgroup (a ticket;
+ * partials are published with a device-scope release and read after an acquire) adds slots 0 .. offset + chunks - 1
+ * in a fixed tree and writes *record.  No separate finalise launch, no host read.
+ * Accuracy: every term is >= 0, so the relative error of S is at most depth * 2^-53 with
+ *   depth = SLU_GRAD_SUMSQ_DEPTH_BASE + ceil(slots / 256)     (additions on the longest path of the tree:
+ *   16 in a thread, 8 in the workgroup, ceil(slots / 256) + 8 in the finalising workgroup, + 1 for the rounding of
+ *   g * g of float64 tensors; (double)g * (double)g is exact for a float g)
+ * ticket: a zero-initialised device uint32 of the caller's, zero again afterwards.  record: device memory, zeroed once
+ * by the caller; the counters run on from launch to launch.  slu_grad_sumsq_workspace_bytes: the bytes all lists of a
+ * step need together (numel: every tensor of the step, any count); 0 for invalid arguments.
+ * slu_adam_multi_clip = slu_adam_multi that reads *record (same stream, after the finalising reduction): the
+ * coefficient multiplies the gradient after grad_div; record->skip set: every element and *step_dev stay as they
+ * are (the ticket word is still returned to zero).  slu_adam_multi itself is unchanged. */
+#define SLU_GRAD_SUMSQ_DEPTH_BASE 33
+typedef struct slu_clip_record {
+  double sumsq;            /* S of the last step */
+  double norm;             /* n */
+  double coef;             /* applied coefficient (0 when the step was skipped) */
+  int64_t skip;            /* 1: the last step was skipped */
+  int64_t steps_seen;      /* running counters */
+  int64_t steps_clipped;   /* steps with coef < 1 */
+  int64_t steps_skipped;
+  int64_t reserved;
+} slu_clip_record;
+int64_t slu_grad_sumsq_chunk(void);
+size_t slu_grad_sumsq_workspace_bytes(const int64_t* numel, int64_t count);
+int slu_grad_sumsq_multi(const void* const* grads, const int64_t* numel, int64_t count, int elem_bytes,
+                         void* workspace, size_t workspace_bytes, int64_t slot_offset, int finalize,
+                         double max_norm, double grad_div, uint32_t* ticket, slu_clip_record* record, void* stream);
+int slu_adam_multi_clip(void* const* params, const void* const* grads, void* const* exp_avg,
+                        void* const* exp_avg_sq, const int64_t* numel, int64_t count, int elem_bytes,
+                        int64_t* step_dev, double lr, double beta1, double beta2, double eps,
+                        double grad_div, uint32_t* ticket, const slu_clip_record* record, void* stream);
+
 /* -------- data parallelism: the gradient all-reduce over the GPUs of a node (RCCL over xGMI) -----------------
  * The reference has no distributed code; these are thin wrappers over the RCCL instance the process already
  * holds (resolved at run time, not linked), so that the one collective of a training step can be enqueued on
