@@ -22,6 +22,15 @@
 // finished, else u + 1.  When all W survivors are finished the workgroup fills the planes u + 1 .. U - 1 with
 // backptr = k, labels = eos, sets step[b] = U and adds 1 to *n_done; an utterance that fills its history unfinished adds
 // its 1 too, so the host stops at *n_done == batch.  eos < 0 is slu_beam_select: none of this runs.
+//
+// Lexicon (slu_beam_select_lex, the LEX instantiation; this project's own rule as well): the labels a hypothesis may take
+// next are the edges of its node in a trie of the valid label sequences (CSR: trie_off (N + 1), trie_lab / trie_dst (N - 1),
+// labels ascending within a node, node 0 the root, a node reached over eos a leaf).  node (W, batch) travels with the
+// hypotheses like lengths.  An unfinished source at a node of d children has min(W, d) candidates — its children in the
+// row's order, scored as above with lse over the WHOLE row — and W - min(W, d) absent ones (-inf, label eos).  The top-W
+// pass therefore reads d logits, not V.  A -inf candidate can now survive (fewer than W finite ones exist): it is written
+// with label eos, so it is finished from the next step on and keeps -inf by the finished rule — a dead slot.  node[k] is
+// the chosen edge's child, or the source's node if the source was finished or the candidate absent.
 #include <limits.h>
 #include "slu_common.h"
 #include "slu_reduce.h"
@@ -44,6 +53,9 @@ struct BeamArgs {
   int eos;                             // < 0: no finished hypotheses (slu_beam_select)
   int* lengths;                        // eos >= 0: (W, batch) hypothesis lengths, updated in place
   int* n_done;                         // eos >= 0: utterances whose search has ended
+  const int* trie_off; const int* trie_lab; const int* trie_dst;   // LEX: the trie, (N + 1) / (N - 1) / (N - 1)
+  int N;                               // LEX: trie nodes
+  int* node;                           // LEX: (W, batch) the hypotheses' trie nodes, updated in place
 };
 
 // (value, index) a before b: larger value, equal values: lower index
@@ -51,6 +63,7 @@ __device__ __forceinline__ bool beam_before(float av, int ai, float bv, int bi) 
   return av > bv || (av == bv && ai < bi);
 }
 
+template <bool LEX>
 __global__ void __launch_bounds__(256)
 beam_select_kernel(const BeamArgs a) {
   __shared__ float red[4];
@@ -61,6 +74,8 @@ beam_select_kernel(const BeamArgs a) {
   __shared__ float sel_s[BEAM_MAX_W];
   __shared__ int sel_src[BEAM_MAX_W], sel_lab[BEAM_MAX_W];
   __shared__ int fin_s[BEAM_MAX_W], len_s[BEAM_MAX_W];
+  __shared__ int node_s[BEAM_MAX_W], sel_node[BEAM_MAX_W];          // LEX only
+  __shared__ int top_n[BEAM_MAX_W * BEAM_MAX_W];                    // LEX only: the candidate's next node
   const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int W = a.W, V = a.V, batch = a.batch, eos = a.eos;
   const int u = a.step[b];
@@ -76,16 +91,32 @@ beam_select_kernel(const BeamArgs a) {
     fin_s[tid] = (u > 0 && a.labels[((size_t)(u - 1) * W + tid) * batch + b] == eos) ? 1 : 0;
     len_s[tid] = a.lengths[(size_t)tid * batch + b];
   }
+  if (LEX) {
+    if (tid < W) {
+      const int n = a.node[(size_t)tid * batch + b];
+      node_s[tid] = (n >= 0 && n < a.N) ? n : 0;
+    }
+    __syncthreads();
+  }
 
   // top W of each row: one wave per row, W passes; a pass takes the first element AFTER the previous pick in the
   // order (value descending, index ascending), so equal logits come out by index and nothing is marked or moved
+  // LEX: the row's elements are the node's edges e (labels ascend with e, so the edge index orders equal logits as the
+  // label does); a pass that finds none (k >= d) leaves the candidate absent
   for (int w = wave; w < W; w += 4) {
     const float* lg = a.logits + ((size_t)w * batch + b) * V;
+    int e0 = 0, e1 = V;
+    if (LEX) {
+      e0 = min(max(a.trie_off[node_s[w]], 0), a.N - 1);
+      e1 = min(max(a.trie_off[node_s[w] + 1], e0), a.N - 1);
+    }
     float last_v = INFINITY; int last_i = -1;
     for (int k = 0; k < W; ++k) {
       float bv = -INFINITY; int bi = INT_MAX;
-      for (int v = lane; v < V; v += 64) {
-        const float x = lg[v];
+      for (int v = e0 + lane; v < e1; v += 64) {
+        float x;
+        if (LEX) { const int l = a.trie_lab[v]; x = lg[(l >= 0 && l < V) ? l : 0]; }
+        else x = lg[v];
         const bool after = x < last_v || (x == last_v && v > last_i);
         if (after && beam_before(x, v, bv, bi)) { bv = x; bi = v; }
       }
@@ -96,7 +127,14 @@ beam_select_kernel(const BeamArgs a) {
         if (beam_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
       }
       last_v = bv; last_i = bi;
-      if (lane == 0) { top_s[w * W + k] = bv; top_i[w * W + k] = (bi >= 0 && bi < V) ? bi : 0; }
+      if (LEX) {
+        if (lane == 0) {
+          const bool absent = bi < e0 || bi >= e1;
+          int l = eos, n = node_s[w];
+          if (!absent) { l = a.trie_lab[bi]; l = (l >= 0 && l < V) ? l : 0; n = a.trie_dst[bi]; n = (n >= 0 && n < a.N) ? n : 0; }
+          top_s[w * W + k] = absent ? -INFINITY : bv; top_i[w * W + k] = l; top_n[w * W + k] = n;
+        }
+      } else if (lane == 0) { top_s[w * W + k] = bv; top_i[w * W + k] = (bi >= 0 && bi < V) ? bi : 0; }
     }
   }
   __syncthreads();
@@ -116,7 +154,14 @@ beam_select_kernel(const BeamArgs a) {
     const float s = cand[tid];
     int rank = 0;
     for (int c = 0; c < n_cand; ++c) rank += (cand[c] > s || (cand[c] == s && c < tid)) ? 1 : 0;
-    if (rank < W) { sel_s[rank] = s; sel_src[rank] = tid / W; sel_lab[rank] = fin_s[tid / W] ? eos : top_i[tid]; }
+    if (rank < W) {
+      sel_s[rank] = s; sel_src[rank] = tid / W; sel_lab[rank] = fin_s[tid / W] ? eos : top_i[tid];
+      if (LEX) {                       // a -inf survivor is a dead slot: eos, and it stays where its source was
+        const bool stay = fin_s[tid / W] || s == -INFINITY;
+        if (stay) sel_lab[rank] = eos;
+        sel_node[rank] = stay ? node_s[tid / W] : top_n[tid];
+      }
+    }
   }
   __syncthreads();
 
@@ -126,6 +171,7 @@ beam_select_kernel(const BeamArgs a) {
     a.backptr[h] = sel_src[tid];
     a.labels[h] = sel_lab[tid];
     if (eos >= 0) a.lengths[(size_t)tid * batch + b] = fin_s[sel_src[tid]] ? len_s[sel_src[tid]] : u + 1;
+    if (LEX) a.node[(size_t)tid * batch + b] = sel_node[tid];
   }
   bool all_fin = eos >= 0;             // uniform over the workgroup
   for (int k = 0; k < W; ++k) all_fin = all_fin && sel_lab[k] == eos;
@@ -202,12 +248,15 @@ beam_backtrack_kernel(const int* __restrict__ backptr, const int* __restrict__ l
 
 using namespace slu;
 
-// both entry points; eos < 0 (slu_beam_select) has no finished hypotheses
+// the three entry points; eos < 0 (slu_beam_select) has no finished hypotheses, node == nullptr (all but
+// slu_beam_select_lex) no lexicon
 static int beam_select_launch(const float* logits, float* scores, const float* state_next, float* state, int32_t* step,
                               int32_t* backptr, int32_t* labels, float* y_prev, int64_t ld_y, const float* embed_w,
                               int64_t ld_ew, const float* embed_b, float* inp, int64_t ld_inp, int64_t E, int64_t W,
                               int64_t batch, int64_t V, int64_t L, int64_t Dd, int64_t U, int64_t eos, int32_t* lengths,
-                              int32_t* n_done, void* stream) {
+                              int32_t* n_done, void* stream, const int32_t* trie_off = nullptr,
+                              const int32_t* trie_lab = nullptr, const int32_t* trie_dst = nullptr, int64_t N = 0,
+                              int32_t* node = nullptr) {
   SLU_REQUIRE(logits && scores && state_next && state && step && backptr && labels, "slu_beam_select: null pointer");
   SLU_REQUIRE(y_prev || inp, "slu_beam_select: null pointer (neither y_prev nor inp: nothing to feed the next step)");
   SLU_REQUIRE(!inp || (embed_w && embed_b && E > 0 && ld_inp >= E && ld_ew >= V),
@@ -227,7 +276,9 @@ static int beam_select_launch(const float* logits, float* scores, const float* s
   a.labels = labels; a.y_prev = y_prev; a.ld_y = ld_y; a.embed_w = embed_w; a.ld_ew = ld_ew; a.embed_b = embed_b;
   a.inp = inp; a.ld_inp = ld_inp; a.E = (int)E; a.W = (int)W; a.batch = (int)batch; a.V = (int)V; a.row = (int)(L * Dd);
   a.U = (int)U; a.eos = (int)eos; a.lengths = lengths; a.n_done = n_done;
-  hipLaunchKernelGGL(beam_select_kernel, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, a);
+  a.trie_off = trie_off; a.trie_lab = trie_lab; a.trie_dst = trie_dst; a.N = (int)N; a.node = node;
+  if (node) hipLaunchKernelGGL(beam_select_kernel<true>, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(beam_select_kernel<false>, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, a);
   SLU_CHECK_LAUNCH("beam_select_kernel");
   return SLU_OK;
 }
@@ -249,6 +300,22 @@ extern "C" int slu_beam_select_eos(const float* logits, float* scores, const flo
   SLU_REQUIRE(eos >= 0 && eos < V, "slu_beam_select_eos: eos outside [0, V)");
   return beam_select_launch(logits, scores, state_next, state, step, backptr, labels, y_prev, ld_y, embed_w, ld_ew, embed_b,
                             inp, ld_inp, E, W, batch, V, L, Dd, U, eos, lengths, n_done, stream);
+}
+
+extern "C" int slu_beam_select_lex(const float* logits, float* scores, const float* state_next, float* state,
+                                   int32_t* step, int32_t* backptr, int32_t* labels, float* y_prev, int64_t ld_y,
+                                   const float* embed_w, int64_t ld_ew, const float* embed_b, float* inp, int64_t ld_inp,
+                                   int64_t E, int64_t W, int64_t batch, int64_t V, int64_t L, int64_t Dd, int64_t U,
+                                   int64_t eos, int32_t* lengths, int32_t* n_done, const int32_t* trie_off,
+                                   const int32_t* trie_lab, const int32_t* trie_dst, int64_t N, int32_t* node,
+                                   void* stream) {
+  SLU_REQUIRE(trie_off && trie_lab && trie_dst && node, "slu_beam_select_lex: null pointer (trie_off, trie_lab, trie_dst, node)");
+  SLU_REQUIRE(N >= 2 && N < (1LL << 31), "slu_beam_select_lex: a trie has N >= 2 nodes (and fewer than 2^31)");
+  SLU_REQUIRE(lengths && n_done, "slu_beam_select_lex: null pointer (lengths, n_done)");
+  SLU_REQUIRE(eos >= 0 && eos < V, "slu_beam_select_lex: eos outside [0, V)");
+  return beam_select_launch(logits, scores, state_next, state, step, backptr, labels, y_prev, ld_y, embed_w, ld_ew, embed_b,
+                            inp, ld_inp, E, W, batch, V, L, Dd, U, eos, lengths, n_done, stream, trie_off, trie_lab, trie_dst,
+                            N, node);
 }
 
 extern "C" int slu_beam_backtrack(const int32_t* backptr, const int32_t* labels, int64_t* out, float* one_hot, int64_t W,

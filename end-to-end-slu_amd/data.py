@@ -510,6 +510,23 @@ class SyntheticSeq2SeqDataset(SLUDataset):
         return x[idx % bs], y[idx % bs]
 
 
+def intent_lexicon(dataset):
+    """The sorted unique semantics strings of a seq2seq SLU dataset: the closed set its targets come from (31 on Fluent
+    Speech Commands), what Model.set_lexicon takes.  A synthetic dataset's strings are read off its one-hot targets."""
+    if not getattr(dataset, "seq2seq", False):
+        raise ValueError("intent_lexicon: the dataset has no seq2seq targets")
+    if hasattr(dataset, "_values"):
+        return sorted(set(dataset._values))
+    S = dataset.Sy_intent
+    sos, eos = S.index("<sos>"), S.index("<eos>")
+    strings = set()
+    for _, y in dataset.batches:
+        for row in y.max(dim=2)[1].tolist():
+            row = row[1:] if row and row[0] == sos else row
+            strings.add("".join(S[c] for c in (row[:row.index(eos)] if eos in row else row)))
+    return sorted(strings)
+
+
 def read_textgrid(path):
     """Interval tiers of a Praat TextGrid (the long "ooTextFile" format the Montreal Forced Aligner writes
     for LibriSpeech): {tier name: [(minTime, maxTime, mark), ...]}; the first tier of a name wins, like

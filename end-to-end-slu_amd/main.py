@@ -12,8 +12,8 @@ import argparse
 import numpy as np
 import torch
 
-from data import get_ASR_datasets, get_SLU_datasets, read_config
-from models import PretrainedModel, Model, set_dropout_seed
+from data import get_ASR_datasets, get_SLU_datasets, intent_lexicon, read_config
+from models import PretrainedModel, Model, beam_lexicon_enabled, set_dropout_seed
 from slu_hip import dp
 from training import Trainer
 
@@ -50,6 +50,8 @@ def run(args):
     if args.train:
         train_dataset, valid_dataset, test_dataset = get_SLU_datasets(config)
         model = Model(config=config)
+        if beam_lexicon_enabled() and config.seq2seq:    # SLU_BEAM_LEXICON=1: decode only the training split's semantics
+            model.set_lexicon(intent_lexicon(train_dataset))
         trainer = Trainer(model=model, config=config)
         if args.restart:
             trainer.load_checkpoint()

@@ -33,6 +33,7 @@ import torch
 from slu_hip import ops as _ops
 from slu_hip import lib as _lib
 from slu_hip import knobs as _knobs
+from slu_hip import lexicon as _lexicon
 
 
 # ------------------------------------------------------------------------------------------------
@@ -210,6 +211,18 @@ def beam_eos_enabled():
     <eos> are finished (the rule in Seq2SeqDecoder.infer): Model.predict_intents / decode_intents / decode_nbest pass
     eos = Sy_intent.index("<eos>") to the search SLU_BEAM_SEARCH selects, which stops once every utterance is done."""
     return _knobs.flag("SLU_BEAM_EOS")
+
+
+def beam_lexicon_enabled():
+    """SLU_BEAM_LEXICON: "0" (default) — the beam search is free to spell any string, whether Model.set_lexicon has stored a
+    lexicon or not; "1" (needs SLU_BEAM_EOS=1: the entries end in <eos>) — Model.predict_intents / decode_intents /
+    decode_nbest / exact_match pass the stored lexicon to the search SLU_BEAM_SEARCH selects, which then decodes only the
+    lexicon's strings (include/slu_hip.h, slu_beam_select_lex); without a stored lexicon they raise ValueError."""
+    on = _knobs.flag("SLU_BEAM_LEXICON")
+    if on and not beam_eos_enabled():
+        raise ValueError("SLU_BEAM_LEXICON=1 needs SLU_BEAM_EOS=1: a lexicon's entries end in <eos>, and only finished "
+                         "hypotheses stop there")
+    return on
 
 
 def mask_train_cnn_enabled():
@@ -636,6 +649,17 @@ def sort_beam(beam_extensions, beam_extension_scores, beam_pointers):
     return ext[order, cols], sc[order, cols], ptr[order, cols]
 
 
+def _check_lexicon(lexicon, eos, V, U):
+    """What infer / search refuse of a lexicon= argument, on the host, before a launch."""
+    if eos is None:
+        raise ValueError("lexicon needs eos: its entries end in it")
+    if lexicon.eos != eos or lexicon.V != V:
+        raise ValueError("lexicon: built for eos = %d of %d labels, the search has eos = %d of %d"
+                         % (lexicon.eos, lexicon.V, eos, V))
+    if lexicon.max_len > U:
+        raise ValueError("lexicon: its longest entry has %d labels, the search has U = %d steps" % (lexicon.max_len, U))
+
+
 class Seq2SeqDecoder(torch.nn.Module):
     """Attention-based decoder for seq2seq SLU (reference models.py:504-651)."""
 
@@ -700,7 +724,8 @@ class Seq2SeqDecoder(torch.nn.Module):
         _, log_p = self.teacher_forced(encoder_outputs.transpose(0, 1), y, n)
         return log_p
 
-    def infer(self, encoder_outputs, Sy, B=4, debug=False, y_lengths=None, eos=None, want_lengths=False, enc_lengths=None):
+    def infer(self, encoder_outputs, Sy, B=4, debug=False, y_lengths=None, eos=None, want_lengths=False, enc_lengths=None,
+              lexicon=None):
         """Beam search of width B for argmax_y log p(y|x) (reference models.py:559-651; B = 1 is greedy search).
         -> (beam_scores (B, batch), beam (B, batch, U, |Sy|) one-hot), U = 200 or max(y_lengths).
         All B hypotheses of all utterances advance in ONE batched decoder step on the HIP kernels (rows w * batch +
@@ -726,7 +751,15 @@ class Seq2SeqDecoder(torch.nn.Module):
 
         enc_lengths (None: the search above): batch encoder frame counts in [1, T] -> every hypothesis of utterance b
         attends over its first enc_lengths[b] frames (ops.attention_len_fwd, the counts replicated per hypothesis):
-        utterance b's hypotheses and scores are those of encoder_outputs[b:b+1, :enc_lengths[b]] searched alone."""
+        utterance b's hypotheses and scores are those of encoder_outputs[b:b+1, :enc_lengths[b]] searched alone.
+
+        lexicon (a slu_hip.lexicon.Lexicon; None: the search above; needs eos) constrains the search to the lexicon's entries
+        (include/slu_hip.h, slu_beam_select_lex): node (W, batch) travels with the hypotheses, every slot starting at the
+        trie's root.  An unfinished source at a node of d children has its min(W, d) best children as candidates, scored
+        (logit - lse) + score with lse over all V logits — nothing is renormalised — and W - min(W, d) absent ones (-inf,
+        label eos).  A survivor with score -inf is a dead slot: label eos, so finished from the next step on, -inf for
+        good.  node follows the chosen edge; it stays for a finished source or an absent candidate.  A finished
+        hypothesis' score is log p(entry | x); with at most W entries the search returns every entry, ranked."""
         n_host = None
         if enc_lengths is not None:
             n_host = _host_lengths(enc_lengths, encoder_outputs.shape[0], encoder_outputs.shape[1], "encoder frames")
@@ -738,6 +771,8 @@ class Seq2SeqDecoder(torch.nn.Module):
         if eos is not None and not 0 <= eos < V:
             raise ValueError("eos = %r outside [0, %d)" % (eos, V))
         U = 200 if y_lengths is None else max(y_lengths)
+        if lexicon is not None:
+            _check_lexicon(lexicon, eos, V, U)
         names, tensors = self._params()
         P = {n: t.detach() for n, t in zip(names, tensors)}
         Kd, Vd = P["key.weight"].shape[0], P["value.weight"].shape[0]
@@ -766,11 +801,26 @@ class Seq2SeqDecoder(torch.nn.Module):
             cols = torch.arange(bsz, device=dev)
             zeros_y = torch.zeros(R, V, dtype=torch.float32, device=dev)
             lengths = torch.zeros(W, bsz, dtype=torch.int32, device=dev)
+            if lexicon is not None:
+                # child[n, v]: the node behind edge v of node n, or -1
+                off, lab, dst = (t.long() for t in lexicon.tables(dev))
+                child = torch.full((lexicon.N, V), -1, dtype=torch.int64, device=dev)
+                child[torch.repeat_interleave(torch.arange(lexicon.N, device=dev), off[1:] - off[:-1]), lab] = dst
+                node = torch.zeros(W, bsz, dtype=torch.int64, device=dev)
             for u in range(U):
                 _ops.decoder_step(P, keys, values, state, state_next, y_prev, q, inp0, att_w, gi, gh, None, drop, logits, u,
                                   (0.0, None, 0, 0, None, R * Dd), n_rows)
                 _ops.logsoftmax_dot_fwd(logits, zeros_y, sink, lse)                     # lse only (y = 0)
-                top_s, top_i = logits.topk(W, dim=1)                                    # log_softmax keeps the order
+                if lexicon is None:
+                    top_s, top_i = logits.topk(W, dim=1)                                # log_softmax keeps the order
+                else:
+                    # the W best children of every row's node (equal logits: lower label first); what is not a child is -inf
+                    nxt = child[node.view(R)]                                           # (R, V)
+                    masked = torch.where(nxt >= 0, logits, torch.full_like(logits, float("-inf")))
+                    top_s, top_i = (t[:, :W] for t in masked.sort(dim=1, descending=True, stable=True))
+                    absent = top_s == float("-inf")
+                    top_i = torch.where(absent, torch.full_like(top_i, eos), top_i)
+                    nxt = torch.where(absent, node.view(R, 1).expand(R, W), nxt.gather(1, top_i)).view(W, bsz, W)
                 cand = (top_s - lse.unsqueeze(1)).view(W, bsz, W) + scores.unsqueeze(2)  # [src hypothesis, b, extension]
                 if u == 0:
                     cand[1:] = float("-inf")
@@ -781,11 +831,16 @@ class Seq2SeqDecoder(torch.nn.Module):
                     frozen[:, :, 0] = scores                                            # the score itself, nothing added
                     cand = torch.where(fin.unsqueeze(2), frozen, cand)
                     top_i = torch.where(fin.unsqueeze(2), torch.full_like(top_i, eos), top_i)
+                    if lexicon is not None:
+                        nxt = torch.where(fin.unsqueeze(2), node.unsqueeze(2).expand(W, bsz, W), nxt)
                 flat = cand.permute(1, 0, 2).reshape(bsz, W * W)                        # candidate order: src major
                 best, pick = flat.sort(dim=1, descending=True, stable=True)
                 best, pick = best[:, :W].t().contiguous(), pick[:, :W].t()              # (W, bsz)
                 src, ext = pick // W, pick % W
                 label = top_i[src, cols.unsqueeze(0), ext]                              # (W, bsz)
+                if lexicon is not None:
+                    label = torch.where(best == float("-inf"), torch.full_like(label, eos), label)   # dead slots
+                    node = nxt[src, cols.unsqueeze(0), ext]
                 hyp = hyp[src, cols.unsqueeze(0)]
                 hyp[:, :, u] = label
                 scores = best
@@ -811,23 +866,26 @@ class Seq2SeqDecoder(torch.nn.Module):
     SEARCH_CHUNK = 8
     SEARCH_PLANS = 4            # captured shapes kept (ragged evaluation batches differ in T), least recently used out
 
-    def _search_plan(self, P, dev, bsz, T, W, U, V, eos=None, with_lengths=False):
-        """Static buffers (+ the captured chunk of SEARCH_CHUNK steps) of one search shape, eos label and attention kind
-        (with_lengths: the chunk's attention reads the plan's own (W * bsz) int32 frame counts)."""
+    def _search_plan(self, P, dev, bsz, T, W, U, V, eos=None, with_lengths=False, lexicon=None):
+        """Static buffers (+ the captured chunk of SEARCH_CHUNK steps) of one search shape, eos label, attention kind
+        (with_lengths: the chunk's attention reads the plan's own (W * bsz) int32 frame counts) and lexicon (the chunk's
+        slu_beam_select_lex reads the lexicon's device tables and the plan's node buffer)."""
         from slu_hip import pipeline as _pipeline
         use_graph = _pipeline.graphs_enabled()
         key = (bsz, T, W, U, V, eos, bool(with_lengths), str(dev), use_graph, tuple((n, t.data_ptr(), tuple(t.shape)) for n, t in P.items()
                                                           if torch.is_tensor(t)))
+        if lexicon is not None:
+            key += (lexicon.key(),)
         plans = self.__dict__.setdefault("_search_plans", {})
         plan = plans.pop(key, None)
         if plan is None:
-            plan = self._build_search_plan(P, dev, bsz, T, W, U, V, use_graph, eos, with_lengths)
+            plan = self._build_search_plan(P, dev, bsz, T, W, U, V, use_graph, eos, with_lengths, lexicon)
             while len(plans) >= self.SEARCH_PLANS:
                 plans.pop(next(iter(plans)))
         plans[key] = plan                                   # most recently used last
         return plan
 
-    def _build_search_plan(self, P, dev, bsz, T, W, U, V, use_graph, eos=None, with_lengths=False):
+    def _build_search_plan(self, P, dev, bsz, T, W, U, V, use_graph, eos=None, with_lengths=False, lexicon=None):
         from slu_hip import pipeline as _pipeline
         Kd, Vd = P["key.weight"].shape[0], P["value.weight"].shape[0]
         Lc, Dd = P["initial_state"].shape
@@ -839,17 +897,21 @@ class Seq2SeqDecoder(torch.nn.Module):
              "q": f(R, Kd), "inp0": f(R, E + Vd), "att_w": f(R, T), "logits": f(R, V), "gi": f(R, 3 * Dd),
              "gh": f(Lc, R, 3 * Dd), "drop": [f(R, Dd) for _ in range(Lc - 1)],
              # step counters (bsz int32), running scores (W * bsz fp32), hypothesis lengths (W * bsz int32) and the
-             # count of finished utterances (1 int32) share one buffer: ONE fill re-arms a search
-             "ctl": i32(bsz + 2 * R + 1), "backptr": i32(U, W, bsz), "labels": i32(U, W, bsz), "graph": None}
+             # count of finished utterances (1 int32) share one buffer: ONE fill re-arms a search; a lexicon's trie nodes
+             # (W * bsz int32, zero = the root) come behind them
+             "ctl": i32(bsz + 2 * R + 1 + (R if lexicon is not None else 0)), "backptr": i32(U, W, bsz),
+             "labels": i32(U, W, bsz), "graph": None}
         b["ctl"].zero_()
         # the rows' encoder frame counts: a static buffer the (captured) chunk reads, filled by one copy per search
         b["n_rows"] = torch.full((R,), T, dtype=torch.int32, device=dev) if with_lengths else None
         b["step"], b["scores"] = b["ctl"][:bsz], b["ctl"][bsz:bsz + R].view(torch.float32).view(W, bsz)
-        b["lengths"], b["n_done"] = b["ctl"][bsz + R:bsz + 2 * R].view(W, bsz), b["ctl"][bsz + 2 * R:]
+        b["lengths"], b["n_done"] = b["ctl"][bsz + R:bsz + 2 * R].view(W, bsz), b["ctl"][bsz + 2 * R:bsz + 2 * R + 1]
         if eos is not None:
             # n_done after every chunk, read behind the next chunk's launches (search)
             b["n_done_host"] = torch.empty(-(-U // self.SEARCH_CHUNK), dtype=torch.int32, pin_memory=True)
         fin = {} if eos is None else {"eos": eos, "lengths": b["lengths"], "n_done": b["n_done"]}
+        if lexicon is not None:
+            fin.update(trie=lexicon.tables(dev), node=b["ctl"][bsz + 2 * R + 1:].view(W, bsz))
         embed = (P["embed.weight"], P["embed.bias"], b["inp0"])
 
         def chunk():
@@ -878,7 +940,7 @@ class Seq2SeqDecoder(torch.nn.Module):
         return b
 
     def search(self, encoder_outputs, Sy, B=4, y_lengths=None, want_beam=False, eos=None, want_lengths=False,
-               enc_lengths=None):
+               enc_lengths=None, lexicon=None):
         """infer's beam search with the books kept on the device -> (scores (B, batch) float32, labels (B, batch, U) int64)
         [, beam (B, batch, U, |Sy|) one-hot float32 when want_beam], U = 200 or max(y_lengths): the hypotheses, bit-equal
         scores and tie rule of infer (tests/test_hip_beam.py).  Per step: ops.decoder_step (its embedding GEMM left out:
@@ -898,7 +960,11 @@ class Seq2SeqDecoder(torch.nn.Module):
 
         enc_lengths: as infer's, bit-equal to it.  A search with lengths has a plan of its own (the chunk's attention is
         ops.attention_len_fwd on the plan's static (W * batch) int32 buffer, which one copy per call fills); the chunk stays
-        one linear chain."""
+        one linear chain.
+
+        lexicon: as infer's (needs eos; its longest entry must fit into U), kept by slu_beam_select_lex — bit-equal to
+        infer(lexicon=...) in scores, labels and lengths.  The lexicon's tables are part of the plan's key; the trie and
+        the node buffer are static buffers of the plan (node behind the counters: the one fill re-arms it too)."""
         n_host = None
         if enc_lengths is not None:
             n_host = _host_lengths(enc_lengths, encoder_outputs.shape[0], encoder_outputs.shape[1], "encoder frames")
@@ -910,6 +976,8 @@ class Seq2SeqDecoder(torch.nn.Module):
         if eos is not None and not 0 <= eos < V:
             raise ValueError("eos = %r outside [0, %d)" % (eos, V))
         U = 200 if y_lengths is None else max(y_lengths)
+        if lexicon is not None:
+            _check_lexicon(lexicon, eos, V, U)
         names, tensors = self._params()
         P = {n: t.detach() for n, t in zip(names, tensors)}
         P["inv_scale"] = 1.0 / float(self.attention.scale_factor)
@@ -919,7 +987,7 @@ class Seq2SeqDecoder(torch.nn.Module):
             enc = encoder_outputs.detach().float().transpose(0, 1).contiguous()          # (T, bsz, C)
             T = enc.shape[0]
             enc2 = enc.view(T * bsz, -1)
-            p = self._search_plan(P, dev, bsz, T, W, U, V, eos, n_host is not None)
+            p = self._search_plan(P, dev, bsz, T, W, U, V, eos, n_host is not None, lexicon)
             R = W * bsz
             if n_host is not None:
                 p["n_rows"].copy_(torch.tensor(n_host * W, dtype=torch.int32), non_blocking=True)
@@ -928,7 +996,7 @@ class Seq2SeqDecoder(torch.nn.Module):
             p["values"].view(T, W, bsz, Vd).copy_(_ops.gemm(enc2, P["value.weight"].t(), P["value.bias"]).view(T, 1, bsz, Vd).expand(T, W, bsz, Vd))
             _ops.broadcast_rows(P["initial_state"].contiguous().view(-1), p["state"].view(R, -1))
             _ops.broadcast_rows(P["embed.bias"], p["inp0"][:, :E])                        # embed(0) = bias
-            p["ctl"].zero_()                                            # step counters, scores, lengths, n_done
+            p["ctl"].zero_()                                            # step counters, scores, lengths, n_done[, node]
             labels = torch.empty(W, bsz, U, dtype=torch.int64, device=dev)
             beam = torch.empty(W, bsz, U, V, dtype=torch.float32, device=dev) if want_beam else None
             chunks, read = -(-U // self.SEARCH_CHUNK), None
@@ -1745,6 +1813,7 @@ class Model(torch.nn.Module):
             _ops.augment_flags()                  # an unknown component name fails here, not at the first step
             _ops.tempo_enabled()                  # likewise a bad SLU_AUGMENT_TEMPO
         self.seq2seq = config.seq2seq
+        self.lexicon = None                       # set_lexicon: not a parameter, not a buffer, not in state_dict
         out_dim = config.word_rnn_num_hidden[-1] * (2 if config.word_rnn_bidirectional else 1)
         if self.seq2seq:
             # character-level decoder instead of the fixed slots (reference models.py:718-725)
@@ -2000,6 +2069,8 @@ class Model(torch.nn.Module):
         models, GRU hidden sizes 16 / 32 / 64 / 128; exact fp32 kernels whatever SLU_FROZEN_MATH says).  A seq2seq model
         (SLU_MASK_SEQ2SEQ=1): the beam search on the lengths — utterance b's hypotheses and scores are those of
         x[b:b+1, :lengths[b]] searched alone."""
+        if self.seq2seq:
+            self._beam_eos()             # a bad knob or a missing lexicon is an error before any launch
         h, n_host, n_dev = self._encode(x, lengths)
         h = h.contiguous()
         if self.seq2seq:
@@ -2012,9 +2083,26 @@ class Model(torch.nn.Module):
             _, logits, pred, _ = _ops.cls_maxpool_len_fwd(h, cls.weight.detach(), cls.bias.detach(), n_dev, None, slots)
         return logits, pred
 
+    def set_lexicon(self, strings):
+        """Stores the closed set of strings the seq2seq search may return under SLU_BEAM_LEXICON=1: an iterable of
+        strings over Sy_intent (data.intent_lexicon(train_dataset)), a slu_hip.lexicon.Lexicon, or None to drop it.  Not
+        part of state_dict: checkpoints are unchanged."""
+        if not self.seq2seq:
+            raise ValueError("set_lexicon: the lexicon constrains the seq2seq decoder's beam search")
+        if strings is None or isinstance(strings, _lexicon.Lexicon):
+            self.lexicon = strings
+        else:
+            self.lexicon = _lexicon.Lexicon.from_strings(strings, self.Sy_intent)
+
     def _beam_eos(self):
-        """The search's eos argument under SLU_BEAM_EOS (nothing when the knob is off: the calls are today's)."""
-        return {"eos": self.Sy_intent.index("<eos>")} if beam_eos_enabled() else {}
+        """The search's eos argument under SLU_BEAM_EOS and its lexicon argument under SLU_BEAM_LEXICON (nothing when the
+        knobs are off: the calls are today's).  Host checks only: a bad knob or a missing lexicon never reaches a launch."""
+        kw = {"eos": self.Sy_intent.index("<eos>")} if beam_eos_enabled() else {}
+        if beam_lexicon_enabled():
+            if self.lexicon is None:
+                raise ValueError("SLU_BEAM_LEXICON=1 without a lexicon: call Model.set_lexicon(strings) first")
+            kw["lexicon"] = self.lexicon
+        return kw
 
     def _search(self, h, enc_lengths, want_beam):
         """The width-4 beam search over h (time-major encoder states; enc_lengths: their valid frames, or None) with the
@@ -2037,7 +2125,9 @@ class Model(torch.nn.Module):
         (Seq2SeqDecoder.search), best first; score = the hypothesis' log-probability as the search ranks it.  With
         SLU_BEAM_EOS=1 a hypothesis is cut at its length before the cleaning decode_intents applies (so entry 0 is
         decode_intents' string); without, the whole row is cleaned.  Labels, scores and lengths cross to the host in one
-        copy.  lengths (None: the call above): the utterances' sample counts, as decode_intents (SLU_MASK_SEQ2SEQ=1)."""
+        copy.  lengths (None: the call above): the utterances' sample counts, as decode_intents (SLU_MASK_SEQ2SEQ=1).
+        Under SLU_BEAM_LEXICON=1 the dead slots (score -inf: the lexicon had fewer continuations than the beam is wide) are
+        dropped, so an utterance's list may have fewer than n items."""
         if not self.seq2seq:
             raise ValueError("decode_nbest: the n-best list comes from the seq2seq decoder's beam search")
         W = 4
@@ -2057,8 +2147,31 @@ class Model(torch.nn.Module):
         res = []
         for b in range(packed.shape[1]):
             rows = [packed[w, b].tolist() for w in range(n)]
-            res.append([(_labels_to_string(row[:int(row[U])], self.Sy_intent), row[U + 1]) for row in rows])
+            res.append([(_labels_to_string(row[:int(row[U])], self.Sy_intent), row[U + 1]) for row in rows
+                        if "lexicon" not in fin or row[U + 1] != float("-inf")])
         return res
+
+    def exact_match(self, x, y, lengths=None):
+        """seq2seq: -> the number of rows whose best hypothesis equals y (B, U, |Sy|) one-hot, or (B, U) label indices, up
+        to and including y's first <eos> — the accuracy forward() returns 0 for, as the reference does.  The search is the
+        one decode_intents runs (same knobs, same lengths); the comparison is on the device and ONE number crosses to the
+        host."""
+        if not self.seq2seq:
+            raise ValueError("exact_match: the seq2seq decoder's best hypothesis against its target")
+        beam_search_mode()
+        self._beam_eos()
+        eos = self.Sy_intent.index("<eos>")
+        h, n_host, _ = self._encode(x, lengths)
+        _, labels, beam = self._search(h.contiguous(), n_host, want_beam=False)
+        best = labels[0] if labels is not None else beam[0].max(dim=2)[1]             # (B, U of the search)
+        y = y.to(best.device)
+        y = (y.max(dim=2)[1] if y.dim() == 3 else y).long()
+        B, Uy = y.shape
+        if best.shape[1] < Uy:                       # a target longer than the search cannot match: no label equals -1
+            best = torch.cat([best, best.new_full((B, Uy - best.shape[1]), -1)], dim=1)
+        is_eos = y == eos
+        upto = (is_eos.cumsum(dim=1) - is_eos.long()) == 0                            # no <eos> strictly before
+        return int(((best[:, :Uy] == y) | ~upto).all(dim=1).sum())
 
     def decode_intents(self, x, lengths=None):
         """-> list (batch) of lists (slots) of slot-value strings (reference models.py:853-865).  A seq2seq model: list
@@ -2072,6 +2185,7 @@ class Model(torch.nn.Module):
             return [[inverse[s][int(row[s])] for s in range(len(inverse)) if int(row[s]) in inverse[s]]
                     for row in pred]
         beam_search_mode()               # a bad value of the knob is an error before any launch
+        self._beam_eos()
         h, n_host, _ = self._encode(x, lengths)
         _, labels, beam = self._search(h.contiguous(), n_host, want_beam=False)
         if labels is not None:

@@ -2334,14 +2334,16 @@ def broadcast_rows(src, dst2d):
 
 
 def beam_select(logits, scores, state_next, state, step, backptr, labels, y_prev=None, embed=None, eos=None, lengths=None,
-                n_done=None):
+                n_done=None, trie=None, node=None):
     """The beam bookkeeping of one decoding step in one launch (csrc/slu_beam.hip; include/slu_hip.h has the rule).
     logits (W * batch, V); scores (W, batch) fp32, in place; state_next -> state (W * batch, L, Dd), two buffers; step
     (batch) int32 device counters (read, then advanced); backptr / labels (U, W, batch) int32 history planes.
     Next input: y_prev (W * batch, V) gets the one-hot rows, and / or embed = (weight (E, V), bias (E), inp (W * batch,
     >= E)) gets the embedded label directly.
     eos (a label index) turns on finished hypotheses (slu_beam_select_eos): lengths (W, batch) int32 hypothesis lengths, in
-    place; n_done (1) int32 counts the utterances whose search has ended.  eos=None is slu_beam_select."""
+    place; n_done (1) int32 counts the utterances whose search has ended.  eos=None is slu_beam_select.
+    trie = (trie_off (N + 1), trie_lab (N - 1), trie_dst (N - 1)) int32, with eos, constrains the step to a lexicon
+    (slu_beam_select_lex): node (W, batch) int32 the hypotheses' trie nodes, in place."""
     L = _lib.load()
     W, batch = scores.shape
     R, V = logits.shape
@@ -2365,6 +2367,21 @@ def beam_select(logits, scores, state_next, state, step, backptr, labels, y_prev
     if eos is not None:
         assert tuple(lengths.shape) == (W, batch) and lengths.dtype == n_done.dtype == torch.int32
         assert lengths.is_contiguous() and n_done.numel() == 1
+        if trie is not None:
+            off, lab, dst = trie
+            N = off.numel() - 1
+            assert lab.numel() == dst.numel() == N - 1 and tuple(node.shape) == (W, batch) and node.is_contiguous()
+            for t in (off, lab, dst, node):
+                assert t.dtype == torch.int32 and t.is_contiguous() and t.device == logits.device
+            _lib.check(L.slu_beam_select_lex(logits.data_ptr(), scores.data_ptr(), state_next.data_ptr(), state.data_ptr(),
+                                             step.data_ptr(), backptr.data_ptr(), labels.data_ptr(), _ptr(y_prev),
+                                             0 if y_prev is None else y_prev.stride(0), _ptr(ew),
+                                             0 if ew is None else ew.stride(0), _ptr(eb), _ptr(inp),
+                                             0 if inp is None else inp.stride(0), E, W, batch, V, Lc, Dd, U, int(eos),
+                                             lengths.data_ptr(), n_done.data_ptr(), off.data_ptr(), lab.data_ptr(),
+                                             dst.data_ptr(), N, node.data_ptr(), _stream()), "slu_beam_select_lex")
+            return
+        assert node is None, "node goes with trie"
         _lib.check(L.slu_beam_select_eos(logits.data_ptr(), scores.data_ptr(), state_next.data_ptr(), state.data_ptr(),
                                          step.data_ptr(), backptr.data_ptr(), labels.data_ptr(), _ptr(y_prev),
                                          0 if y_prev is None else y_prev.stride(0), _ptr(ew),
@@ -2372,7 +2389,7 @@ def beam_select(logits, scores, state_next, state, step, backptr, labels, y_prev
                                          0 if inp is None else inp.stride(0), E, W, batch, V, Lc, Dd, U, int(eos),
                                          lengths.data_ptr(), n_done.data_ptr(), _stream()), "slu_beam_select_eos")
         return
-    assert lengths is None and n_done is None, "lengths / n_done go with eos"
+    assert lengths is None and n_done is None and trie is None and node is None, "lengths / n_done / trie / node go with eos"
     _lib.check(L.slu_beam_select(logits.data_ptr(), scores.data_ptr(), state_next.data_ptr(), state.data_ptr(),
                                  step.data_ptr(), backptr.data_ptr(), labels.data_ptr(), _ptr(y_prev),
                                  0 if y_prev is None else y_prev.stride(0), _ptr(ew), 0 if ew is None else ew.stride(0),

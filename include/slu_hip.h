@@ -591,7 +591,33 @@ int slu_broadcast_rows_f32(const float* src, float* dst, int64_t ld_dst, int64_t
  *                      backptr / labels with k / eos, writes step[b] = U (later calls do nothing for b) and adds 1 to
  *                      *n_done (int32, zero it with step); an utterance that reaches u + 1 == U unfinished adds 1 too:
  *                      the search is over when *n_done == batch.  slu_beam_backtrack reads the planes unchanged.
- *                      SLU_ERR_INVALID_ARG for eos outside [0, V) and NULL lengths / n_done; else as slu_beam_select. */
+ *                      SLU_ERR_INVALID_ARG for eos outside [0, V) and NULL lengths / n_done; else as slu_beam_select.
+ *   slu_beam_select_lex (ABI 10 as well: one more entry point, nothing existing changed) slu_beam_select_eos that decodes
+ *                      only strings of a closed set — this project's own rule.  A LEXICON is a non-empty set of label
+ *                      sequences over [0, V), each ending in eos with eos nowhere else.  Its TRIE, CSR in int32: trie_off
+ *                      (N + 1) the offsets of each node's edges, trie_lab (N - 1) the edge labels, ascending within a node,
+ *                      trie_dst (N - 1) each edge's child; node 0 is the root, a node is a leaf exactly when its incoming
+ *                      edge is eos; nodes are numbered breadth-first with children in label order, so equal lexicons give
+ *                      equal tables.  node (W, batch) int32 travels with the hypotheses; zero it with step (every slot
+ *                      starts at the root).
+ *                      Unfinished source src at node n = node[src] with d children: for ext < min(W, d) candidate
+ *                      src * W + ext is the ext-th child in the order (logit descending, equal logits: lower label first),
+ *                      scored (logit - lse) + score[src] with lse over the WHOLE row of V logits as above — scores are not
+ *                      renormalised over the allowed set, so a hypothesis' score is the model's log p of the labels it
+ *                      spells and a finished one's is log p(entry | x); for ext >= d the candidate is ABSENT: score -inf,
+ *                      label eos.  Finished sources, the first step (source 0 only) and the selection (the W best of the
+ *                      W * W, descending, stable over the candidate index; -inf candidates tie and come out by index) are
+ *                      slu_beam_select_eos's.  A survivor with score -inf is a DEAD slot: it is written with label eos, is
+ *                      therefore finished from the next step on and keeps -inf by the finished rule.  node[k] = trie_dst
+ *                      of the chosen edge, or node[src] unchanged if the source was finished or the candidate absent.
+ *                      lengths, step, n_done, the fill of the remaining planes and the termination (all W survivors carry
+ *                      eos) are slu_beam_select_eos's.  Logits are assumed finite.  Consequences: every survivor with a
+ *                      finite score spells a prefix of an entry, and an entry once finished; with M <= W entries nothing
+ *                      is pruned and the M finite survivors are the M entries ranked by log p(entry | x); an utterance is
+ *                      done after at most (longest entry) steps.  The kernel clamps node and trie_dst into [0, N), edge
+ *                      offsets into [0, N - 1] and edge labels into [0, V).
+ *                      SLU_ERR_INVALID_ARG for NULL trie_off / trie_lab / trie_dst / node and N < 2; else as
+ *                      slu_beam_select_eos. */
 int slu_beam_select(const float* logits, float* scores, const float* state_next, float* state, int32_t* step,
                     int32_t* backptr, int32_t* labels, float* y_prev, int64_t ld_y, const float* embed_w, int64_t ld_ew,
                     const float* embed_b, float* inp, int64_t ld_inp, int64_t E, int64_t W, int64_t batch, int64_t V,
@@ -600,6 +626,12 @@ int slu_beam_select_eos(const float* logits, float* scores, const float* state_n
                         int32_t* backptr, int32_t* labels, float* y_prev, int64_t ld_y, const float* embed_w, int64_t ld_ew,
                         const float* embed_b, float* inp, int64_t ld_inp, int64_t E, int64_t W, int64_t batch, int64_t V,
                         int64_t L, int64_t Dd, int64_t U, int64_t eos, int32_t* lengths, int32_t* n_done, void* stream);
+int slu_beam_select_lex(const float* logits, float* scores, const float* state_next, float* state, int32_t* step,
+                        int32_t* backptr, int32_t* labels, float* y_prev, int64_t ld_y, const float* embed_w, int64_t ld_ew,
+                        const float* embed_b, float* inp, int64_t ld_inp, int64_t E, int64_t W, int64_t batch, int64_t V,
+                        int64_t L, int64_t Dd, int64_t U, int64_t eos, int32_t* lengths, int32_t* n_done,
+                        const int32_t* trie_off, const int32_t* trie_lab, const int32_t* trie_dst, int64_t N, int32_t* node,
+                        void* stream);
 int slu_beam_backtrack(const int32_t* backptr, const int32_t* labels, int64_t* out, float* one_hot, int64_t W,
                        int64_t batch, int64_t U, int64_t V, void* stream);
 
