@@ -225,6 +225,18 @@ def beam_lexicon_enabled():
     return on
 
 
+def lexicon_exact_enabled():
+    """SLU_LEXICON_EXACT: "0" (default) — every call is what it was; "1" (needs SLU_BEAM_LEXICON=1 and a stored lexicon) —
+    Model.predict_intents / decode_intents / decode_nbest / exact_match score EVERY entry of the lexicon instead of
+    searching it with a beam (Seq2SeqDecoder.score_lexicon; include/slu_hip.h, slu_trie_expand): the best hypothesis is the
+    entry with the highest log p(entry | x), guaranteed, and decode_nbest is no longer capped at the beam width."""
+    on = _knobs.flag("SLU_LEXICON_EXACT")
+    if on and not beam_lexicon_enabled():
+        raise ValueError("SLU_LEXICON_EXACT=1 needs SLU_BEAM_LEXICON=1 (and SLU_BEAM_EOS=1): the sweep scores the entries of "
+                         "the lexicon the constrained search decodes")
+    return on
+
+
 def mask_train_cnn_enabled():
     """SLU_MASK_TRAIN_CNN: "0" (default) — Model.forward(lengths=...) refuses a trainable CNN block; "1" — such a block
     runs length-aware inside autograd (ops.SincBlockLenFn / ConvBlockLenFn), so masked training goes on when the unfreezing
@@ -1019,6 +1031,129 @@ class Seq2SeqDecoder(torch.nn.Module):
             scores = p["scores"].clone()
             out = (scores, labels) + ((beam,) if want_beam else ())
         return out + (p["lengths"].clone(),) if want_lengths else out
+
+    LEXICON_PLANS = 2           # sweep plans kept (shape, parameter storage, lexicon), least recently used out: the
+                                # retained device memory is at most this many plans (DESIGN.md section 7 has the bytes)
+
+    def _lexicon_plan(self, P, dev, bsz, T, V, eos, with_lengths, lexicon):
+        """Static buffers (+ the captured sweep) of one score_lexicon shape, attention kind and lexicon, sized from
+        lexicon.width: the widest level's rows are width * bsz (DESIGN.md section 7 has the byte count)."""
+        from slu_hip import pipeline as _pipeline
+        use_graph = _pipeline.graphs_enabled()
+        key = (bsz, T, V, eos, bool(with_lengths), str(dev), use_graph, lexicon.key(),
+               tuple((n, t.data_ptr(), tuple(t.shape)) for n, t in P.items() if torch.is_tensor(t)))
+        plans = self.__dict__.setdefault("_lexicon_plans", {})
+        plan = plans.pop(key, None)
+        if plan is None:
+            plan = self._build_lexicon_plan(P, dev, bsz, T, V, use_graph, eos, with_lengths, lexicon)
+            while len(plans) >= self.LEXICON_PLANS:
+                plans.pop(next(iter(plans)))
+        plans[key] = plan                                   # most recently used last
+        return plan
+
+    def _build_lexicon_plan(self, P, dev, bsz, T, V, use_graph, eos, with_lengths, lexicon):
+        from slu_hip import pipeline as _pipeline
+        Kd, Vd = P["key.weight"].shape[0], P["value.weight"].shape[0]
+        Lc, Dd = P["initial_state"].shape
+        E = P["embed.weight"].shape[0]
+        _, inner, _, width = lexicon.levels()
+        R, M = width * bsz, len(lexicon)
+        f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        # state: the level's rows; state_next: the step's output, which slu_trie_expand scatters back into state for the
+        # next level (the step has read state by then).  scores: the levels alternate between the two halves.
+        b = {"keys": f(T, R, Kd), "values": f(T, R, Vd), "state": f(R, Lc, Dd), "state_next": f(R, Lc, Dd),
+             "q": f(R, Kd), "inp0": f(R, E + Vd), "att_w": f(R, T), "logits": f(R, V), "gi": f(R, 3 * Dd),
+             "gh": f(Lc, R, 3 * Dd), "drop": [f(R, Dd) for _ in range(Lc - 1)], "scores": f(2, R),
+             "entry_logp": f(bsz, M), "log_z": f(bsz), "best": torch.empty(bsz, dtype=torch.int32, device=dev),
+             "graph": None, "width": width}
+        b["n_rows"] = torch.full((R,), T, dtype=torch.int32, device=dev) if with_lengths else None
+        trie = lexicon.tables(dev)
+        slot, inner_dev = lexicon.level_tables(dev)
+        levels = [(d, len(inner[d]), len(inner[d + 1])) for d in range(lexicon.max_len) if inner[d]]
+        b["row_steps"] = sum(n for _, n, _ in levels) * bsz
+
+        def sweep():
+            for d, n_in, n_out in levels:
+                r = n_in * bsz
+                # y_prev=None: slu_trie_expand has written the embedding half of inp0 (the bias before the first level)
+                _ops.decoder_step(P, b["keys"][:, :r], b["values"][:, :r], b["state"][:r], b["state_next"][:r], None,
+                                  b["q"][:r], b["inp0"][:r], b["att_w"][:r], b["gi"][:r], b["gh"][:, :r], None,
+                                  [t[:r] for t in b["drop"]], b["logits"][:r], 0, (0.0, None, 0, 0, None, r * Dd),
+                                  None if b["n_rows"] is None else b["n_rows"][:r])
+                nxt = {}
+                if n_out:
+                    ro = n_out * bsz
+                    nxt = dict(score_out=b["scores"][(d + 1) % 2, :ro], state_out=b["state"][:ro],
+                               embed=(P["embed.weight"], P["embed.bias"], b["inp0"][:ro]))
+                _ops.trie_expand(b["logits"][:r], b["state_next"][:r], b["scores"][d % 2, :r], inner_dev[d], trie, slot, eos,
+                                 b["entry_logp"], **nxt)
+            _ops.trie_finish(b["entry_logp"], b["best"], b["log_z"])
+        b["sweep"] = sweep
+        if use_graph:
+            # warm-up on the capture stream (lazy initialisation happens outside the capture), on zeroed operands
+            for t in (b["keys"], b["values"], b["state"], b["inp0"], b["scores"]):
+                t.zero_()
+            side = torch.cuda.Stream(dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                sweep()
+            side.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with _pipeline.capture(graph, side):            # one linear chain: no forked stream inside
+                sweep()
+            torch.cuda.current_stream(dev).wait_stream(side)
+            b["graph"] = graph
+        return b
+
+    def score_lexicon(self, encoder_outputs, Sy, lexicon, eos, enc_lengths=None):
+        """Exact decoding over a closed set (include/slu_hip.h, slu_trie_expand): log p(entry | x) of
+        EVERY entry of `lexicon`, not the survivors of a beam -> (entry_logp (batch, M) float32, best (batch) int32,
+        log_z (batch) float32); columns in lexicon.entries order, best = the argmax (an exact tie: the lowest index),
+        log_z = logsumexp over the M entries, so entry_logp - log_z is log p(entry | x, entry in lexicon).
+        The lexicon's trie is numbered breadth-first: all inner nodes of depth d are ONE batch through ops.decoder_step
+        (rows i * batch + b, search's layout with W = n_inner[d]), followed by ONE slu_trie_expand that scores every edge,
+        hands the inner children their state, score and embedded label for the next level and the leaves their entry's
+        score.  lexicon.max_len levels, then ONE slu_trie_finish; no torch op and no host read in between.  A value is what
+        search(..., lexicon=) gives that hypothesis: all-zero first input, log-softmax over all labels, nothing renormalised
+        per step.  With SLU_GRAPHS=1 the whole sweep is one captured linear chain per plan (shapes, parameter storage,
+        lexicon.key()), reading the parameters in place; bit-equal to the eager sweep.
+        enc_lengths: as search's — the attention is ops.attention_len_fwd on the plan's per-row int32 buffer, which one
+        copy per call fills."""
+        n_host = None
+        if enc_lengths is not None:
+            n_host = _host_lengths(enc_lengths, encoder_outputs.shape[0], encoder_outputs.shape[1], "encoder frames")
+        _require_device(encoder_outputs)
+        dev = encoder_outputs.device
+        bsz, V = encoder_outputs.shape[0], len(Sy)
+        if eos is None or not 0 <= eos < V:
+            raise ValueError("eos = %r outside [0, %d)" % (eos, V))
+        _check_lexicon(lexicon, eos, V, lexicon.max_len)
+        names, tensors = self._params()
+        P = {n: t.detach() for n, t in zip(names, tensors)}
+        P["inv_scale"] = 1.0 / float(self.attention.scale_factor)
+        Kd, Vd = P["key.weight"].shape[0], P["value.weight"].shape[0]
+        E = P["embed.weight"].shape[0]
+        with torch.no_grad():
+            enc = encoder_outputs.detach().float().transpose(0, 1).contiguous()          # (T, bsz, C)
+            T = enc.shape[0]
+            enc2 = enc.view(T * bsz, -1)
+            p = self._lexicon_plan(P, dev, bsz, T, V, eos, n_host is not None, lexicon)
+            W = p["width"]
+            if n_host is not None:
+                p["n_rows"].copy_(torch.tensor(n_host * W, dtype=torch.int32), non_blocking=True)
+            # set-up as in search: keys / values once, replicated per slot; the root's rows get the initial state, the
+            # all-zero first input and score 0
+            p["keys"].view(T, W, bsz, Kd).copy_(_ops.gemm(enc2, P["key.weight"].t(), P["key.bias"]).view(T, 1, bsz, Kd).expand(T, W, bsz, Kd))
+            p["values"].view(T, W, bsz, Vd).copy_(_ops.gemm(enc2, P["value.weight"].t(), P["value.bias"]).view(T, 1, bsz, Vd).expand(T, W, bsz, Vd))
+            _ops.broadcast_rows(P["initial_state"].contiguous().view(-1), p["state"][:bsz].view(bsz, -1))
+            _ops.broadcast_rows(P["embed.bias"], p["inp0"][:bsz, :E])                     # embed(0) = bias
+            p["scores"][0, :bsz].zero_()
+            if p["graph"] is not None:
+                p["graph"].replay()
+            else:
+                p["sweep"]()
+            self.last_lexicon_row_steps = p["row_steps"]
+            return p["entry_logp"].clone(), p["best"].clone(), p["log_z"].clone()
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2102,14 +2237,24 @@ class Model(torch.nn.Module):
             if self.lexicon is None:
                 raise ValueError("SLU_BEAM_LEXICON=1 without a lexicon: call Model.set_lexicon(strings) first")
             kw["lexicon"] = self.lexicon
+        lexicon_exact_enabled()                          # SLU_LEXICON_EXACT=1 without SLU_BEAM_LEXICON=1: refused here
         return kw
 
     def _search(self, h, enc_lengths, want_beam):
         """The width-4 beam search over h (time-major encoder states; enc_lengths: their valid frames, or None) with the
         books where SLU_BEAM_SEARCH keeps them -> (scores, labels (4, B, U), beam one-hot): "host" (Seq2SeqDecoder.infer)
-        gives no labels, "device" (Seq2SeqDecoder.search) the beam only when want_beam."""
+        gives no labels, "device" (Seq2SeqDecoder.search) the beam only when want_beam.  Under SLU_LEXICON_EXACT=1 neither
+        runs: the 4 best entries of the exact sweep (_exact_top) in the same shapes, row 0 the sweep's best; a lexicon of
+        M < 4 entries leaves 4 - M dead slots, score -inf and <eos> throughout, as the search does."""
         mode, enc = beam_search_mode(), h.transpose(0, 1)
         kw = dict(self._beam_eos(), B=4)                 # the dense calls' arguments are what they always were
+        if lexicon_exact_enabled():                      # no search: every entry scored, the 4 best read off
+            scores, labels = self._exact_top(h, enc_lengths, 4, pad=True)
+            beam = None
+            if want_beam:
+                beam = torch.zeros(labels.shape + (len(self.Sy_intent),), dtype=torch.float32, device=labels.device)
+                beam.scatter_(3, labels.unsqueeze(3), 1.0)
+            return scores, labels, beam
         if enc_lengths is not None:
             kw["enc_lengths"] = enc_lengths
         if mode == "host":
@@ -2120,6 +2265,56 @@ class Model(torch.nn.Module):
         out = self.decoder.search(enc, self.Sy_intent, **kw)
         return out[0], out[1], out[2] if want_beam else None
 
+    def lexicon_strings(self):
+        """The stored lexicon's strings in the order of its entries — the columns of lexicon_scores / lexicon_posteriors —
+        cleaned as decode_intents cleans a hypothesis."""
+        if self.lexicon is None:
+            raise ValueError("lexicon_strings: no lexicon, call Model.set_lexicon(strings) first")
+        return [_labels_to_string(e, self.Sy_intent) for e in self.lexicon.entries]
+
+    def lexicon_scores(self, x, lengths=None):
+        """seq2seq, with a stored lexicon: exact decoding over the closed set -> (entry_logp (batch, M) float32: log p(entry |
+        x) of every entry, columns in lexicon_strings() order; best (batch) int32: the argmax; log_z (batch) float32: the
+        logsumexp over the entries), on the device (Seq2SeqDecoder.score_lexicon).  entry_logp - log_z is the
+        log-posterior over the lexicon.  lengths: as decode_nbest (SLU_MASK_SEQ2SEQ=1); the knobs are checked as there."""
+        if not self.seq2seq:
+            raise ValueError("lexicon_scores: the entries are scored by the seq2seq decoder")
+        self._beam_eos()
+        if self.lexicon is None:
+            raise ValueError("lexicon_scores: no lexicon, call Model.set_lexicon(strings) first")
+        h, n_host, _ = self._encode(x, lengths)
+        return self._exact_sweep(h, n_host)
+
+    def lexicon_posteriors(self, x, lengths=None):
+        """-> (batch, M) float32 on the device: p(entry | x, entry in lexicon) = exp(entry_logp - log_z) of lexicon_scores,
+        the number to threshold when an utterance may be none of the entries' business.  Evaluated as the softmax of
+        entry_logp, the same quantity with the maximum subtracted first: log_z of an utterance whose entries score around
+        -30 carries half an ulp of 2e-6, which exp(entry_logp - log_z) would turn into rows that sum to 1 +- 2e-6.  So a
+        caller who forms exp(entry_logp - log_z) from lexicon_scores gets these rows to within that, not bit for bit."""
+        return torch.softmax(self.lexicon_scores(x, lengths)[0], dim=1)
+
+    def _exact_sweep(self, h, n_host):
+        kw = {} if n_host is None else {"enc_lengths": n_host}
+        return self.decoder.score_lexicon(h.contiguous().transpose(0, 1), self.Sy_intent, self.lexicon,
+                                          self.Sy_intent.index("<eos>"), **kw)
+
+    def _exact_top(self, h, n_host, n, pad=False):
+        """The min(n, M) best entries of the sweep, best first, in the search's shapes -> (scores (n', batch) float32,
+        labels (n', batch, 200) int64, an entry's labels and then <eos> to the end).  A stable descending sort: equal
+        scores come out by entry index, so row 0 is the sweep's `best`.  pad: n' = n whatever M is — the rows beyond M are
+        the search's dead slots, score -inf and <eos> throughout."""
+        lx, eos, U = self.lexicon, self.Sy_intent.index("<eos>"), 200
+        if lx.max_len > U:
+            raise ValueError("lexicon: its longest entry has %d labels, the search has U = %d steps" % (lx.max_len, U))
+        entry_logp, _, _ = self._exact_sweep(h, n_host)
+        top_s, top_i = entry_logp.sort(dim=1, descending=True, stable=True)
+        k = min(n, len(lx))
+        scores, labels = top_s[:, :k].t().contiguous(), lx.entry_table(entry_logp.device, U)[top_i[:, :k].t()]
+        if pad and k < n:
+            scores = torch.cat([scores, scores.new_full((n - k, scores.shape[1]), float("-inf"))])
+            labels = torch.cat([labels, labels.new_full((n - k,) + tuple(labels.shape[1:]), eos)])
+        return scores, labels
+
     def decode_nbest(self, x, n=4, lengths=None):
         """seq2seq: -> list (batch) of lists of (string, score): the n <= 4 best hypotheses of the width-4 device search
         (Seq2SeqDecoder.search), best first; score = the hypothesis' log-probability as the search ranks it.  With
@@ -2127,10 +2322,22 @@ class Model(torch.nn.Module):
         decode_intents' string); without, the whole row is cleaned.  Labels, scores and lengths cross to the host in one
         copy.  lengths (None: the call above): the utterances' sample counts, as decode_intents (SLU_MASK_SEQ2SEQ=1).
         Under SLU_BEAM_LEXICON=1 the dead slots (score -inf: the lexicon had fewer continuations than the beam is wide) are
-        dropped, so an utterance's list may have fewer than n items."""
+        dropped, so an utterance's list may have fewer than n items.
+        Under SLU_LEXICON_EXACT=1 there is no beam: the min(n, M) best of the lexicon's M entries, each with its exact
+        log p(entry | x) (lexicon_scores), any n >= 1."""
         if not self.seq2seq:
             raise ValueError("decode_nbest: the n-best list comes from the seq2seq decoder's beam search")
         W = 4
+        if lexicon_exact_enabled():
+            # SLU_LEXICON_EXACT=1: the min(n, M) best entries of the sweep with their log p(entry | x); no beam, no cap
+            if n < 1:
+                raise ValueError("decode_nbest: n = %r outside [1, the lexicon's size]" % (n,))
+            self._beam_eos()
+            h, n_host, _ = self._encode(x, lengths)
+            scores, labels = self._exact_top(h, n_host, n)
+            scores, labels = scores.t().tolist(), labels.transpose(0, 1).tolist()
+            return [[(_labels_to_string(row[:row.index(self.lexicon.eos) + 1], self.Sy_intent), s)
+                     for row, s in zip(labels[b], scores[b])] for b in range(len(scores))]
         if not 1 <= n <= W:
             raise ValueError("decode_nbest: n = %r outside [1, %d]" % (n, W))
         fin = self._beam_eos()

@@ -54,6 +54,7 @@ class Lexicon:
         self.trie_off, self.trie_lab, self.trie_dst = tuple(off), tuple(lab), tuple(dst)
         self.N = n_nodes
         self._device = {}
+        self._levels = None
 
     @classmethod
     def from_strings(cls, strings, Sy):
@@ -84,4 +85,67 @@ class Lexicon:
         if k not in self._device:
             self._device[k] = tuple(torch.tensor(t, dtype=torch.int32).to(device)
                                     for t in (self.trie_off, self.trie_lab, self.trie_dst))
+        return self._device[k]
+
+    def levels(self):
+        """What the exact sweep over the lexicon needs (include/slu_hip.h, slu_trie_expand), as tuples:
+
+            level_off (max_len + 2)  the nodes of depth d are level_off[d] .. level_off[d + 1] - 1 (breadth-first numbers:
+                                     a depth is a contiguous range; depth 0 is the root, depth max_len the last leaves)
+            inner (max_len + 1)      per depth, the ascending tuple of its inner nodes (a node is a leaf exactly when its
+                                     incoming edge is eos); len(inner[d]) is n_inner[d]
+            slot (N)                 an inner node: its index in its depth's inner tuple; a leaf: the index in `entries` of
+                                     the entry it ends (entries are sorted; leaves and entries are in bijection)
+            width                    max(n_inner)
+
+        -> (level_off, inner, slot, width).  Equal lexicons give equal tables."""
+        if self._levels is None:
+            depth, leaf, path = [0] * self.N, [False] * self.N, [()] * self.N
+            for n in range(self.N):                      # a child's number is larger than its parent's
+                for e in range(self.trie_off[n], self.trie_off[n + 1]):
+                    c = self.trie_dst[e]
+                    depth[c], leaf[c], path[c] = depth[n] + 1, self.trie_lab[e] == self.eos, path[n] + (self.trie_lab[e],)
+            level_off = [0] * (self.max_len + 2)
+            for d in depth:
+                level_off[d + 1] += 1
+            for d in range(self.max_len + 1):
+                level_off[d + 1] += level_off[d]
+            inner = tuple(tuple(n for n in range(level_off[d], level_off[d + 1]) if not leaf[n])
+                          for d in range(self.max_len + 1))
+            index = {e: i for i, e in enumerate(self.entries)}
+            slot = [0] * self.N
+            for nodes in inner:
+                for i, n in enumerate(nodes):
+                    slot[n] = i
+            for n in range(self.N):
+                if leaf[n]:
+                    slot[n] = index[path[n]]
+            self._levels = (tuple(level_off), inner, tuple(slot), max(len(nodes) for nodes in inner))
+        return self._levels
+
+    @property
+    def width(self):
+        """The widest level of the sweep: the most inner nodes any depth has."""
+        return self.levels()[3]
+
+    def level_tables(self, device):
+        """(slot (N) int32, [inner nodes of depth d (n_inner[d]) int32 or None, d = 0 .. max_len]) on `device`, copied once
+        per device."""
+        import torch
+        k = "levels:" + str(device)
+        if k not in self._device:
+            _, inner, slot, _ = self.levels()
+            self._device[k] = (torch.tensor(slot, dtype=torch.int32).to(device),
+                               [torch.tensor(nodes, dtype=torch.int32).to(device) if nodes else None for nodes in inner])
+        return self._device[k]
+
+    def entry_table(self, device, U):
+        """(M, U) int64 on `device`: row m is entry m's labels and then eos to the end (U >= max_len), copied once per device
+        and U."""
+        import torch
+        k = "entries:%d:%s" % (U, device)
+        if k not in self._device:
+            assert U >= self.max_len
+            self._device[k] = torch.tensor([list(e) + [self.eos] * (U - len(e)) for e in self.entries],
+                                           dtype=torch.int64).to(device)
         return self._device[k]

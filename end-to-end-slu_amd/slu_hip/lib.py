@@ -53,6 +53,9 @@ SIGNATURES = {
     "slu_beam_select_lex": (c_int, [vp, vp, vp, vp, vp, vp, vp, vp, c_i64, vp, c_i64, vp, vp, c_i64, c_i64, c_i64, c_i64,
                                     c_i64, c_i64, c_i64, c_i64, c_i64, vp, vp, vp, vp, vp, c_i64, vp, vp]),
     "slu_beam_backtrack": (c_int, [vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, vp]),
+    "slu_trie_expand": (c_int, [vp, vp, vp, vp, vp, vp, vp, vp, c_i64, vp, c_i64, vp, vp, vp, vp, c_i64, vp, c_i64, c_i64,
+                                c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, vp]),
+    "slu_trie_finish": (c_int, [vp, vp, vp, vp, c_i64, c_i64, vp]),
     "slu_sinc_filters_fwd": (c_int, [vp, vp, vp, c_i64, c_i64, c_f64, vp]),
     "slu_sinc_filters_bwd": (c_int, [vp, vp, vp, vp, vp, c_i64, c_i64, c_f64, vp]),
     "slu_wconv_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),

@@ -2414,6 +2414,64 @@ def beam_backtrack(backptr, labels, out, one_hot=None):
                                     _stream()), "slu_beam_backtrack")
 
 
+def trie_expand(logits, state_next, score_in, inner, trie, slot, eos, entry_logp, score_out=None, state_out=None,
+                embed=None):
+    """The bookkeeping of one level of the exact sweep over a lexicon in one launch (csrc/slu_trie.hip; include/slu_hip.h has
+    the rule).  logits (n_inner * batch, V), state_next (n_inner * batch, L, Dd), score_in (n_inner * batch) fp32: the rows
+    i * batch + b of this level's inner nodes `inner` (n_inner) int32; trie = (trie_off (N + 1), trie_lab (N - 1), trie_dst
+    (N - 1)) and slot (N) int32; entry_logp (batch, M) fp32 gets the scores of the entries that end behind this level.
+    The next level (None when every child is a leaf): score_out (n_out * batch), state_out (n_out * batch, L, Dd) and embed
+    = (weight (E, V), bias (E), inp (n_out * batch, >= E)) get the inner children's scores, states and embedded labels."""
+    L = _lib.load()
+    R, V = logits.shape
+    n_inner = inner.numel()
+    batch, M = entry_logp.shape
+    Lc, Dd = state_next.shape[1], state_next.shape[2]
+    off, lab, dst = trie
+    N = off.numel() - 1
+    assert n_inner > 0 and R == n_inner * batch and tuple(state_next.shape) == (R, Lc, Dd) and score_in.numel() == R
+    assert lab.numel() == dst.numel() == N - 1 and slot.numel() == N
+    for t in (off, lab, dst, slot, inner):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.device == logits.device
+    for t in (logits, state_next, score_in, entry_logp):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    ew = eb = inp = None
+    E = n_out = 0
+    if score_out is not None:
+        assert state_out is not None and embed is not None, "score_out, state_out and embed go together"
+        ew, eb, inp = embed
+        E = ew.shape[0]
+        assert score_out.numel() % batch == 0
+        n_out = score_out.numel() // batch
+        assert tuple(state_out.shape) == (n_out * batch, Lc, Dd)
+        for t in (score_out, state_out):
+            assert t.dtype == torch.float32 and t.is_contiguous()
+        assert ew.shape[1] == V and ew.stride(1) == 1 and eb.is_contiguous() and eb.numel() == E
+        assert inp.shape[0] == n_out * batch and inp.shape[1] >= E and inp.stride(1) == 1
+    else:
+        assert state_out is None and embed is None, "score_out, state_out and embed go together"
+    _lib.check(L.slu_trie_expand(logits.data_ptr(), state_next.data_ptr(), score_in.data_ptr(), inner.data_ptr(),
+                                 off.data_ptr(), lab.data_ptr(), dst.data_ptr(), slot.data_ptr(), N, _ptr(ew),
+                                 0 if ew is None else ew.stride(0), _ptr(eb), _ptr(score_out), _ptr(state_out), _ptr(inp),
+                                 0 if inp is None else inp.stride(0), entry_logp.data_ptr(), n_inner, n_out, batch, V, Lc, Dd,
+                                 E, M, int(eos), _stream()), "slu_trie_expand")
+
+
+def trie_finish(entry_logp, best, log_z, log_post=None):
+    """entry_logp (batch, M) fp32 -> best (batch) int32: the argmax, an exact tie to the lowest index; log_z (batch) fp32:
+    the logsumexp over the M values (include/slu_hip.h has the reduction tree); log_post (batch, M), when given: entry_logp -
+    log_z."""
+    L = _lib.load()
+    batch, M = entry_logp.shape
+    assert entry_logp.dtype == log_z.dtype == torch.float32 and best.dtype == torch.int32
+    assert entry_logp.is_contiguous() and best.is_contiguous() and log_z.is_contiguous()
+    assert best.numel() == log_z.numel() == batch
+    if log_post is not None:
+        assert log_post.dtype == torch.float32 and log_post.is_contiguous() and tuple(log_post.shape) == (batch, M)
+    _lib.check(L.slu_trie_finish(entry_logp.data_ptr(), best.data_ptr(), log_z.data_ptr(), _ptr(log_post), batch, M,
+                                 _stream()), "slu_trie_finish")
+
+
 def decoder_step(P, keys, values, state_prev, state_next, y_prev, q, inp0, att_w, gi, gh, save, drop, logits, step,
                  drop_cfg, n_rows=None):
     """One decoding step (models.py:528-536) on the HIP kernels, shared by the teacher-forced forward and the beam

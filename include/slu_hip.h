@@ -635,6 +635,48 @@ int slu_beam_select_lex(const float* logits, float* scores, const float* state_n
 int slu_beam_backtrack(const int32_t* backptr, const int32_t* labels, int64_t* out, float* one_hot, int64_t W,
                        int64_t batch, int64_t U, int64_t V, void* stream);
 
+/* -------- exact decoding over a lexicon — added under ABI 10 (two new entry points; nothing existing changed, so the version
+ * number stays).  This project's own rule.  With a closed set no search is needed: the lexicon's trie (slu_beam_select_lex
+ * above) is numbered breadth-first, so the nodes of one depth are a contiguous range, and ALL inner nodes of depth d are one
+ * batch through the decoder step.  One sweep over the depths visits every node once and gives every entry its exact
+ * log p(entry | x) — the value slu_beam_select_lex gives a finished hypothesis (all-zero first input, log-softmax over all V
+ * labels, nothing renormalised per step).
+ *   Host tables beside the trie: per depth d the ascending list of its INNER nodes (a node is a leaf exactly when its
+ *   incoming edge is eos), n_inner[d] of them; slot (N): an inner node's index in its depth's list, a leaf's index among the
+ *   M sorted entries (leaves and entries are in bijection).
+ *   slu_trie_expand    one launch per depth behind that depth's decoder step, one workgroup per row r = i * batch + b (i:
+ *                      index into inner, b: utterance — the search's (W, batch) row layout with W = n_inner).  logits
+ *                      (n_inner * batch, V); state_next (n_inner * batch, L, Dd); score_in (n_inner * batch) the rows'
+ *                      running log-probabilities (zeros at depth 0).  lse = logsumexp(logits[r]) by the reduction of
+ *                      slu_beam_select (one shared statement).  For every edge of node inner[i], label v, child c:
+ *                        s = (logits[r, v] - lse) + score_in[r]        (fp32, in this order: the search's)
+ *                        v != eos, k = slot[c]:  score_out[k * batch + b] = s;  state_out[k * batch + b] = state_next[r]
+ *                                                (all L * Dd);  inp_out[k * batch + b, :E] = embed_w[:, v] + embed_b, what
+ *                                                slu_beam_select writes: the next step skips the embedding GEMM
+ *                        v == eos, k = slot[c]:  entry_logp[b, k] = s            (entry_logp (batch, M))
+ *                      Valid tables give every slot of the next depth exactly one writer, and every entry exactly one over
+ *                      the sweep: no atomics, and every score is finite when the logits are.  n_out = the next depth's
+ *                      n_inner: the rows score_out / state_out / inp_out hold, per utterance; n_out == 0 (every child is a
+ *                      leaf): the three may be NULL.  The kernel clamps nodes and trie_dst into [0, N), edge offsets into
+ *                      [0, N - 1] and edge labels into [0, V) as slu_beam_select_lex does, and SKIPS a write whose slot is
+ *                      outside [0, n_out) resp. [0, M).  state_out / score_out must not be state_next / score_in.
+ *                      SLU_ERR_INVALID_ARG for NULL tables, N < 2, eos outside [0, V), non-positive sizes;
+ *                      SLU_ERR_UNSUPPORTED for Dd % 4 != 0 or state buffers not 16-byte aligned.
+ *   slu_trie_finish    one workgroup per utterance over entry_logp (batch, M): best[b] (int32) = the argmax, an exact tie
+ *                      to the lowest entry index; log_z[b] (fp32) = logsumexp of the M values, max-subtracted, in the fixed
+ *                      tree of every row reduction here: thread t of 256 adds expf(x[j] - max) over j = t, t + 256, ...
+ *                      ascending; a wave of 64 adds its partial sums by the xor butterfly 32, 16, 8, 4, 2, 1; the four waves'
+ *                      sums are (w0 + w1) + (w2 + w3); log_z = max + logf(sum).  M == 1 gives log_z == entry_logp bit for
+ *                      bit.  log p(entry | x, entry in lexicon) = entry_logp - log_z; log_post (NULL or (batch, M)) gets
+ *                      that difference. */
+int slu_trie_expand(const float* logits, const float* state_next, const float* score_in, const int32_t* inner,
+                    const int32_t* trie_off, const int32_t* trie_lab, const int32_t* trie_dst, const int32_t* slot, int64_t N,
+                    const float* embed_w, int64_t ld_ew, const float* embed_b, float* score_out, float* state_out,
+                    float* inp_out, int64_t ld_inp, float* entry_logp, int64_t n_inner, int64_t n_out, int64_t batch,
+                    int64_t V, int64_t L, int64_t Dd, int64_t E, int64_t M, int64_t eos, void* stream);
+int slu_trie_finish(const float* entry_logp, int32_t* best, float* log_z, float* log_post, int64_t batch, int64_t M,
+                    void* stream);
+
 /* -------- per-utterance lengths: padding-invariant inference — added under ABI 10 (five new entry points; nothing
  * existing changed, so the version number stays).  The definition is this library's own: the reference's collate functions
  * zero-pad a batch to its longest row and pass no lengths (data.py:244), so its convolutions, ceil_mode windows, reverse
