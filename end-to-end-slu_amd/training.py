@@ -97,7 +97,9 @@ def _graph_forks():
 
 
 def _param_signature(model):
-    return tuple(True if p.requires_grad else p._version for p in model.parameters())
+    """Per parameter: None = trainable, else the frozen tensor's version.  (Not True for trainable: True == 1, so a
+    parameter frozen at version 1 and the same parameter unfrozen gave equal — and equally hashed — signatures.)"""
+    return tuple(None if p.requires_grad else p._version for p in model.parameters())
 
 
 def _lookahead_width(depth, batch_size):
@@ -737,6 +739,7 @@ class Trainer:
                 for _ in self._slots[1:]:
                     ahead.start_next()
                 host_wait = _host_wait()
+                batch_axis = 1 if n_prefix >= len(pm._cnn_stages) else 0
                 while ahead.pending:
                     sb = ahead.pending.popleft()
                     group, feats_cat, done, steps = sb.group, sb.feats, sb.done, sb.steps
@@ -767,7 +770,9 @@ class Trainer:
                         if k == 0:
                             main.wait_event(done)
                             feats_cat.record_stream(main)
-                        feats = feats_cat[:, k * B:(k + 1) * B] if len(group) > 1 else feats_cat
+                        # the batches lie along the batch axis of what the prefix hands over: time-major (T, B, C) from
+                        # the last CNN block on, channels-last (B, L, C) where the prefix ends at an earlier CNN block
+                        feats = feats_cat.narrow(batch_axis, k * B, B) if len(group) > 1 else feats_cat
                         y = batch[1].to(dev, non_blocking=True)
                         if step_graphs:
                             key = (tuple(feats.shape), tuple(y.shape), n_prefix, trainable, sums is not None)

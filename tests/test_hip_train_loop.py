@@ -147,6 +147,69 @@ def test_lookahead_pipeline_equals_sequential_training(tmp_path, monkeypatch):
     assert len(set(results["0"][0])) == len(results["0"][0])         # dropout really varied step to step
 
 
+@pytest.mark.parametrize("steps", [2, 5])
+def test_training_loops_agree_across_the_whole_unfreezing_schedule(tmp_path, monkeypatch, steps):
+    """The sibling of the test above over ALL states of unfreezing_type 2 (eight: from the frozen encoder down to the Sinc
+    block), `steps` optimisation steps per state on 8 utterances of 6000 samples: SLU_LOOKAHEAD 0 against 3 and SLU_GRAPHS 0
+    against 1 give identical losses and, after the last state, identical parameters.  A self-consistency check by design
+    (tests/test_hip_unfreeze_states.py ties the values to the oracle).
+    A step is captured after three eager steps of its key, and the key carries the set of trainable parameters: with 2 steps
+    per state no step is ever captured, but every state counts its eager steps under a key of its own; with 5 steps per state
+    every state captures its own step (steps 1-3 eager, capture at the 4th, replay at the 5th) — one more entry of
+    trainer._step_graphs per state, none of them reused by the next."""
+    sys.path.insert(0, PKG)
+    import data
+    import models
+    import training
+    cfg = O.OracleConfig(cnn_N_filt=[16, 12, 12], cnn_len_filt=[101, 5, 5], cnn_stride=[20, 1, 1],
+                         phone_rnn_num_hidden=[32, 32], word_rnn_num_hidden=[32, 32],
+                         intent_rnn_num_hidden=[32], vocabulary_size=60, num_phonemes=20, pretraining_type=2)
+    cfg.folder = str(tmp_path)
+    cfg.training_lr = 0.003
+    cfg.starting_unfreezing_index = 1
+    cfg.unfreezing_type = 2
+    cfg.Sy_intent = data.synthetic_Sy_intent(cfg.values_per_slot)
+    os.makedirs(tmp_path / "pretraining")
+    os.makedirs(tmp_path / "training")
+    torch.manual_seed(1)
+    torch.save(O.init_pretrained_state_dict(cfg), tmp_path / "pretraining" / "model_state.pth")
+    ds = data.SyntheticSLUDataset(steps, 8, 6000, cfg.values_per_slot, seed=5)
+    n_states = 8
+    results = {}
+    for depth, graphs in (("0", "0"), ("3", "0"), ("0", "1"), ("3", "1")):
+        monkeypatch.setenv("SLU_LOOKAHEAD", depth)
+        monkeypatch.setenv("SLU_GRAPHS", graphs)
+        torch.manual_seed(2)
+        model = models.Model(cfg)
+        models.set_dropout_seed(77)
+        trainer = training.Trainer(model, cfg)
+        losses, captured, keys = [], [], []
+        model.train()
+        for state in range(n_states):
+            assert model.frozen_prefix_len() == 7 - state
+            assert trainer.lookahead_depth(True, False) == ((3, 7 - state) if depth == "3" and state < 7 else (0, 0))
+            for vals, _ in trainer._iterate(ds.loader, True, False):
+                losses.append(vals[0].item())
+            captured.append(len(trainer._step_graphs))
+            keys.append(len(trainer._eager_steps))
+            model.unfreeze_one_layer()
+        torch.cuda.synchronize()
+        assert model.frozen_prefix_len() == 0 and trainer.capture_failures == 0
+        if graphs == "0":
+            assert captured == [0] * n_states
+        else:
+            # a new freeze signature is a new key: its eager steps are counted afresh and its step is captured afresh
+            assert keys == list(range(1, n_states + 1)), keys
+            assert captured == ([0] * n_states if steps < 4 else list(range(1, n_states + 1))), captured
+        results[(depth, graphs)] = (losses, {k: v.detach().cpu().clone() for k, v in model.state_dict().items()})
+    base = results[("0", "0")]
+    assert len(base[0]) == steps * n_states and len(set(base[0])) == len(base[0])       # dropout really varied step to step
+    for key, (losses, sd) in results.items():
+        assert losses == base[0], key
+        for k, v in base[1].items():
+            assert torch.equal(v, sd[k]), (key, k)
+
+
 def test_data_parallel_step_graph_logic_with_emulated_second_rank(tmp_path, monkeypatch):
     """The multi-GPU code path of the captured training step (gradient packing into the flat bucket
     inside the graph, eager all-reduce between the two graphs, Adam on the bucket slices) exercised on
