@@ -243,6 +243,52 @@ def mask_asr_enabled():
     return on
 
 
+def asr_ctc_enabled():
+    """SLU_ASR_CTC: "0" (default) — ASR batches carry one label per frame (forced alignments); "1" — they carry label
+    SEQUENCES and PretrainedModel trains its heads by CTC (models.asr_ctc_enabled).  Needs SLU_MASK_PADDING=1,
+    SLU_MASK_ASR=1 and SLU_MASK_TRAIN=1: CTC needs every utterance's length, in training and in evaluation."""
+    on = _knobs.flag("SLU_ASR_CTC")
+    if on:
+        for name in ("SLU_MASK_PADDING", "SLU_MASK_ASR", "SLU_MASK_TRAIN"):
+            if not _knobs.flag(name):
+                raise ValueError("SLU_ASR_CTC=1 needs %s=1: CTC needs the utterances' lengths in training and in evaluation"
+                                 % name)
+    return on
+
+
+def ctc_max_seconds():
+    """SLU_CTC_MAX_SECONDS (default 20): TranscriptASRDataset skips utterances longer than this."""
+    v = os.environ.get("SLU_CTC_MAX_SECONDS", "20")
+    try:
+        sec = float(v)
+    except ValueError:
+        sec = -1.0
+    if not sec > 0:
+        raise ValueError("SLU_CTC_MAX_SECONDS=%r: expected a positive number of seconds" % v)
+    return sec
+
+
+def ctc_collapse(track):
+    """A frame-label track -> its label sequence: runs of equal consecutive entries are merged first, -1 (no label)
+    counting as an entry, then the -1 are dropped.  A,A,-1,A,B,B -> A,A,B: the track is itself a CTC path of the
+    sequence it gives (-1 in the blank's role), so a forced alignment is always feasible for its own frames."""
+    out, prev = [], None
+    for v in track:
+        v = int(v)
+        if v != prev and v != -1:
+            out.append(v)
+        prev = v
+    return out
+
+
+def _pad_sequences(seqs):
+    y = torch.full((len(seqs), max([len(s) for s in seqs] + [1])), -1, dtype=torch.int64)
+    for i, s in enumerate(seqs):
+        if len(s):
+            y[i, :len(s)] = torch.as_tensor(np.asarray(s, dtype=np.int64))
+    return y
+
+
 class CollateWavsSLU:
     """list of (waveform, [action, object, location]) -> (x (B, T_max) float32 zero-padded at the end,
     y_intent (B, 3) int64), as reference data.py:344-376.  seq2seq: the labels are <sos> ... <eos> index
@@ -575,10 +621,15 @@ class CollateWavsASR:
     y_phoneme, y_word, lengths int32 (B)), so that PretrainedModel.forward(lengths=...) can skip the padded frames.
     pad_multiple (samples; 0, the default and what ASRDataset uses: none) rounds T_max up to a multiple, and the label
     tracks follow by the dataset's own rule, one label per factors = (phone, word downsample factor) samples: with lengths
-    a masked step must not depend on how far its batch is padded, and this is how a test pads it further."""
+    a masked step must not depend on how far its batch is padded, and this is how a test pads it further.
+    Opt-in (SLU_ASR_CTC=1, or ctc=True): (x, y_phoneme_seq (B, S_p), y_word_seq (B, S_w), lengths) — each label track
+    collapsed to its label sequence (ctc_collapse), padded with -1; sequences=True: the items carry label sequences
+    already (TranscriptASRDataset), taken as they are."""
 
-    def __init__(self, mask_asr=None, pad_multiple=0, factors=None):
-        self.mask_asr = mask_asr_enabled() if mask_asr is None else bool(mask_asr)
+    def __init__(self, mask_asr=None, pad_multiple=0, factors=None, ctc=None, sequences=False):
+        self.ctc = asr_ctc_enabled() if ctc is None else bool(ctc)
+        self.sequences = bool(sequences)
+        self.mask_asr = self.ctc or (mask_asr_enabled() if mask_asr is None else bool(mask_asr))
         self.pad_multiple = int(pad_multiple)
         if self.pad_multiple > 1 and factors is None:
             raise ValueError("CollateWavsASR: pad_multiple needs factors = (phone_downsample_factor, word_downsample_factor)")
@@ -593,6 +644,10 @@ class CollateWavsASR:
             T = -(-T // self.pad_multiple) * self.pad_multiple
             Up, Uw = max(Up, -(-T // self.factors[0])), max(Uw, -(-T // self.factors[1]))
         x = _pad_waveforms([b[0] for b in batch], T)
+        if self.ctc:
+            seq = (lambda t: [int(v) for v in t]) if self.sequences else ctc_collapse
+            return (x, _pad_sequences([seq(b[1]) for b in batch]), _pad_sequences([seq(b[2]) for b in batch]),
+                    torch.tensor([len(b[0]) for b in batch], dtype=torch.int32))
         yp = torch.full((n, Up), -1, dtype=torch.int64)
         yw = torch.full((n, Uw), -1, dtype=torch.int64)
         for i, (xi, pi, wi) in enumerate(batch):
@@ -678,6 +733,17 @@ class SyntheticASRDataset(ASRDataset):
             yw = torch.randint(0, config.vocabulary_size, (batch_size, Tw), generator=g)
             yp[torch.rand(batch_size, Tp, generator=g) < 0.1] = -1
             yw[torch.rand(batch_size, Tw, generator=g) < 0.1] = -1
+            if asr_ctc_enabled():
+                # the same draws, served as CollateWavsASR serves an aligned corpus under the knob: ragged sample counts (the
+                # waveforms are zero beyond them), the tracks cut to the frames inside them and collapsed
+                n = torch.randint(num_samples // 2, num_samples + 1, (batch_size,), generator=g)
+                n[0] = num_samples
+                x = x * (torch.arange(num_samples).unsqueeze(0) < n.unsqueeze(1))
+                cut = lambda y, f: _pad_sequences([ctc_collapse(y[i, :max(1, int(n[i]) // f)].tolist())
+                                                   for i in range(batch_size)])
+                batches.append((x, cut(yp, config.phone_downsample_factor), cut(yw, config.word_downsample_factor),
+                                n.to(torch.int32)))
+                continue
             batches.append((x, yp, yw))
         self.batches = batches
         self.loader = _SyntheticLoader(batches)
@@ -689,6 +755,131 @@ class SyntheticASRDataset(ASRDataset):
         bs = len(self.batches[0][0])
         b = self.batches[idx // bs]
         return tuple(t[idx % bs] for t in b)
+
+
+CTC_MAX_LABELS = 255        # 2 S + 1 <= 512 states: what slu_ctc_loss_fwd is instantiated for
+
+
+def read_lexicon(path):
+    """A pronunciation lexicon in CMUdict text format — `WORD  PH PH ...` per line, `;;;` comments, alternative
+    pronunciations as WORD(2) (the first one wins) — -> {WORD: [phoneme, ...]} with the stress digits stripped."""
+    lex = {}
+    with open(path, "r", encoding="latin-1") as f:
+        for ln in f:
+            parts = ln.split()
+            if not parts or ln.startswith(";;;"):
+                continue
+            word = parts[0].split("(")[0]
+            lex.setdefault(word, [_strip_stress(ph) for ph in parts[1:]])
+    return lex
+
+
+def read_transcripts(audio_root, split):
+    """LibriSpeech's own transcripts: audio/<split>*/<spk>/<chap>/<spk>-<chap>.trans.txt, lines `<utt-id> WORD WORD ...`
+    -> sorted [(wav path, [WORD, ...])] of the utterances whose .wav file exists."""
+    import glob
+    items = []
+    for tr in sorted(glob.glob(os.path.join(audio_root, split + "*", "*", "*", "*.trans.txt"))):
+        with open(tr, "r") as f:
+            for ln in f:
+                parts = ln.split()
+                if not parts:
+                    continue
+                wav = os.path.join(os.path.dirname(tr), parts[0] + ".wav")
+                if os.path.isfile(wav):
+                    items.append((wav, parts[1:]))
+    return sorted(items)
+
+
+class TranscriptASRDataset(ASRDataset):
+    """ASR pre-training without alignments (SLU_ASR_CTC=1): item = a WHOLE utterance (a transcript cannot be cut) with its
+    word-index sequence (out-of-vocabulary words dropped) and its phoneme-index sequence through the lexicon (a word
+    without an entry contributes no phonemes).  Utterances longer than SLU_CTC_MAX_SECONDS, or with more than
+    CTC_MAX_LABELS labels, are skipped, with one printed count.  `.loader` yields CollateWavsASR's CTC batches."""
+
+    def __init__(self, items, Sy_phoneme, Sy_word, lexicon, config, shard=False):
+        self._phone_idx, self._word_idx = {}, {}
+        for i, v in enumerate(Sy_phoneme):
+            self._phone_idx.setdefault(v, i)
+        for i, v in enumerate(Sy_word):
+            self._word_idx.setdefault(v, i)
+        self.Sy_phoneme, self.Sy_word = Sy_phoneme, Sy_word
+        limit, kept, skipped = ctc_max_seconds(), [], 0
+        for wav, words in items:
+            n, fs = _wav_frames_rate(wav)
+            wd = [self._word_idx[w] for w in words if w in self._word_idx]
+            ph = [self._phone_idx[p] for w in words for p in lexicon.get(w, ()) if p in self._phone_idx]
+            if n > limit * fs or n < 1 or max(len(wd), len(ph)) > CTC_MAX_LABELS:
+                skipped += 1
+                continue
+            kept.append((wav, ph, wd))
+        if skipped:
+            print("TranscriptASRDataset: skipped %d of %d utterances (longer than %g s or more than %d labels)"
+                  % (skipped, len(items), limit, CTC_MAX_LABELS))
+        self.items = kept
+        self.wav_paths = [k[0] for k in kept]
+        rank, world = _world() if shard else (0, 1)
+        collate = CollateWavsASR(ctc=True, sequences=True)
+        kw = dict(batch_size=config.pretraining_batch_size, num_workers=_loader_workers(), collate_fn=collate,
+                  pin_memory=torch.cuda.is_available())
+        if world > 1:
+            kw["sampler"] = torch.utils.data.distributed.DistributedSampler(self, num_replicas=world, rank=rank, shuffle=True,
+                                                                            seed=getattr(config, "seed", 0))
+        else:
+            kw["shuffle"] = shard
+        self.loader = ForkSafeDataLoader(self, **kw)
+
+    def __len__(self):
+        return len(self.items)
+
+    def __getitem__(self, idx):
+        wav, ph, wd = self.items[idx]
+        x32, _ = read_wav(wav)
+        return x32.astype(np.float64), ph, wd
+
+
+def _wav_frames_rate(path):
+    from scipy.io import wavfile
+    fs, a = wavfile.read(path, mmap=True)
+    return int(a.shape[0]), int(fs)
+
+
+def _transcript_datasets(config):
+    """get_ASR_datasets without alignments: the vocabularies from <folder>/pretraining/{words,phonemes}.txt, or built from
+    the dev split's transcripts (the vocabulary_size most common words; the lexicon's phonemes in first-seen order)."""
+    audio = os.path.join(config.asr_path, "audio")
+    splits = {k: read_transcripts(audio, k) for k in ("train", "dev", "test")}
+    lex_file = os.path.join(config.folder, "pretraining", "lexicon.txt")
+    if not os.path.isfile(lex_file):
+        raise ValueError("SLU_ASR_CTC=1 without alignments needs a pronunciation lexicon (CMUdict text format) at %s" % lex_file)
+    lexicon = read_lexicon(lex_file)
+    ph_file = os.path.join(config.folder, "pretraining", "phonemes.txt")
+    wd_file = os.path.join(config.folder, "pretraining", "words.txt")
+    rank, world = _world()
+    if world > 1:
+        import torch.distributed as dist
+        if rank != 0:
+            dist.barrier()
+    if os.path.isfile(wd_file):
+        with open(wd_file, "r") as f:
+            Sy_word = [ln.rstrip("\n") for ln in f.readlines()]
+    else:
+        counter = Counter(w for _, words in splits["dev"] for w in words)
+        Sy_word = [w for w, _ in counter.most_common(config.vocabulary_size)]
+        with open(wd_file, "w") as f:
+            f.writelines(w + "\n" for w in Sy_word)
+    if os.path.isfile(ph_file):
+        with open(ph_file, "r") as f:
+            Sy_phoneme = [ln.rstrip("\n") for ln in f.readlines() if ln.rstrip("\n") != ""]
+    else:
+        Sy_phoneme = list(dict.fromkeys(p for _, words in splits["dev"] for w in words for p in lexicon.get(w, ())))
+        with open(ph_file, "w") as f:
+            f.writelines(p + "\n" for p in Sy_phoneme)
+    if world > 1 and rank == 0:
+        dist.barrier()
+    config.num_phonemes = len(Sy_phoneme)
+    mk = lambda k, shard=False: TranscriptASRDataset(splits[k], Sy_phoneme, Sy_word, lexicon, config, shard=shard)
+    return mk("train", True), mk("dev"), mk("test")
 
 
 def _synthetic_spec(path):
@@ -844,6 +1035,8 @@ def get_ASR_datasets(config):
     # sorted: glob returns the directory order of the file system, which differs from machine to machine — and with it the
     # ties of the vocabulary count below, which utterances share a batch under a given seed, and (under data parallelism,
     # where DistributedSampler indexes into the list) which rank gets which file
+    if asr_ctc_enabled() and not glob.glob(base_path + "/text/*/*/*/*.TextGrid"):
+        return _transcript_datasets(config)              # no alignments: LibriSpeech's own transcripts (CTC only)
     train_tg = sorted(glob.glob(base_path + "/text/train*/*/*/*.TextGrid"))
     valid_tg = sorted(glob.glob(base_path + "/text/dev*/*/*/*.TextGrid"))
     test_tg = sorted(glob.glob(base_path + "/text/test*/*/*/*.TextGrid"))

@@ -258,6 +258,14 @@ def mask_augment_enabled():
     return _knobs.flag("SLU_MASK_AUGMENT")
 
 
+def asr_ctc_enabled():
+    """SLU_ASR_CTC: "0" (default) — PretrainedModel's heads are the frame heads (cross-entropy against forced alignments);
+    "1" — a PretrainedModel built under it has CTC heads (DESIGN.md section 7 "CTC pre-training"): one more output per
+    Linear, the blank, LAST; forward takes label SEQUENCES and needs lengths.  Read at construction only.  data.py adds
+    the data side's rule: 1 needs SLU_MASK_PADDING=1, SLU_MASK_ASR=1 and SLU_MASK_TRAIN=1."""
+    return _knobs.flag("SLU_ASR_CTC")
+
+
 def mask_frozen_math_mode():
     """SLU_MASK_FROZEN_MATH: the contraction arithmetic of FROZEN stages in every lengths=... call: "fp32" (default) — the
     exact kernels, whatever SLU_FROZEN_MATH says; "bf16x3" — a stage with no trainable parameter whose input needs no
@@ -1573,11 +1581,17 @@ def _build_rnn_stack(layers, stages, prefix, in_dim, hidden, bidirectional, drop
 
 
 class PretrainedModel(torch.nn.Module):
-    """Encoder pre-trained to recognise phonemes and words (reference models.py:170-361)."""
+    """Encoder pre-trained to recognise phonemes and words (reference models.py:170-361).
+    SLU_ASR_CTC=1 at construction (asr_ctc_enabled; self.ctc): phoneme_linear has num_phonemes + 1 outputs and word_linear
+    vocabulary_size + 1, the blank being the LAST index of each; the state_dict keys are the same.  Initialisation order:
+    phoneme_linear is drawn between the phoneme layers and the word layers, as in the reference, so under the knob every
+    draw up to and including the phoneme layers is the knob-off one, and the word layers and word_linear follow a
+    phoneme_linear that drew one more row."""
 
     def __init__(self, config):
         super().__init__()
         self.is_cuda = torch.cuda.is_available()
+        self.ctc = asr_ctc_enabled()
         phoneme_layers, self._cnn_stages, self._phone_stages = [], [], []
         n_conv = len(config.cnn_N_filt)
         for idx in range(n_conv):
@@ -1606,7 +1620,7 @@ class PretrainedModel(torch.nn.Module):
                                    config.phone_rnn_drop, config.phone_downsample_type,
                                    config.phone_downsample_len)
         self.phoneme_layers = torch.nn.ModuleList(phoneme_layers)
-        self.phoneme_linear = torch.nn.Linear(out_dim, config.num_phonemes)
+        self.phoneme_linear = torch.nn.Linear(out_dim, config.num_phonemes + int(self.ctc))
 
         word_layers, self._word_stages = [], []
         out_dim = _build_rnn_stack(word_layers, self._word_stages, "word", out_dim,
@@ -1614,7 +1628,7 @@ class PretrainedModel(torch.nn.Module):
                                    config.word_rnn_drop, config.word_downsample_type,
                                    config.word_downsample_len)
         self.word_layers = torch.nn.ModuleList(word_layers)
-        self.word_linear = torch.nn.Linear(out_dim, config.vocabulary_size)
+        self.word_linear = torch.nn.Linear(out_dim, config.vocabulary_size + int(self.ctc))
         self.pretraining_type = config.pretraining_type
         if self.is_cuda:
             self.cuda()
@@ -1787,7 +1801,14 @@ class PretrainedModel(torch.nn.Module):
         one, or a 1-element int64 CUDA tensor holding step*16 (hipGraph-captured steps).
         lengths (not in the reference; None: the call as it was): the utterances' sample counts, each in [1, T] -> the
         masked pre-training step (_forward_len): a frame counts iff its label is not -1 and it lies inside its utterance,
-        and losses and gradients are the kept-frame-weighted mean of what each x[b:b+1, :lengths[b]] gives run alone."""
+        and losses and gradients are the kept-frame-weighted mean of what each x[b:b+1, :lengths[b]] gives run alone.
+        A CTC model (self.ctc) takes label SEQUENCES — y_phoneme / y_word (B, S) int64 padded with -1 — and needs lengths:
+        losses are sum nll / sum of the target lengths over the feasible rows, the "accuracies" 1 - label error rate of
+        the greedy decoding (include/slu_hip.h, "CTC pre-training")."""
+        if self.ctc:
+            if lengths is None:
+                raise ValueError("ctc: a CTC model (SLU_ASR_CTC=1) needs lengths=...: the utterances' sample counts")
+            return self._forward_ctc(x, y_phoneme, y_word, lengths, rng_step)
         if lengths is not None:
             return self._forward_len(x, y_phoneme, y_word, lengths, rng_step)
         x, y_phoneme, y_word = self._to_device(x, y_phoneme, y_word)
@@ -1832,6 +1853,62 @@ class PretrainedModel(torch.nn.Module):
         word_loss, word_acc = _ops.FrameHeadLenFn.apply(wd.out, wd.n_dev.contiguous(), wd.pack[0].contiguous(), wd.pack[1],
                                                         wl.weight, wl.bias, y_word)
         return phoneme_loss, word_loss, phoneme_acc, word_acc
+
+    @staticmethod
+    def _ctc_targets(y, name, B):
+        """(B, S) int64 label sequences padded with -1 -> (y on the host, the counts of leading non--1 entries)."""
+        if not torch.is_tensor(y) or y.dtype != torch.int64 or y.dim() != 2 or y.shape[0] != B:
+            raise ValueError("ctc: %s must be int64 label sequences of shape (%d, S) padded with -1" % (name, B))
+        y = y.detach().cpu()
+        lead = (y != -1).to(torch.int64).cumprod(dim=1).sum(dim=1) if y.shape[1] else torch.zeros(B, dtype=torch.int64)
+        return y, lead.to(torch.int32)
+
+    def _forward_ctc(self, x, y_phoneme, y_word, lengths, rng_step):
+        """_forward_len with ops.CTCHeadLenFn in place of ops.FrameHeadLenFn for both heads: the encoder, the packing, the
+        Linear, the backward GEMMs and every refusal of _enter_len are the masked frame heads'."""
+        first = self._cnn_stages + self._phone_stages
+        word = list(self._word_stages) if self.pretraining_type != 1 else []
+        B = x.shape[0] if x.dim() == 2 else -1
+        y_phoneme, n_ph = self._ctc_targets(y_phoneme, "y_phoneme", B)
+        if word:
+            y_word, n_wd = self._ctc_targets(y_word, "y_word", B)
+        x, host = _enter_len(self, x, lengths, first + word, train_ok=True, rng_step=rng_step)
+        ph = _run_stages_len(first, x, host, training=self.training, pack=True)
+        pl = self.phoneme_linear
+        phoneme_loss, phoneme_acc = _ops.CTCHeadLenFn.apply(ph.out, ph.n_dev.contiguous(), ph.pack[0].contiguous(), ph.pack[1],
+                                                            pl.weight, pl.bias, y_phoneme, n_ph, pl.out_features - 1)
+        self.ctc_records = [_ops.CTCHeadLenFn.last_out4]
+        if self.pretraining_type == 1:
+            return phoneme_loss, torch.tensor([0.]), phoneme_acc, torch.tensor([0.])
+        wd = _run_stages_len(word, ph.out, ph.n_host, training=self.training, pack=True)
+        wl = self.word_linear
+        word_loss, word_acc = _ops.CTCHeadLenFn.apply(wd.out, wd.n_dev.contiguous(), wd.pack[0].contiguous(), wd.pack[1],
+                                                      wl.weight, wl.bias, y_word, n_wd, wl.out_features - 1)
+        self.ctc_records.append(_ops.CTCHeadLenFn.last_out4)
+        return phoneme_loss, word_loss, phoneme_acc, word_acc
+
+    def decode_phonemes(self, x, lengths):
+        """Greedy CTC decoding of the phoneme head (a CTC model in eval mode): x (B, T) waveforms, lengths their sample
+        counts -> one list of phoneme indices per utterance (per frame the first arg-max, repeats collapsed, blanks
+        dropped: slu_ctc_greedy_errors).  One device-to-host copy at the end."""
+        if not self.ctc:
+            raise ValueError("ctc: decode_phonemes needs a CTC model (SLU_ASR_CTC=1 at construction)")
+        if self.training:
+            raise ValueError("lengths: the length-aware path is inference only (dropout is not applied): call eval() first")
+        first = self._cnn_stages + self._phone_stages
+        x, host = _enter_len(self, x, lengths, first)
+        with torch.no_grad():
+            ph = _run_stages_len(first, x, host, pack=True)
+            n_dev, off = ph.n_dev.contiguous(), ph.pack[0].contiguous()
+            hp, _ = _ops.frame_pack_len(ph.out, None, n_dev, off, ph.pack[1])
+            pl = self.phoneme_linear
+            logits = _ops.gemm(hp, pl.weight.detach().t(), pl.bias.detach())
+            B = len(host)
+            _, hyp, hyp_len, _ = _ops.ctc_greedy(logits, n_dev, off, torch.zeros(B, 1, dtype=torch.int64), [0] * B,
+                                                 pl.out_features - 1)
+            hyp, hyp_len = hyp.cpu().tolist(), hyp_len.cpu().tolist()
+        offsets, _ = _ops.frame_pack_plan(ph.n_host)
+        return [hyp[o:o + n] for o, n in zip(offsets, hyp_len)]
 
     def _posteriors_len(self, x, lengths):
         """compute_posteriors with per-utterance lengths: the length-aware evaluation of compute_features(x, lengths), the two
@@ -1936,7 +2013,15 @@ class Model(torch.nn.Module):
             path = os.path.join(config.folder, "pretraining", "model_state.pth")
             # the file was written by rank 0 from cuda:0: deserialise onto the host, copy into this rank's
             # parameters (no allocation on a device the rank does not own)
-            pretrained_model.load_state_dict(torch.load(path, map_location="cpu"))
+            state = torch.load(path, map_location="cpu")
+            for key in ("phoneme_linear.weight", "word_linear.weight"):
+                have, want = state[key].shape[0] if key in state else None, pretrained_model.state_dict()[key].shape[0]
+                if have is not None and have != want and abs(have - want) == 1:
+                    raise ValueError("%s: %s has %d rows in the checkpoint and %d in this model: the checkpoint was pre-trained "
+                                     "with SLU_ASR_CTC=%d (CTC heads carry one more output, the blank) and this process runs "
+                                     "with SLU_ASR_CTC=%d — set the knob as the pre-training had it"
+                                     % (path, key, have, want, int(have > want), int(pretrained_model.ctc)))
+            pretrained_model.load_state_dict(state)
         self.pretrained_model = pretrained_model
         self.unfreezing_type = config.unfreezing_type
         self.unfreezing_index = config.starting_unfreezing_index

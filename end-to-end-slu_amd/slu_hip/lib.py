@@ -116,6 +116,9 @@ SIGNATURES = {
                                       c_f32, c_i64, c_i64, c_i64, c_i64, vp]),
     "slu_frame_pack_len": (c_int, [vp, vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_i64, vp]),
     "slu_frame_unpack_len": (c_int, [vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, vp]),
+    "slu_ctc_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
+    "slu_ctc_loss_fwd": (c_int, [vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, vp, vp, vp, c_sz, vp]),
+    "slu_ctc_greedy_errors": (c_int, [vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_i64, vp, vp, vp, vp, vp]),
     "slu_comm_version": (c_int, []),
     "slu_comm_unique_id": (c_int, [vp]),
     "slu_comm_init": (c_int, [vp, vp, c_i64, c_i64]),

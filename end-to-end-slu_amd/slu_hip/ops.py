@@ -1810,6 +1810,152 @@ class FrameHeadLenFn(torch.autograd.Function):
         return dh, None, None, None, dW, db, None
 
 
+CTC_MAX_STATES = 512       # 2 S + 1 states slu_ctc_loss_fwd is instantiated for (csrc/slu_ctc.hip)
+
+
+def ctc_prepare(targets, target_lengths, V, blank, device):
+    """Every host refusal of the CTC calls (ValueError("ctc: ...")), then the two tables on the device.  targets (B, S)
+    int64 label sequences, entries at and beyond target_lengths[b] are padding (any value: never read); target_lengths (B)
+    int32 / int64 or a list.  Both are HOST data — a CUDA tensor is read back here, which synchronises; the model hands
+    the collate function's CPU tensors.  -> (targets (B, max(S, 1)) int64, target_lengths (B) int32) on `device`."""
+    if not torch.is_tensor(targets) or targets.dtype != torch.int64 or targets.dim() != 2:
+        raise ValueError("ctc: targets must be an int64 tensor of shape (B, S), got %s"
+                         % ("%s %s" % (targets.dtype, tuple(targets.shape)) if torch.is_tensor(targets) else type(targets)))
+    B, S = targets.shape
+    tl = torch.as_tensor(target_lengths)
+    if tl.is_floating_point() or tl.dtype == torch.bool or tl.dim() != 1 or tl.numel() != B:
+        raise ValueError("ctc: target_lengths must be %d integers, got %s %s" % (B, tl.dtype, tuple(tl.shape)))
+    if not 0 <= int(blank) < V:
+        raise ValueError("ctc: blank %d outside [0, %d)" % (blank, V))
+    if 2 * S + 1 > CTC_MAX_STATES:
+        raise ValueError("ctc: targets of up to %d labels need %d states, the kernels take %d" % (S, 2 * S + 1, CTC_MAX_STATES))
+    th, tl = targets.detach().cpu(), tl.detach().cpu().to(torch.int64)
+    if B == 0 or bool(((tl < 0) | (tl > S)).any()):
+        raise ValueError("ctc: target_lengths outside [0, %d]" % S)
+    if S > 0:
+        used = torch.arange(S).unsqueeze(0) < tl.unsqueeze(1)
+        lab = th[used]
+        if bool((lab == -1).any()):
+            raise ValueError("ctc: a -1 inside the first target_lengths[b] entries of a target")
+        if bool(((lab < 0) | (lab >= V)).any()):
+            raise ValueError("ctc: a label outside [0, %d)" % V)
+        if bool((lab == blank).any()):
+            raise ValueError("ctc: a label equal to the blank (%d)" % blank)
+        th = torch.where(used, th, torch.zeros_like(th))
+    else:
+        th = torch.zeros(B, 1, dtype=torch.int64)
+    return th.contiguous().to(device, non_blocking=True), tl.to(torch.int32).to(device, non_blocking=True)
+
+
+def _ctc_logits(logits, lengths, offsets):
+    if (not torch.is_tensor(logits) or logits.dtype != torch.float32 or not logits.is_cuda or logits.dim() != 2
+            or not logits.is_contiguous()):
+        raise ValueError("ctc: logits must be a contiguous float32 CUDA tensor (N, V)")
+    N, V = logits.shape
+    B = lengths.numel() if torch.is_tensor(lengths) else -1
+    for t, name in ((lengths, "lengths"), (offsets, "offsets")):
+        if (not torch.is_tensor(t) or t.dtype != torch.int32 or not t.is_cuda or t.dim() != 1 or t.numel() != B
+                or not t.is_contiguous() or B < 1):
+            raise ValueError("ctc: %s must be a contiguous int32 CUDA tensor of B entries" % name)
+    if N < 1 or V < 1:
+        raise ValueError("ctc: empty logits %s" % (tuple(logits.shape),))
+    return N, V, B
+
+
+def _ctc_loss_dev(logits, lengths, offsets, tg, tl, blank, write_grad):
+    L = _lib.load()
+    N, V = logits.shape
+    B, S = tg.shape
+    nbytes = L.slu_ctc_workspace_bytes(N, B, S)
+    ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=logits.device)
+    nll = torch.empty(B, dtype=torch.float32, device=logits.device)
+    out4 = torch.empty(4, dtype=torch.float32, device=logits.device)
+    _lib.check(L.slu_ctc_loss_fwd(logits.data_ptr(), lengths.data_ptr(), offsets.data_ptr(), tg.data_ptr(), tl.data_ptr(), N, V,
+                                  B, S, int(blank), int(bool(write_grad)), nll.data_ptr(), out4.data_ptr(), ws.data_ptr(),
+                                  nbytes, _stream()), "slu_ctc_loss_fwd")
+    return out4, nll
+
+
+def _ctc_greedy_dev(logits, lengths, offsets, tg, tl, blank):
+    L = _lib.load()
+    N, V = logits.shape
+    B, S = tg.shape
+    dev = logits.device
+    hyp = torch.empty(N, dtype=torch.int32, device=dev)
+    hyp_len = torch.empty(B, dtype=torch.int32, device=dev)
+    errors = torch.empty(B, dtype=torch.int32, device=dev)
+    out2 = torch.empty(2, dtype=torch.float32, device=dev)
+    _lib.check(L.slu_ctc_greedy_errors(logits.data_ptr(), lengths.data_ptr(), offsets.data_ptr(), tg.data_ptr(), tl.data_ptr(),
+                                       N, V, B, S, int(blank), hyp.data_ptr(), hyp_len.data_ptr(), errors.data_ptr(),
+                                       out2.data_ptr(), _stream()), "slu_ctc_greedy_errors")
+    return out2, hyp, hyp_len, errors
+
+
+def ctc_loss(logits, lengths, offsets, targets, target_lengths, blank, write_grad=False):
+    """slu_ctc_loss_fwd (include/slu_hip.h, "CTC pre-training") on the packed rows: logits (N, V) fp32 CUDA, lengths /
+    offsets int32 CUDA (B), targets (B, S) int64 and target_lengths (B) host data (ctc_prepare) ->
+    (out4 = [loss, sum S_b, #infeasible, B], nll (B)).  write_grad: logits are overwritten with d loss / d logits."""
+    N, V, B = _ctc_logits(logits, lengths, offsets)
+    if not torch.is_tensor(targets) or targets.dim() != 2 or targets.shape[0] != B:
+        raise ValueError("ctc: targets must be an int64 tensor of shape (%d, S)" % B)
+    tg, tl = ctc_prepare(targets, target_lengths, V, blank, logits.device)
+    return _ctc_loss_dev(logits, lengths, offsets, tg, tl, blank, write_grad)
+
+
+def ctc_greedy(logits, lengths, offsets, targets, target_lengths, blank):
+    """slu_ctc_greedy_errors: greedy CTC decoding of the packed rows and the label errors against the targets ->
+    (out2 = [1 - sum errors / sum S_b, sum S_b], hyp (N) int32 — utterance b's labels at hyp[offsets[b] : offsets[b] +
+    hyp_len[b]], -1 behind them —, hyp_len (B) int32, errors (B) int32)."""
+    N, V, B = _ctc_logits(logits, lengths, offsets)
+    if not torch.is_tensor(targets) or targets.dim() != 2 or targets.shape[0] != B:
+        raise ValueError("ctc: targets must be an int64 tensor of shape (%d, S)" % B)
+    tg, tl = ctc_prepare(targets, target_lengths, V, blank, logits.device)
+    return _ctc_greedy_dev(logits, lengths, offsets, tg, tl, blank)
+
+
+class CTCHeadLenFn(torch.autograd.Function):
+    """The CTC form of FrameHeadLenFn (SLU_ASR_CTC=1): h time-major (T, B, C), lengths / offsets / n_total as there,
+    targets (B, S) int64 label sequences and target_lengths (B) on the host (ctc_prepare refuses bad ones before the first
+    launch), blank = the blank's index among the weight's V rows.  slu_frame_pack_len gathers the valid rows (activations
+    only), the Linear is FrameHeadFn's, slu_ctc_loss_fwd takes slu_frame_ce_fwd's place and leaves d loss / d logits in the
+    logits buffer, slu_ctc_greedy_errors gives the second output; the backward is _frame_head_bwd and slu_frame_unpack_len:
+    d h is exactly 0 at padded frames.  Returns (loss, 1 - label error rate); CTCHeadLenFn.last_out4 keeps the device
+    record [loss, sum S_b, #infeasible, B] of the last call for the Trainer's count."""
+
+    last_out4 = None
+
+    @staticmethod
+    def forward(ctx, h, lengths, offsets, n_total, weight, bias, targets, target_lengths, blank):
+        V = weight.shape[0]
+        if h.dim() != 3 or not torch.is_tensor(targets) or targets.dim() != 2 or targets.shape[0] != h.shape[1]:
+            raise ValueError("ctc: targets must be an int64 tensor of shape (%d, S)" % (h.shape[1] if h.dim() == 3 else -1))
+        tg, tl = ctc_prepare(targets, target_lengths, V, blank, h.device)
+        hp, _ = frame_pack_len(h, None, lengths, offsets, n_total)
+        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[4] or ctx.needs_input_grad[5]
+        logits = gemm_nt(hp, weight, bias, bf16_ok=False)
+        out2 = _ctc_greedy_dev(logits, lengths, offsets, tg, tl, blank)[0]          # before the logits become a gradient
+        out4, _ = _ctc_loss_dev(logits, lengths, offsets, tg, tl, blank, need)
+        if need:
+            ctx.save_for_backward(hp, weight, logits, lengths, offsets)
+        ctx.set_materialize_grads(False)
+        ctx.shape = tuple(h.shape)
+        CTCHeadLenFn.last_out4 = out4
+        acc = out2[0]
+        ctx.mark_non_differentiable(acc)
+        return out4[0], acc
+
+    @staticmethod
+    def backward(ctx, d_loss, _d_acc):
+        if d_loss is None:
+            return (None,) * 9
+        hp, weight, d_logits, lengths, offsets = ctx.saved_tensors
+        T, B, _ = ctx.shape
+        need = ctx.needs_input_grad
+        dhp, dW, db = _frame_head_bwd(hp, weight, d_logits, d_loss, need[0], need[4], need[5])
+        dh = frame_unpack_len(dhp, lengths, offsets, T, B) if dhp is not None else None
+        return dh, None, None, None, dW, db, None, None, None
+
+
 class SincBlockFn(torch.autograd.Function):
     """SincLayer -> Abs -> MaxPool1d(ceil) -> LeakyReLU  (models.py:77-110, :163-168, :205, :211).
     x (B,T) -> (B, L_out, N_filt) channels-last, or (L_out, B, N_filt) when time_major."""

@@ -24,7 +24,7 @@ import torch
 from tqdm import tqdm
 
 from data import SLUDataset, ASRDataset, mask_padding_enabled as data_mask_padding_enabled
-from data import mask_asr_enabled
+from data import asr_ctc_enabled, mask_asr_enabled
 from models import PretrainedModel, Model, next_rng_step, mask_augment_enabled as models_mask_augment_enabled
 from slu_hip import dp, ops, pipeline
 from slu_hip import knobs as _knobs
@@ -302,6 +302,8 @@ class Trainer:
         mask_train_enabled()                     # SLU_MASK_TRAIN=1 without SLU_MASK_PADDING=1 fails here, not at the first step
         mask_asr_enabled()                       # and so does SLU_MASK_ASR=1
         mask_augment_enabled()                   # and SLU_MASK_AUGMENT=1 without SLU_MASK_TRAIN=1
+        asr_ctc_enabled()                        # and SLU_ASR_CTC=1 without the three lengths knobs
+        self._ctc_infeasible = None              # CTC pre-training: this epoch's infeasible rows, a device counter (_run reads it)
         if isinstance(self.model, PretrainedModel):
             self.lr = config.pretraining_lr
             self.checkpoint_path = os.path.join(self.config.folder, "pretraining")
@@ -430,6 +432,10 @@ class Trainer:
             x, y_phoneme, y_word = batch[:3]
             if extra:
                 phoneme_loss, word_loss, phoneme_acc, word_acc = self.model(x, y_phoneme, y_word, **extra)
+                if getattr(self.model, "ctc", False) and getattr(self.model, "training", False):
+                    # [loss, sum S_b, #infeasible, B] of each head (ops.CTCHeadLenFn): counted on the device
+                    for rec in self.model.ctc_records:
+                        self._ctc_infeasible = rec[2].clone() if self._ctc_infeasible is None else self._ctc_infeasible + rec[2]
             elif rng_step is None:
                 phoneme_loss, word_loss, phoneme_acc, word_acc = self.model(x, y_phoneme, y_word)
             else:
@@ -907,6 +913,10 @@ class Trainer:
                 warnings.warn("non-finite epoch metrics with SLU_FROZEN_MATH=f16x2 (the UNGUARDED form of the scheme: "
                               "operands must stay below 65504 in magnitude) — the default mode guards the range and falls "
                               "back to bf16x3 by itself")
+        if train and asr and self._ctc_infeasible is not None:
+            # one read per epoch, with the device idle; an infeasible row (fewer frames than its labels need) trains nothing
+            self._say("CTC: %d infeasible rows this epoch (both heads)" % int(self._ctc_infeasible.item()))
+            self._ctc_infeasible = None
         if train and self.clip_grad_norm is not None:
             cs = self.clip_stats()                   # one read of the device record per epoch, with the device idle
             self._say("gradient clipping (max norm %g): last norm %.6g, last coefficient %.6g; %d steps so far, %d clipped, "

@@ -880,6 +880,46 @@ int slu_frame_pack_len(const float* h, const int64_t* y, const int32_t* lengths,
 int slu_frame_unpack_len(const float* src, const int32_t* lengths, const int32_t* offsets, float* dst, int64_t T, int64_t B,
                          int64_t C, int64_t N, void* stream);
 
+/* -------- CTC pre-training: the heads of PretrainedModel.forward under SLU_ASR_CTC=1 — added under ABI 10 (three new
+ * entry points; nothing existing changed, so the version number stays).  No counterpart in the reference, which trains
+ * its heads against forced alignments only.  Layout: the length-aware frame heads' — logits (N, V) fp32 row-major on the
+ * PACKED rows (N = sum_b n[b], utterance-major), lengths / offsets (B) int32 from the host's table, V includes the blank,
+ * targets (B, S) int64, target_lengths (B) int32 (S_b, clamped into [0, S]), blank in [0, V).  targets[b, s] for
+ * s >= S_b is never read.
+ * Definition (slu_ctc_loss_fwd):
+ *   nll[b]     = -log sum over the alignments of targets[b, :S_b] to the n[b] frames, by the alpha recursion over the
+ *                extended sequence l' (2 S_b + 1 states: blanks around every label) in log space; +inf when infeasible;
+ *   feasible   row b is feasible iff n[b] >= S_b + #{s : targets[b, s] == targets[b, s - 1]};
+ *   loss       = sum_feasible nll[b] / sum_feasible S_b.  A feasible row with S_b = 0 adds its nll to the numerator and
+ *                nothing to the denominator.  An infeasible row contributes nothing; its gradient rows are exactly 0.0f
+ *                (selected, never a product);
+ *   out4       = [loss, sum_feasible S_b, #infeasible, B]; no feasible row: loss = NaN, as the frame heads give when no
+ *                frame is kept;
+ *   hence      loss = sum_b S_b L_b / sum_b S_b with L_b = nll[b] / S_b what utterance b gives run alone: the weighted
+ *                mean of the masked frame heads;
+ *   gradient   write_grad != 0: logits are overwritten IN PLACE with d loss / d logits (as slu_frame_ce_fwd does)
+ *                = (softmax[t, v] - occ[t, v]) / sum_feasible S_b,
+ *                occ[t, v] = sum_{s : l'_s = v} exp(alpha_t(s) + beta_t(s) - logp[t, l'_s]) / Z_t,
+ *                Z_t = the same sum over all s (= exp(-nll[b]) for every t, taken per frame so that every gradient
+ *                row sums to 0 up to the rounding of its own terms).  Repeated labels add in increasing s.
+ * No floating-point atomics: two runs are bit-equal.  -inf (an unreachable state) combined with -inf gives -inf.
+ * Supported: 2 S + 1 <= 512 (SLU_ERR_UNSUPPORTED beyond).  SLU_ERR_INVALID_ARG: a NULL pointer, a non-positive size,
+ * blank outside [0, V), N or V or B * S >= 2^31; SLU_ERR_WORKSPACE: fewer than slu_ctc_workspace_bytes(N, B, S) bytes
+ * (0 for sizes the call would refuse).  All refusals happen before any launch.  Bad tables cannot index out of bounds:
+ * n[b] is clamped into [1, N]; an utterance whose rows leave [0, N), or with a label outside [0, V) (clamped for
+ * addressing) or equal to the blank, is infeasible (the host rejects all of these first).
+ * slu_ctc_greedy_errors — the metric logged in place of the frame accuracy.  Per utterance: the first arg-max of every
+ * frame, repeats collapsed, blanks dropped -> hyp (N) int32 (utterance b's hypothesis at hyp[offsets[b] ..], hyp_len[b]
+ * entries, -1 behind them) and the Levenshtein distance to targets[b, :S_b] -> errors (B) int32;
+ * out2 = [1 - sum errors / sum S_b, sum S_b] over ALL rows, feasible or not.  Integers apart from the arg-max.        */
+size_t slu_ctc_workspace_bytes(int64_t N, int64_t B, int64_t S);
+int slu_ctc_loss_fwd(float* logits, const int32_t* lengths, const int32_t* offsets, const int64_t* targets,
+                     const int32_t* target_lengths, int64_t N, int64_t V, int64_t B, int64_t S, int64_t blank,
+                     int write_grad, float* nll, float* out4, void* workspace, size_t workspace_bytes, void* stream);
+int slu_ctc_greedy_errors(const float* logits, const int32_t* lengths, const int32_t* offsets, const int64_t* targets,
+                          const int32_t* target_lengths, int64_t N, int64_t V, int64_t B, int64_t S, int64_t blank,
+                          int32_t* hyp, int32_t* hyp_len, int32_t* errors, float* out2, void* stream);
+
 /* -------- Adam: torch.optim.Adam(model.parameters(), lr) (training.py:19, default betas / eps) ------
  * One launch updates up to slu_adam_max_tensors() tensors of one dtype (elem_bytes 4 / 8); the pointer
  * arrays are HOST arrays of device pointers (they travel in the kernel arguments: hipGraph-safe).
