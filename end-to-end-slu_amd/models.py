@@ -24,6 +24,7 @@ Seq2SeqDecoder with beam search) is provided on the same kernels (ops.Seq2SeqDec
 """
 import collections
 import contextlib
+import copy
 import os
 import sys
 
@@ -680,6 +681,88 @@ def _check_lexicon(lexicon, eos, V, U):
         raise ValueError("lexicon: its longest entry has %d labels, the search has U = %d steps" % (lexicon.max_len, U))
 
 
+def _one_hot(labels, V):
+    """labels (...) int64 -> (..., V) float32 one-hot."""
+    out = torch.zeros(labels.shape + (V,), dtype=torch.float32, device=labels.device)
+    return out.scatter_(labels.dim(), labels.unsqueeze(-1), 1.0)
+
+
+class _StepScratch:
+    """What one ops.decoder_step reads and writes for a step batch of R = W * bsz rows, shared by infer, search and
+    score_lexicon: row w * bsz + b is hypothesis slot (or trie node) w of utterance b — it reads utterance b's keys and
+    values and, with lengths, carries utterance b's frame count in n_rows (int32, T until fill_memory)."""
+    ROW_DIM = dict(keys=1, values=1, state=0, state_next=0, q=0, inp0=0, att_w=0, logits=0, gi=0, gh=1, n_rows=0)
+
+    def __init__(self, P, dev, R, T, V, with_lengths=False):
+        Kd, Vd = P["key.weight"].shape[0], P["value.weight"].shape[0]
+        self.Lc, self.Dd = P["initial_state"].shape
+        self.E = P["embed.weight"].shape[0]
+        Lc, Dd, E = self.Lc, self.Dd, self.E
+        f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        self.keys, self.values, self.state, self.state_next = f(T, R, Kd), f(T, R, Vd), f(R, Lc, Dd), f(R, Lc, Dd)
+        self.q, self.inp0, self.att_w, self.logits = f(R, Kd), f(R, E + Vd), f(R, T), f(R, V)
+        self.gi, self.gh, self.drop = f(R, 3 * Dd), f(Lc, R, 3 * Dd), [f(R, Dd) for _ in range(Lc - 1)]
+        self.n_rows = torch.full((R,), T, dtype=torch.int32, device=dev) if with_lengths else None
+        self.no_dropout = (0.0, None, 0, 0, None, R * Dd)               # ops.decoder_step's drop_cfg
+
+    def fill_memory(self, P, enc2, T, W, bsz, n_host):
+        """The encoder memory of a call: keys / values once, replicated per slot; the rows' frame counts (one copy)."""
+        if n_host is not None:
+            self.n_rows.copy_(torch.tensor(n_host * W, dtype=torch.int32), non_blocking=True)
+        for buf, name in ((self.keys, "key"), (self.values, "value")):
+            D = buf.shape[2]
+            buf.view(T, W, bsz, D).copy_(_ops.gemm(enc2, P[name + ".weight"].t(), P[name + ".bias"])
+                                         .view(T, 1, bsz, D).expand(T, W, bsz, D))
+
+    def start(self, P, r, embed_bias=True):
+        """Rows [:r] at the first step: the initial state and (device paths) the all-zero first input, embed(0) = bias."""
+        _ops.broadcast_rows(P["initial_state"].contiguous().view(-1), self.state[:r].view(r, -1))
+        if embed_bias:
+            _ops.broadcast_rows(P["embed.bias"], self.inp0[:r, :self.E])
+
+    def rows(self, r):
+        """A view of the first r rows (a level of the sweep)."""
+        v = copy.copy(self)
+        for name, dim in self.ROW_DIM.items():
+            t = getattr(self, name)
+            setattr(v, name, None if t is None else t.narrow(dim, 0, r))
+        v.drop, v.no_dropout = [t[:r] for t in self.drop], self.no_dropout[:5] + (r * self.Dd,)
+        return v
+
+    def step(self, P, y_prev=None, step=0):
+        """One decoder step, state -> state_next and logits, no dropout.  y_prev None: the select / expand kernel has
+        written the embedding half of inp0 (start: the bias before the first step)."""
+        _ops.decoder_step(P, self.keys, self.values, self.state, self.state_next, y_prev, self.q, self.inp0, self.att_w,
+                          self.gi, self.gh, None, self.drop, self.logits, step, self.no_dropout, self.n_rows)
+
+
+def _control_words(dev, fields):
+    """One int32 buffer for `fields`, a list of (name, words, dtype of 4 bytes), in that order -> (the buffer, {name: its
+    words viewed as dtype}): the layout of a plan's control words is the list."""
+    ctl = torch.empty(sum(words for _, words, _ in fields), dtype=torch.int32, device=dev)
+    views, at = {}, 0
+    for name, words, dtype in fields:
+        views[name] = ctl[at:at + words].view(dtype)
+        at += words
+    return ctl, views
+
+
+def _param_key(P):
+    """The part of a plan's key that names the parameter storage a captured chain reads in place."""
+    return tuple((n, t.data_ptr(), tuple(t.shape)) for n, t in P.items() if torch.is_tensor(t))
+
+
+def _lru_plan(plans, capacity, key, build):
+    """plans[key], built on a miss (the least recently used plans leave to keep `capacity`); most recently used last."""
+    plan = plans.pop(key, None)
+    if plan is None:
+        plan = build()
+        while len(plans) >= capacity:
+            plans.pop(next(iter(plans)))
+    plans[key] = plan
+    return plan
+
+
 class Seq2SeqDecoder(torch.nn.Module):
     """Attention-based decoder for seq2seq SLU (reference models.py:504-651)."""
 
@@ -744,6 +827,30 @@ class Seq2SeqDecoder(torch.nn.Module):
         _, log_p = self.teacher_forced(encoder_outputs.transpose(0, 1), y, n)
         return log_p
 
+    def _decode_setup(self, encoder_outputs, Sy, eos, y_lengths, enc_lengths, lexicon, want_lengths, sweep=False):
+        """What infer, search and score_lexicon do before their first launch: every host-side refusal (lengths, device,
+        eos, lexicon, in that order), the detached parameters P, the encoder states time-major as (T * bsz, C) rows.
+        sweep (score_lexicon): eos is not optional and U is the lexicon's depth.
+        -> (P, n_host (the validated enc_lengths, or None), enc2, (bsz, T, U, V))."""
+        n_host = None
+        if enc_lengths is not None:
+            n_host = _host_lengths(enc_lengths, encoder_outputs.shape[0], encoder_outputs.shape[1], "encoder frames")
+        _require_device(encoder_outputs)
+        if want_lengths and eos is None:
+            raise ValueError("want_lengths needs eos: without it every hypothesis has U labels")
+        bsz, V = encoder_outputs.shape[0], len(Sy)
+        if (sweep and eos is None) or (eos is not None and not 0 <= eos < V):
+            raise ValueError("eos = %r outside [0, %d)" % (eos, V))
+        U = lexicon.max_len if sweep else 200 if y_lengths is None else max(y_lengths)
+        if lexicon is not None:
+            _check_lexicon(lexicon, eos, V, U)
+        names, tensors = self._params()
+        P = {n: t.detach() for n, t in zip(names, tensors)}
+        P["inv_scale"] = 1.0 / float(self.attention.scale_factor)
+        enc = encoder_outputs.detach().float().transpose(0, 1).contiguous()              # (T, bsz, C)
+        T = enc.shape[0]
+        return P, n_host, enc.view(T * bsz, -1), (bsz, T, U, V)
+
     def infer(self, encoder_outputs, Sy, B=4, debug=False, y_lengths=None, eos=None, want_lengths=False, enc_lengths=None,
               lexicon=None):
         """Beam search of width B for argmax_y log p(y|x) (reference models.py:559-651; B = 1 is greedy search).
@@ -780,46 +887,20 @@ class Seq2SeqDecoder(torch.nn.Module):
         label eos).  A survivor with score -inf is a dead slot: label eos, so finished from the next step on, -inf for
         good.  node follows the chosen edge; it stays for a finished source or an absent candidate.  A finished
         hypothesis' score is log p(entry | x); with at most W entries the search returns every entry, ranked."""
-        n_host = None
-        if enc_lengths is not None:
-            n_host = _host_lengths(enc_lengths, encoder_outputs.shape[0], encoder_outputs.shape[1], "encoder frames")
-        _require_device(encoder_outputs)
-        if want_lengths and eos is None:
-            raise ValueError("want_lengths needs eos: without it every hypothesis has U labels")
-        dev = encoder_outputs.device
-        W, bsz, V = B, encoder_outputs.shape[0], len(Sy)
-        if eos is not None and not 0 <= eos < V:
-            raise ValueError("eos = %r outside [0, %d)" % (eos, V))
-        U = 200 if y_lengths is None else max(y_lengths)
-        if lexicon is not None:
-            _check_lexicon(lexicon, eos, V, U)
-        names, tensors = self._params()
-        P = {n: t.detach() for n, t in zip(names, tensors)}
-        Kd, Vd = P["key.weight"].shape[0], P["value.weight"].shape[0]
-        P["inv_scale"] = 1.0 / float(self.attention.scale_factor)
-        Lc, Dd = P["initial_state"].shape
-        E = P["embed.weight"].shape[0]
-        f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        P, n_host, enc2, (bsz, T, U, V) = self._decode_setup(encoder_outputs, Sy, eos, y_lengths, enc_lengths, lexicon,
+                                                             want_lengths)
+        dev, W, R = encoder_outputs.device, B, B * bsz
         with torch.no_grad():
-            enc = encoder_outputs.detach().float().transpose(0, 1).contiguous()          # (T, bsz, C)
-            T = enc.shape[0]
-            enc2 = enc.view(T * bsz, -1)
-            # keys / values once, replicated per hypothesis: row w * bsz + b of the step batch reads utterance b
-            keys = _ops.gemm(enc2, P["key.weight"].t(), P["key.bias"]).view(T, 1, bsz, Kd).expand(T, W, bsz, Kd).reshape(T, W * bsz, Kd)
-            values = _ops.gemm(enc2, P["value.weight"].t(), P["value.bias"]).view(T, 1, bsz, Vd).expand(T, W, bsz, Vd).reshape(T, W * bsz, Vd)
-            R = W * bsz
-            # row w * bsz + b of the step batch carries utterance b's count
-            n_rows = None if n_host is None else torch.tensor(n_host * W, dtype=torch.int32).to(dev, non_blocking=True)
-            state, state_next = f(R, Lc, Dd), f(R, Lc, Dd)
-            _ops.broadcast_rows(P["initial_state"].contiguous().view(-1), state.view(R, Lc * Dd))
-            y_prev = torch.zeros(R, V, dtype=torch.float32, device=dev)
-            q, inp0, att_w, logits = f(R, Kd), f(R, E + Vd), f(R, T), f(R, V)
-            gi, gh, lse, sink = f(R, 3 * Dd), f(Lc, R, 3 * Dd), f(R), f(R)
-            drop = [f(R, Dd) for _ in range(Lc - 1)]
+            s = _StepScratch(P, dev, R, T, V, n_host is not None)
+            s.fill_memory(P, enc2, T, W, bsz, n_host)
+            s.start(P, R, embed_bias=False)
+            Lc, Dd, logits = s.Lc, s.Dd, s.logits
+            lse, sink = torch.empty(R, dtype=torch.float32, device=dev), torch.empty(R, dtype=torch.float32, device=dev)
             hyp = torch.zeros(W, bsz, U, dtype=torch.int64, device=dev)
             scores = torch.zeros(W, bsz, dtype=torch.float32, device=dev)
             cols = torch.arange(bsz, device=dev)
             zeros_y = torch.zeros(R, V, dtype=torch.float32, device=dev)
+            y_prev = zeros_y                                                            # the all-zero first input
             lengths = torch.zeros(W, bsz, dtype=torch.int32, device=dev)
             if lexicon is not None:
                 # child[n, v]: the node behind edge v of node n, or -1
@@ -828,8 +909,7 @@ class Seq2SeqDecoder(torch.nn.Module):
                 child[torch.repeat_interleave(torch.arange(lexicon.N, device=dev), off[1:] - off[:-1]), lab] = dst
                 node = torch.zeros(W, bsz, dtype=torch.int64, device=dev)
             for u in range(U):
-                _ops.decoder_step(P, keys, values, state, state_next, y_prev, q, inp0, att_w, gi, gh, None, drop, logits, u,
-                                  (0.0, None, 0, 0, None, R * Dd), n_rows)
+                s.step(P, y_prev, u)
                 _ops.logsoftmax_dot_fwd(logits, zeros_y, sink, lse)                     # lse only (y = 0)
                 if lexicon is None:
                     top_s, top_i = logits.topk(W, dim=1)                                # log_softmax keeps the order
@@ -870,15 +950,13 @@ class Seq2SeqDecoder(torch.nn.Module):
                     if bool((label == eos).all()):                                      # every utterance is done
                         hyp[:, :, u + 1:] = eos
                         break
-                state = state_next.view(W, bsz, Lc, Dd)[src, cols.unsqueeze(0)].reshape(R, Lc, Dd)
+                s.state = s.state_next.view(W, bsz, Lc, Dd)[src, cols.unsqueeze(0)].reshape(R, Lc, Dd)
                 y_prev = torch.zeros(R, V, dtype=torch.float32, device=dev)
                 y_prev.scatter_(1, label.reshape(R, 1), 1.0)
                 if debug:
                     print("step %d | best score of utterance 0: %1.2f" % (u, scores[0, 0].item()))
-            beam = torch.zeros(W, bsz, U, V, dtype=torch.float32, device=dev)
-            beam.scatter_(3, hyp.unsqueeze(3), 1.0)
+            beam = _one_hot(hyp, V)
         return (scores, beam, lengths) if want_lengths else (scores, beam)
-
 
     # steps per captured chunk of the device search: U = 200 is 25 replays; a U that is no multiple runs its last chunk to
     # the end (slu_beam_select does nothing once an utterance's counter has reached U, and the surplus decoder steps only
@@ -891,73 +969,40 @@ class Seq2SeqDecoder(torch.nn.Module):
         (with_lengths: the chunk's attention reads the plan's own (W * bsz) int32 frame counts) and lexicon (the chunk's
         slu_beam_select_lex reads the lexicon's device tables and the plan's node buffer)."""
         from slu_hip import pipeline as _pipeline
-        use_graph = _pipeline.graphs_enabled()
-        key = (bsz, T, W, U, V, eos, bool(with_lengths), str(dev), use_graph, tuple((n, t.data_ptr(), tuple(t.shape)) for n, t in P.items()
-                                                          if torch.is_tensor(t)))
+        key = (bsz, T, W, U, V, eos, bool(with_lengths), str(dev), _pipeline.graphs_enabled(), _param_key(P))
         if lexicon is not None:
             key += (lexicon.key(),)
-        plans = self.__dict__.setdefault("_search_plans", {})
-        plan = plans.pop(key, None)
-        if plan is None:
-            plan = self._build_search_plan(P, dev, bsz, T, W, U, V, use_graph, eos, with_lengths, lexicon)
-            while len(plans) >= self.SEARCH_PLANS:
-                plans.pop(next(iter(plans)))
-        plans[key] = plan                                   # most recently used last
-        return plan
 
-    def _build_search_plan(self, P, dev, bsz, T, W, U, V, use_graph, eos=None, with_lengths=False, lexicon=None):
-        from slu_hip import pipeline as _pipeline
-        Kd, Vd = P["key.weight"].shape[0], P["value.weight"].shape[0]
-        Lc, Dd = P["initial_state"].shape
-        E = P["embed.weight"].shape[0]
-        R = W * bsz
-        f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
-        i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
-        b = {"keys": f(T, R, Kd), "values": f(T, R, Vd), "state": f(R, Lc, Dd), "state_next": f(R, Lc, Dd),
-             "q": f(R, Kd), "inp0": f(R, E + Vd), "att_w": f(R, T), "logits": f(R, V), "gi": f(R, 3 * Dd),
-             "gh": f(Lc, R, 3 * Dd), "drop": [f(R, Dd) for _ in range(Lc - 1)],
-             # step counters (bsz int32), running scores (W * bsz fp32), hypothesis lengths (W * bsz int32) and the
-             # count of finished utterances (1 int32) share one buffer: ONE fill re-arms a search; a lexicon's trie nodes
-             # (W * bsz int32, zero = the root) come behind them
-             "ctl": i32(bsz + 2 * R + 1 + (R if lexicon is not None else 0)), "backptr": i32(U, W, bsz),
-             "labels": i32(U, W, bsz), "graph": None}
-        b["ctl"].zero_()
-        # the rows' encoder frame counts: a static buffer the (captured) chunk reads, filled by one copy per search
-        b["n_rows"] = torch.full((R,), T, dtype=torch.int32, device=dev) if with_lengths else None
-        b["step"], b["scores"] = b["ctl"][:bsz], b["ctl"][bsz:bsz + R].view(torch.float32).view(W, bsz)
-        b["lengths"], b["n_done"] = b["ctl"][bsz + R:bsz + 2 * R].view(W, bsz), b["ctl"][bsz + 2 * R:bsz + 2 * R + 1]
-        if eos is not None:
-            # n_done after every chunk, read behind the next chunk's launches (search)
-            b["n_done_host"] = torch.empty(-(-U // self.SEARCH_CHUNK), dtype=torch.int32, pin_memory=True)
-        fin = {} if eos is None else {"eos": eos, "lengths": b["lengths"], "n_done": b["n_done"]}
-        if lexicon is not None:
-            fin.update(trie=lexicon.tables(dev), node=b["ctl"][bsz + 2 * R + 1:].view(W, bsz))
-        embed = (P["embed.weight"], P["embed.bias"], b["inp0"])
+        def build():
+            R = W * bsz
+            s = _StepScratch(P, dev, R, T, V, with_lengths)
+            # ONE fill re-arms a search: the utterances' step counters, the running scores, the hypothesis lengths, the
+            # count of finished utterances and, with a lexicon, the slots' trie nodes (zero = the root)
+            ctl, c = _control_words(dev, [("step", bsz, torch.int32), ("scores", R, torch.float32),
+                                          ("lengths", R, torch.int32), ("n_done", 1, torch.int32)]
+                                    + ([("node", R, torch.int32)] if lexicon is not None else []))
+            ctl.zero_()
+            b = {"scratch": s, "ctl": ctl, "step": c["step"], "scores": c["scores"].view(W, bsz),
+                 "lengths": c["lengths"].view(W, bsz), "n_done": c["n_done"],
+                 "backptr": torch.empty(U, W, bsz, dtype=torch.int32, device=dev),
+                 "labels": torch.empty(U, W, bsz, dtype=torch.int32, device=dev)}
+            if eos is not None:
+                # n_done after every chunk, read behind the next chunk's launches (search)
+                b["n_done_host"] = torch.empty(-(-U // self.SEARCH_CHUNK), dtype=torch.int32, pin_memory=True)
+            fin = {} if eos is None else {"eos": eos, "lengths": b["lengths"], "n_done": b["n_done"]}
+            if lexicon is not None:
+                fin.update(trie=lexicon.tables(dev), node=c["node"].view(W, bsz))
+            embed = (P["embed.weight"], P["embed.bias"], s.inp0)
 
-        def chunk():
-            for _ in range(self.SEARCH_CHUNK):
-                # y_prev=None: slu_beam_select has written the embedding half of inp0 (the bias before the first step)
-                _ops.decoder_step(P, b["keys"], b["values"], b["state"], b["state_next"], None, b["q"], b["inp0"],
-                                  b["att_w"], b["gi"], b["gh"], None, b["drop"], b["logits"], 0,
-                                  (0.0, None, 0, 0, None, R * Dd), b["n_rows"])
-                _ops.beam_select(b["logits"], b["scores"], b["state_next"], b["state"], b["step"], b["backptr"],
-                                 b["labels"], None, embed, **fin)
-        b["chunk"] = chunk
-        if use_graph:
-            # warm-up on the capture stream (lazy initialisation happens outside the capture), on zeroed operands
-            for t in (b["keys"], b["values"], b["state"], b["inp0"]):
-                t.zero_()
-            side = torch.cuda.Stream(dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                chunk()
-            side.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with _pipeline.capture(graph, side):            # one linear chain: no forked stream inside
-                chunk()
-            torch.cuda.current_stream(dev).wait_stream(side)
-            b["graph"] = graph
-        return b
+            def chunk():
+                for _ in range(self.SEARCH_CHUNK):
+                    s.step(P)
+                    _ops.beam_select(s.logits, b["scores"], s.state_next, s.state, b["step"], b["backptr"], b["labels"],
+                                     None, embed, **fin)
+            b["chunk"] = chunk
+            b["graph"] = _pipeline.capture_chain(chunk, dev, zero=(s.keys, s.values, s.state, s.inp0))
+            return b
+        return _lru_plan(self.__dict__.setdefault("_search_plans", {}), self.SEARCH_PLANS, key, build)
 
     def search(self, encoder_outputs, Sy, B=4, y_lengths=None, want_beam=False, eos=None, want_lengths=False,
                enc_lengths=None, lexicon=None):
@@ -985,37 +1030,13 @@ class Seq2SeqDecoder(torch.nn.Module):
         lexicon: as infer's (needs eos; its longest entry must fit into U), kept by slu_beam_select_lex — bit-equal to
         infer(lexicon=...) in scores, labels and lengths.  The lexicon's tables are part of the plan's key; the trie and
         the node buffer are static buffers of the plan (node behind the counters: the one fill re-arms it too)."""
-        n_host = None
-        if enc_lengths is not None:
-            n_host = _host_lengths(enc_lengths, encoder_outputs.shape[0], encoder_outputs.shape[1], "encoder frames")
-        _require_device(encoder_outputs)
-        if want_lengths and eos is None:
-            raise ValueError("want_lengths needs eos: without it every hypothesis has U labels")
-        dev = encoder_outputs.device
-        W, bsz, V = B, encoder_outputs.shape[0], len(Sy)
-        if eos is not None and not 0 <= eos < V:
-            raise ValueError("eos = %r outside [0, %d)" % (eos, V))
-        U = 200 if y_lengths is None else max(y_lengths)
-        if lexicon is not None:
-            _check_lexicon(lexicon, eos, V, U)
-        names, tensors = self._params()
-        P = {n: t.detach() for n, t in zip(names, tensors)}
-        P["inv_scale"] = 1.0 / float(self.attention.scale_factor)
-        Kd, Vd = P["key.weight"].shape[0], P["value.weight"].shape[0]
-        E = P["embed.weight"].shape[0]
+        P, n_host, enc2, (bsz, T, U, V) = self._decode_setup(encoder_outputs, Sy, eos, y_lengths, enc_lengths, lexicon,
+                                                             want_lengths)
+        dev, W = encoder_outputs.device, B
         with torch.no_grad():
-            enc = encoder_outputs.detach().float().transpose(0, 1).contiguous()          # (T, bsz, C)
-            T = enc.shape[0]
-            enc2 = enc.view(T * bsz, -1)
             p = self._search_plan(P, dev, bsz, T, W, U, V, eos, n_host is not None, lexicon)
-            R = W * bsz
-            if n_host is not None:
-                p["n_rows"].copy_(torch.tensor(n_host * W, dtype=torch.int32), non_blocking=True)
-            # set-up as in infer: keys / values once, replicated per hypothesis; initial state; all-zero first input
-            p["keys"].view(T, W, bsz, Kd).copy_(_ops.gemm(enc2, P["key.weight"].t(), P["key.bias"]).view(T, 1, bsz, Kd).expand(T, W, bsz, Kd))
-            p["values"].view(T, W, bsz, Vd).copy_(_ops.gemm(enc2, P["value.weight"].t(), P["value.bias"]).view(T, 1, bsz, Vd).expand(T, W, bsz, Vd))
-            _ops.broadcast_rows(P["initial_state"].contiguous().view(-1), p["state"].view(R, -1))
-            _ops.broadcast_rows(P["embed.bias"], p["inp0"][:, :E])                        # embed(0) = bias
+            p["scratch"].fill_memory(P, enc2, T, W, bsz, n_host)
+            p["scratch"].start(P, W * bsz)
             p["ctl"].zero_()                                            # step counters, scores, lengths, n_done[, node]
             labels = torch.empty(W, bsz, U, dtype=torch.int64, device=dev)
             beam = torch.empty(W, bsz, U, V, dtype=torch.float32, device=dev) if want_beam else None
@@ -1047,71 +1068,40 @@ class Seq2SeqDecoder(torch.nn.Module):
         """Static buffers (+ the captured sweep) of one score_lexicon shape, attention kind and lexicon, sized from
         lexicon.width: the widest level's rows are width * bsz (DESIGN.md section 7 has the byte count)."""
         from slu_hip import pipeline as _pipeline
-        use_graph = _pipeline.graphs_enabled()
-        key = (bsz, T, V, eos, bool(with_lengths), str(dev), use_graph, lexicon.key(),
-               tuple((n, t.data_ptr(), tuple(t.shape)) for n, t in P.items() if torch.is_tensor(t)))
-        plans = self.__dict__.setdefault("_lexicon_plans", {})
-        plan = plans.pop(key, None)
-        if plan is None:
-            plan = self._build_lexicon_plan(P, dev, bsz, T, V, use_graph, eos, with_lengths, lexicon)
-            while len(plans) >= self.LEXICON_PLANS:
-                plans.pop(next(iter(plans)))
-        plans[key] = plan                                   # most recently used last
-        return plan
+        key = (bsz, T, V, eos, bool(with_lengths), str(dev), _pipeline.graphs_enabled(), lexicon.key(), _param_key(P))
 
-    def _build_lexicon_plan(self, P, dev, bsz, T, V, use_graph, eos, with_lengths, lexicon):
-        from slu_hip import pipeline as _pipeline
-        Kd, Vd = P["key.weight"].shape[0], P["value.weight"].shape[0]
-        Lc, Dd = P["initial_state"].shape
-        E = P["embed.weight"].shape[0]
-        _, inner, _, width = lexicon.levels()
-        R, M = width * bsz, len(lexicon)
-        f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
-        # state: the level's rows; state_next: the step's output, which slu_trie_expand scatters back into state for the
-        # next level (the step has read state by then).  scores: the levels alternate between the two halves.
-        b = {"keys": f(T, R, Kd), "values": f(T, R, Vd), "state": f(R, Lc, Dd), "state_next": f(R, Lc, Dd),
-             "q": f(R, Kd), "inp0": f(R, E + Vd), "att_w": f(R, T), "logits": f(R, V), "gi": f(R, 3 * Dd),
-             "gh": f(Lc, R, 3 * Dd), "drop": [f(R, Dd) for _ in range(Lc - 1)], "scores": f(2, R),
-             "entry_logp": f(bsz, M), "log_z": f(bsz), "best": torch.empty(bsz, dtype=torch.int32, device=dev),
-             "graph": None, "width": width}
-        b["n_rows"] = torch.full((R,), T, dtype=torch.int32, device=dev) if with_lengths else None
-        trie = lexicon.tables(dev)
-        slot, inner_dev = lexicon.level_tables(dev)
-        levels = [(d, len(inner[d]), len(inner[d + 1])) for d in range(lexicon.max_len) if inner[d]]
-        b["row_steps"] = sum(n for _, n, _ in levels) * bsz
+        def build():
+            _, inner, _, width = lexicon.levels()
+            R, M = width * bsz, len(lexicon)
+            f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+            # scratch.state: the level's rows; state_next: the step's output, which slu_trie_expand scatters back into state
+            # for the next level (the step has read state by then).  scores: the levels alternate between the two halves.
+            s = _StepScratch(P, dev, R, T, V, with_lengths)
+            b = {"scratch": s, "scores": f(2, R), "entry_logp": f(bsz, M), "log_z": f(bsz),
+                 "best": torch.empty(bsz, dtype=torch.int32, device=dev), "width": width}
+            trie = lexicon.tables(dev)
+            slot, inner_dev = lexicon.level_tables(dev)
+            # (depth, this level's rows, the next level's rows or None behind the last inner level)
+            levels = [(d, s.rows(len(inner[d]) * bsz), s.rows(len(inner[d + 1]) * bsz) if inner[d + 1] else None)
+                      for d in range(lexicon.max_len) if inner[d]]
+            b["row_steps"] = sum(lv.state.shape[0] for _, lv, _ in levels)
 
-        def sweep():
-            for d, n_in, n_out in levels:
-                r = n_in * bsz
-                # y_prev=None: slu_trie_expand has written the embedding half of inp0 (the bias before the first level)
-                _ops.decoder_step(P, b["keys"][:, :r], b["values"][:, :r], b["state"][:r], b["state_next"][:r], None,
-                                  b["q"][:r], b["inp0"][:r], b["att_w"][:r], b["gi"][:r], b["gh"][:, :r], None,
-                                  [t[:r] for t in b["drop"]], b["logits"][:r], 0, (0.0, None, 0, 0, None, r * Dd),
-                                  None if b["n_rows"] is None else b["n_rows"][:r])
-                nxt = {}
-                if n_out:
-                    ro = n_out * bsz
-                    nxt = dict(score_out=b["scores"][(d + 1) % 2, :ro], state_out=b["state"][:ro],
-                               embed=(P["embed.weight"], P["embed.bias"], b["inp0"][:ro]))
-                _ops.trie_expand(b["logits"][:r], b["state_next"][:r], b["scores"][d % 2, :r], inner_dev[d], trie, slot, eos,
-                                 b["entry_logp"], **nxt)
-            _ops.trie_finish(b["entry_logp"], b["best"], b["log_z"])
-        b["sweep"] = sweep
-        if use_graph:
-            # warm-up on the capture stream (lazy initialisation happens outside the capture), on zeroed operands
-            for t in (b["keys"], b["values"], b["state"], b["inp0"], b["scores"]):
-                t.zero_()
-            side = torch.cuda.Stream(dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                sweep()
-            side.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with _pipeline.capture(graph, side):            # one linear chain: no forked stream inside
-                sweep()
-            torch.cuda.current_stream(dev).wait_stream(side)
-            b["graph"] = graph
-        return b
+            def sweep():
+                for d, lv, nx in levels:
+                    r = lv.state.shape[0]
+                    lv.step(P)
+                    nxt = {}
+                    if nx is not None:
+                        ro = nx.state.shape[0]
+                        nxt = dict(score_out=b["scores"][(d + 1) % 2, :ro], state_out=nx.state,
+                                   embed=(P["embed.weight"], P["embed.bias"], nx.inp0))
+                    _ops.trie_expand(lv.logits, lv.state_next, b["scores"][d % 2, :r], inner_dev[d], trie, slot, eos,
+                                     b["entry_logp"], **nxt)
+                _ops.trie_finish(b["entry_logp"], b["best"], b["log_z"])
+            b["sweep"] = sweep
+            b["graph"] = _pipeline.capture_chain(sweep, dev, zero=(s.keys, s.values, s.state, s.inp0, b["scores"]))
+            return b
+        return _lru_plan(self.__dict__.setdefault("_lexicon_plans", {}), self.LEXICON_PLANS, key, build)
 
     def score_lexicon(self, encoder_outputs, Sy, lexicon, eos, enc_lengths=None):
         """Exact decoding over a closed set (include/slu_hip.h, slu_trie_expand): log p(entry | x) of
@@ -1127,34 +1117,13 @@ class Seq2SeqDecoder(torch.nn.Module):
         lexicon.key()), reading the parameters in place; bit-equal to the eager sweep.
         enc_lengths: as search's — the attention is ops.attention_len_fwd on the plan's per-row int32 buffer, which one
         copy per call fills."""
-        n_host = None
-        if enc_lengths is not None:
-            n_host = _host_lengths(enc_lengths, encoder_outputs.shape[0], encoder_outputs.shape[1], "encoder frames")
-        _require_device(encoder_outputs)
-        dev = encoder_outputs.device
-        bsz, V = encoder_outputs.shape[0], len(Sy)
-        if eos is None or not 0 <= eos < V:
-            raise ValueError("eos = %r outside [0, %d)" % (eos, V))
-        _check_lexicon(lexicon, eos, V, lexicon.max_len)
-        names, tensors = self._params()
-        P = {n: t.detach() for n, t in zip(names, tensors)}
-        P["inv_scale"] = 1.0 / float(self.attention.scale_factor)
-        Kd, Vd = P["key.weight"].shape[0], P["value.weight"].shape[0]
-        E = P["embed.weight"].shape[0]
+        P, n_host, enc2, (bsz, T, _, V) = self._decode_setup(encoder_outputs, Sy, eos, None, enc_lengths, lexicon, False,
+                                                             sweep=True)
         with torch.no_grad():
-            enc = encoder_outputs.detach().float().transpose(0, 1).contiguous()          # (T, bsz, C)
-            T = enc.shape[0]
-            enc2 = enc.view(T * bsz, -1)
-            p = self._lexicon_plan(P, dev, bsz, T, V, eos, n_host is not None, lexicon)
-            W = p["width"]
-            if n_host is not None:
-                p["n_rows"].copy_(torch.tensor(n_host * W, dtype=torch.int32), non_blocking=True)
-            # set-up as in search: keys / values once, replicated per slot; the root's rows get the initial state, the
-            # all-zero first input and score 0
-            p["keys"].view(T, W, bsz, Kd).copy_(_ops.gemm(enc2, P["key.weight"].t(), P["key.bias"]).view(T, 1, bsz, Kd).expand(T, W, bsz, Kd))
-            p["values"].view(T, W, bsz, Vd).copy_(_ops.gemm(enc2, P["value.weight"].t(), P["value.bias"]).view(T, 1, bsz, Vd).expand(T, W, bsz, Vd))
-            _ops.broadcast_rows(P["initial_state"].contiguous().view(-1), p["state"][:bsz].view(bsz, -1))
-            _ops.broadcast_rows(P["embed.bias"], p["inp0"][:bsz, :E])                     # embed(0) = bias
+            p = self._lexicon_plan(P, encoder_outputs.device, bsz, T, V, eos, n_host is not None, lexicon)
+            p["scratch"].fill_memory(P, enc2, T, p["width"], bsz, n_host)
+            # the root's rows only: the initial state, the all-zero first input and score 0
+            p["scratch"].start(P, bsz)
             p["scores"][0, :bsz].zero_()
             if p["graph"] is not None:
                 p["graph"].replay()
@@ -2325,6 +2294,19 @@ class Model(torch.nn.Module):
         lexicon_exact_enabled()                          # SLU_LEXICON_EXACT=1 without SLU_BEAM_LEXICON=1: refused here
         return kw
 
+    def _open_decode(self, x, lengths, mode=False, need_lexicon=None):
+        """What decode_intents, exact_match, decode_nbest and lexicon_scores run in front of their decoder: the knob checks
+        (mode: SLU_BEAM_SEARCH's too; need_lexicon: the caller's name, which refuses a model without a stored lexicon) —
+        a bad knob or a missing lexicon is an error before any launch — then the encoder.
+        -> (the search's eos / lexicon arguments (_beam_eos), h time-major and contiguous, host lengths or None)."""
+        if mode:
+            beam_search_mode()
+        kw = self._beam_eos()
+        if need_lexicon and self.lexicon is None:
+            raise ValueError("%s: no lexicon, call Model.set_lexicon(strings) first" % need_lexicon)
+        h, n_host, _ = self._encode(x, lengths)
+        return kw, h.contiguous(), n_host
+
     def _search(self, h, enc_lengths, want_beam):
         """The width-4 beam search over h (time-major encoder states; enc_lengths: their valid frames, or None) with the
         books where SLU_BEAM_SEARCH keeps them -> (scores, labels (4, B, U), beam one-hot): "host" (Seq2SeqDecoder.infer)
@@ -2335,11 +2317,7 @@ class Model(torch.nn.Module):
         kw = dict(self._beam_eos(), B=4)                 # the dense calls' arguments are what they always were
         if lexicon_exact_enabled():                      # no search: every entry scored, the 4 best read off
             scores, labels = self._exact_top(h, enc_lengths, 4, pad=True)
-            beam = None
-            if want_beam:
-                beam = torch.zeros(labels.shape + (len(self.Sy_intent),), dtype=torch.float32, device=labels.device)
-                beam.scatter_(3, labels.unsqueeze(3), 1.0)
-            return scores, labels, beam
+            return scores, labels, _one_hot(labels, len(self.Sy_intent)) if want_beam else None
         if enc_lengths is not None:
             kw["enc_lengths"] = enc_lengths
         if mode == "host":
@@ -2364,10 +2342,7 @@ class Model(torch.nn.Module):
         log-posterior over the lexicon.  lengths: as decode_nbest (SLU_MASK_SEQ2SEQ=1); the knobs are checked as there."""
         if not self.seq2seq:
             raise ValueError("lexicon_scores: the entries are scored by the seq2seq decoder")
-        self._beam_eos()
-        if self.lexicon is None:
-            raise ValueError("lexicon_scores: no lexicon, call Model.set_lexicon(strings) first")
-        h, n_host, _ = self._encode(x, lengths)
+        _, h, n_host = self._open_decode(x, lengths, need_lexicon="lexicon_scores")
         return self._exact_sweep(h, n_host)
 
     def lexicon_posteriors(self, x, lengths=None):
@@ -2417,19 +2392,17 @@ class Model(torch.nn.Module):
             # SLU_LEXICON_EXACT=1: the min(n, M) best entries of the sweep with their log p(entry | x); no beam, no cap
             if n < 1:
                 raise ValueError("decode_nbest: n = %r outside [1, the lexicon's size]" % (n,))
-            self._beam_eos()
-            h, n_host, _ = self._encode(x, lengths)
+            _, h, n_host = self._open_decode(x, lengths)
             scores, labels = self._exact_top(h, n_host, n)
             scores, labels = scores.t().tolist(), labels.transpose(0, 1).tolist()
             return [[(_labels_to_string(row[:row.index(self.lexicon.eos) + 1], self.Sy_intent), s)
                      for row, s in zip(labels[b], scores[b])] for b in range(len(scores))]
         if not 1 <= n <= W:
             raise ValueError("decode_nbest: n = %r outside [1, %d]" % (n, W))
-        fin = self._beam_eos()
-        h, n_host, _ = self._encode(x, lengths)
+        fin, h, n_host = self._open_decode(x, lengths)
         if n_host is not None:
             fin = dict(fin, enc_lengths=n_host)
-        out = self.decoder.search(h.contiguous().transpose(0, 1), self.Sy_intent, B=W, want_lengths="eos" in fin, **fin)
+        out = self.decoder.search(h.transpose(0, 1), self.Sy_intent, B=W, want_lengths="eos" in fin, **fin)
         scores, labels = out[0], out[1]
         U = labels.shape[2]
         lengths = out[2] if "eos" in fin else torch.full_like(scores, U, dtype=torch.int32)
@@ -2450,11 +2423,9 @@ class Model(torch.nn.Module):
         host."""
         if not self.seq2seq:
             raise ValueError("exact_match: the seq2seq decoder's best hypothesis against its target")
-        beam_search_mode()
-        self._beam_eos()
+        _, h, n_host = self._open_decode(x, lengths, mode=True)
         eos = self.Sy_intent.index("<eos>")
-        h, n_host, _ = self._encode(x, lengths)
-        _, labels, beam = self._search(h.contiguous(), n_host, want_beam=False)
+        _, labels, beam = self._search(h, n_host, want_beam=False)
         best = labels[0] if labels is not None else beam[0].max(dim=2)[1]             # (B, U of the search)
         y = y.to(best.device)
         y = (y.max(dim=2)[1] if y.dim() == 3 else y).long()
@@ -2476,10 +2447,8 @@ class Model(torch.nn.Module):
             inverse = [{idx: value for value, idx in self.Sy_intent[slot].items()} for slot in self.Sy_intent]
             return [[inverse[s][int(row[s])] for s in range(len(inverse)) if int(row[s]) in inverse[s]]
                     for row in pred]
-        beam_search_mode()               # a bad value of the knob is an error before any launch
-        self._beam_eos()
-        h, n_host, _ = self._encode(x, lengths)
-        _, labels, beam = self._search(h.contiguous(), n_host, want_beam=False)
+        _, h, n_host = self._open_decode(x, lengths, mode=True)
+        _, labels, beam = self._search(h, n_host, want_beam=False)
         if labels is not None:
             return [_labels_to_string(row, self.Sy_intent) for row in labels[0].cpu().tolist()]
         beam = beam.cpu()

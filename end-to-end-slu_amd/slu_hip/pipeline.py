@@ -41,6 +41,27 @@ def capture(graph, stream):
         if was:
             gc.enable()
 
+
+def capture_chain(fn, dev, zero=()):
+    """The linear-chain case of capture: fn launches on ONE stream, forks nothing and arms no guard -> the graph of one
+    call of fn, or None with SLU_GRAPHS=0.  fn runs once before the capture, on the capture stream and on the `zero`
+    tensors zeroed (its operands: lazy initialisation happens outside the capture, on finite values)."""
+    if not graphs_enabled():
+        return None
+    for t in zero:
+        t.zero_()
+    side = torch.cuda.Stream(dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        fn()
+    side.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with capture(graph, side):
+        fn()
+    torch.cuda.current_stream(dev).wait_stream(side)
+    return graph
+
+
 def cu_split(device=None):
     """CUs [0, n) of the device are reserved for the trainable part of the step, the look-ahead
     super-batches get the rest.  Without the partition the big frozen-prefix kernels keep every CU

@@ -294,6 +294,32 @@ def test_search_graph_equals_eager_and_keeps_no_state(models_mod, monkeypatch):
     assert len(dec._search_plans) <= dec.SEARCH_PLANS
 
 
+def test_search_reuses_the_plans_buffers(models_mod, monkeypatch):
+    """The captured chunk reads the plan's buffers by address: a second search of the same shape, on other encoder values,
+    gets the same plan with every buffer where it was, and the new values' result."""
+    monkeypatch.setenv("SLU_GRAPHS", "1")
+    dec, labels = reference_size_decoder(models_mod, 41)
+    g = torch.Generator().manual_seed(42)
+    enc_a = torch.randn(8, 19, 256, generator=g).cuda()
+    enc_b = torch.randn(8, 19, 256, generator=g).cuda()
+    yl = [12] * 8                                                    # no multiple of the chunk
+
+    def where(plan):
+        s = plan["scratch"]
+        return [id(plan)] + [t.data_ptr() for t in (s.keys, s.values, s.state, s.inp0, plan["ctl"])]
+
+    dec.search(enc_a, labels, B=4, y_lengths=yl)
+    (plan,) = dec._search_plans.values()
+    assert plan["graph"] is not None
+    before = where(plan)
+    s_b, lab_b = dec.search(enc_b, labels, B=4, y_lengths=yl)
+    (plan_b,) = dec._search_plans.values()
+    assert where(plan_b) == before
+    s_h, beam = dec.infer(enc_b, labels, B=4, y_lengths=yl)
+    assert torch.equal(s_b, s_h) and torch.equal(lab_b, beam.max(dim=3)[1])
+    assert not torch.equal(lab_b, dec.infer(enc_a, labels, B=4, y_lengths=yl)[1].max(dim=3)[1])
+
+
 # ------------------------------------------------------------------------------------------------
 # (c) against the reference's own beam
 # ------------------------------------------------------------------------------------------------
