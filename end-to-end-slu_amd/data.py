@@ -182,7 +182,7 @@ def pcm16_batches():
     first stage computes on sample / 32768 (slu_hip.ops.PCM16_SCALE), which is exactly the float32 value the default
     loaders (and the reference's, data.py:273-293) produce, so losses and parameters are bit-identical.  Off by default:
     code that consumes `dataset.loader` directly keeps seeing the reference's float32 waveforms."""
-    return os.environ.get("SLU_PCM16_BATCHES", "0") == "1"
+    return _knobs.get("SLU_PCM16_BATCHES")
 
 
 def read_wav(path, keep_pcm16=False):
@@ -231,13 +231,13 @@ def one_hot(letters, S):
 
 def mask_padding_enabled():
     """SLU_MASK_PADDING: "0" (default) — batches are (x, y); "1" — CollateWavsSLU adds the per-utterance sample counts."""
-    return _knobs.flag("SLU_MASK_PADDING")
+    return _knobs.get("SLU_MASK_PADDING")
 
 
 def mask_asr_enabled():
     """SLU_MASK_ASR: "0" (default) — ASR batches are (x, y_phoneme, y_word), also under SLU_MASK_PADDING=1; "1" —
     CollateWavsASR adds the snippets' own sample counts.  Needs SLU_MASK_PADDING=1."""
-    on = _knobs.flag("SLU_MASK_ASR")
+    on = _knobs.get("SLU_MASK_ASR")
     if on and not mask_padding_enabled():
         raise ValueError("SLU_MASK_ASR=1 needs SLU_MASK_PADDING=1: the lengths come from the collate function")
     return on
@@ -247,10 +247,10 @@ def asr_ctc_enabled():
     """SLU_ASR_CTC: "0" (default) — ASR batches carry one label per frame (forced alignments); "1" — they carry label
     SEQUENCES and PretrainedModel trains its heads by CTC (models.asr_ctc_enabled).  Needs SLU_MASK_PADDING=1,
     SLU_MASK_ASR=1 and SLU_MASK_TRAIN=1: CTC needs every utterance's length, in training and in evaluation."""
-    on = _knobs.flag("SLU_ASR_CTC")
+    on = _knobs.get("SLU_ASR_CTC")
     if on:
         for name in ("SLU_MASK_PADDING", "SLU_MASK_ASR", "SLU_MASK_TRAIN"):
-            if not _knobs.flag(name):
+            if not _knobs.get(name):
                 raise ValueError("SLU_ASR_CTC=1 needs %s=1: CTC needs the utterances' lengths in training and in evaluation"
                                  % name)
     return on
@@ -258,7 +258,7 @@ def asr_ctc_enabled():
 
 def ctc_max_seconds():
     """SLU_CTC_MAX_SECONDS (default 20): TranscriptASRDataset skips utterances longer than this."""
-    v = os.environ.get("SLU_CTC_MAX_SECONDS", "20")
+    v = _knobs.get("SLU_CTC_MAX_SECONDS")
     try:
         sec = float(v)
     except ValueError:
@@ -307,7 +307,7 @@ class CollateWavsSLU:
         # data falls into a few batch shapes (the look-ahead super-batches and hipGraphs are per shape).
         # Off by default: the extra trailing zeros are seen by the recurrences, i.e. it is not the
         # reference's batch any more.
-        self.pad_multiple = int(os.environ.get("SLU_PAD_TO_MULTIPLE", "0")) if pad_multiple is None else pad_multiple
+        self.pad_multiple = _knobs.get("SLU_PAD_TO_MULTIPLE") if pad_multiple is None else pad_multiple
         # Opt-in (SLU_MASK_PADDING=1): also return the utterances' own sample counts, (x, y, lengths int32 (B)) — taken
         # before the rounding above — so that evaluation can run padding-invariant (Model.eval_group(lengths=...):
         # every utterance's logits are those of the utterance alone, whatever it was batched with).  The training loops
@@ -346,10 +346,8 @@ def _world():
 def _loader_workers():
     """The reference starts one DataLoader worker per core (data.py:261); on a 256-thread MI355X host
     that is all start-up cost, so the default is capped (SLU_DATA_WORKERS overrides, 0 = in-process)."""
-    env = os.environ.get("SLU_DATA_WORKERS")
-    if env is not None:
-        return int(env)
-    return min(16, os.cpu_count() or 1)
+    n = _knobs.get("SLU_DATA_WORKERS")
+    return min(16, os.cpu_count() or 1) if n is None else n
 
 
 class ForkSafeDataLoader(torch.utils.data.DataLoader):
@@ -459,7 +457,7 @@ class SLUDataset(torch.utils.data.Dataset):
         # validation / test stay whole on every rank, so their metrics are the single-process ones.
         rank, world = _world() if shard else (0, 1)
         seed = getattr(config, "seed", 0)
-        if os.environ.get("SLU_BUCKET_BATCHES", "0") == "1" and collate.pad_multiple > 1:
+        if _knobs.get("SLU_BUCKET_BATCHES") and collate.pad_multiple > 1:
             lengths = [wav_num_samples(p) for p in self._paths] * self.upsample_factor
             self.loader = ForkSafeDataLoader(
                 self, num_workers=_loader_workers(), collate_fn=collate, pin_memory=pin,

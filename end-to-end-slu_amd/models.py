@@ -152,14 +152,8 @@ def frozen_math_scope(guard):
 # the split is EXACT), six bf16 MFMA products per fp32 product (hi*hi, hi*mid, mid*hi, mid*mid, hi*lo, lo*hi; what is
 # dropped is below 2^-24 |a b| per product, the size of one fp32 rounding), fp32 accumulation.  The 22-bit f16x2 scheme
 # under its range guard ("auto") is faster and opt-in: narrower than the reference's arithmetic, it is not the default.
-DEFAULT_FROZEN_MATH = "bf16x3"
-
-
 def frozen_math_mode():
-    mode = os.environ.get("SLU_FROZEN_MATH", DEFAULT_FROZEN_MATH)
-    if mode not in _FROZEN_MATH:
-        raise ValueError("SLU_FROZEN_MATH=%r: expected one of %s" % (mode, sorted(_FROZEN_MATH)))
-    return mode
+    return _knobs.get("SLU_FROZEN_MATH")
 
 
 def contraction_nsplit(frozen):
@@ -176,7 +170,7 @@ def contraction_nsplit(frozen):
       1  plain bf16 operands, fp32 accumulation and gate math — every layer when SLU_DTYPE=bf16
          (BASELINE configs[4]: weights and activations enter every forward contraction and the data-gradient
          contractions as bf16 — ops.bf16_mode; weight gradients, master weights and Adam stay fp32)."""
-    if os.environ.get("SLU_DTYPE", "f32") == "bf16":
+    if _ops.bf16_mode():
         return 1
     if frozen:
         mode = frozen_math_mode()
@@ -189,11 +183,16 @@ def contraction_nsplit(frozen):
 _FROZEN_MATH = {"auto": None, "f16x2": 2, "bf16x3": 3, "fp32": 0}
 
 
+def _guard_decides():
+    """Is the arithmetic of frozen stages left to the range guard (SLU_FROZEN_MATH=auto, and not SLU_DTYPE=bf16)?"""
+    return frozen_math_mode() == "auto" and not _ops.bf16_mode()
+
+
 def guarded_frozen_nsplit(model=None):
     """The split scheme of frozen stages INSIDE a guarded evaluation (what the look-ahead pipeline and the eager entry
     points run): the default mode gives f16x2 unless `model` (a PretrainedModel / Model) is pinned to bf16x3 or its
     weights are out of range; explicit modes as set.  For reports (bench.py) and tests."""
-    if frozen_math_mode() != "auto" or os.environ.get("SLU_DTYPE", "f32") == "bf16":
+    if not _guard_decides():
         return contraction_nsplit(True)
     pm = getattr(model, "pretrained_model", model)
     return 2 if (pm is None or pm.f16x2_allowed()) else 3
@@ -203,7 +202,7 @@ def beam_search_mode():
     """SLU_BEAM_SEARCH: where the seq2seq decoder's beam search keeps its books when Model.predict_intents / decode_intents
     decode: "device" (default) — Seq2SeqDecoder.search, slu_beam_select after every step and one slu_beam_backtrack;
     "host" — Seq2SeqDecoder.infer, torch bookkeeping as in the reference.  Same hypotheses, same scores."""
-    return _knobs.one_of("SLU_BEAM_SEARCH", "device", ("device", "host"))
+    return _knobs.get("SLU_BEAM_SEARCH")
 
 
 def beam_eos_enabled():
@@ -211,7 +210,7 @@ def beam_eos_enabled():
     expanded for all U steps and the log-probabilities of what follows <eos> count; "1" — hypotheses that have emitted
     <eos> are finished (the rule in Seq2SeqDecoder.infer): Model.predict_intents / decode_intents / decode_nbest pass
     eos = Sy_intent.index("<eos>") to the search SLU_BEAM_SEARCH selects, which stops once every utterance is done."""
-    return _knobs.flag("SLU_BEAM_EOS")
+    return _knobs.get("SLU_BEAM_EOS")
 
 
 def beam_lexicon_enabled():
@@ -219,7 +218,7 @@ def beam_lexicon_enabled():
     lexicon or not; "1" (needs SLU_BEAM_EOS=1: the entries end in <eos>) — Model.predict_intents / decode_intents /
     decode_nbest / exact_match pass the stored lexicon to the search SLU_BEAM_SEARCH selects, which then decodes only the
     lexicon's strings (include/slu_hip.h, slu_beam_select_lex); without a stored lexicon they raise ValueError."""
-    on = _knobs.flag("SLU_BEAM_LEXICON")
+    on = _knobs.get("SLU_BEAM_LEXICON")
     if on and not beam_eos_enabled():
         raise ValueError("SLU_BEAM_LEXICON=1 needs SLU_BEAM_EOS=1: a lexicon's entries end in <eos>, and only finished "
                          "hypotheses stop there")
@@ -231,7 +230,7 @@ def lexicon_exact_enabled():
     Model.predict_intents / decode_intents / decode_nbest / exact_match score EVERY entry of the lexicon instead of
     searching it with a beam (Seq2SeqDecoder.score_lexicon; include/slu_hip.h, slu_trie_expand): the best hypothesis is the
     entry with the highest log p(entry | x), guaranteed, and decode_nbest is no longer capped at the beam width."""
-    on = _knobs.flag("SLU_LEXICON_EXACT")
+    on = _knobs.get("SLU_LEXICON_EXACT")
     if on and not beam_lexicon_enabled():
         raise ValueError("SLU_LEXICON_EXACT=1 needs SLU_BEAM_LEXICON=1 (and SLU_BEAM_EOS=1): the sweep scores the entries of "
                          "the lexicon the constrained search decodes")
@@ -242,21 +241,21 @@ def mask_train_cnn_enabled():
     """SLU_MASK_TRAIN_CNN: "0" (default) — Model.forward(lengths=...) refuses a trainable CNN block; "1" — such a block
     runs length-aware inside autograd (ops.SincBlockLenFn / ConvBlockLenFn), so masked training goes on when the unfreezing
     reaches the convolutions, or with nothing frozen."""
-    return _knobs.flag("SLU_MASK_TRAIN_CNN")
+    return _knobs.get("SLU_MASK_TRAIN_CNN")
 
 
 def mask_seq2seq_enabled():
     """SLU_MASK_SEQ2SEQ: "0" (default) — every lengths=... call refuses a seq2seq model; "1" — the intent encoder runs
     length-aware and the decoder's attention ranges over every utterance's own frames (ops.attention_len_fwd / _bwd):
     Model.forward(lengths=...), eval_group, predict_intents, decode_intents and decode_nbest take lengths for seq2seq models."""
-    return _knobs.flag("SLU_MASK_SEQ2SEQ")
+    return _knobs.get("SLU_MASK_SEQ2SEQ")
 
 
 def mask_augment_enabled():
     """SLU_MASK_AUGMENT: "0" (default) — a masked training step (Model.forward(lengths=...) in train() mode) refuses a model
     with augment=True; "1" — its waveforms pass through the length-taking augmentation kernels (_enter_len) and the
     stages run on the lengths behind them.  training.mask_augment_enabled adds the Trainer's rule: 1 needs SLU_MASK_TRAIN=1."""
-    return _knobs.flag("SLU_MASK_AUGMENT")
+    return _knobs.get("SLU_MASK_AUGMENT")
 
 
 def asr_ctc_enabled():
@@ -264,7 +263,7 @@ def asr_ctc_enabled():
     "1" — a PretrainedModel built under it has CTC heads (DESIGN.md section 7 "CTC pre-training"): one more output per
     Linear, the blank, LAST; forward takes label SEQUENCES and needs lengths.  Read at construction only.  data.py adds
     the data side's rule: 1 needs SLU_MASK_PADDING=1, SLU_MASK_ASR=1 and SLU_MASK_TRAIN=1."""
-    return _knobs.flag("SLU_ASR_CTC")
+    return _knobs.get("SLU_ASR_CTC")
 
 
 def mask_frozen_math_mode():
@@ -273,7 +272,7 @@ def mask_frozen_math_mode():
     gradient runs its convolution / input projection / recurrence on the split-precision kernels (ops.wconv_fwd_bf16,
     ops.gemm_a32, ops.gru_seq_fwd_len_bf16) where they take its shape, else its fp32 form.  A knob of its own: it does not
     follow SLU_FROZEN_MATH, and f16x2 / auto are refused (the range guard is not wired through the length-aware path)."""
-    return _knobs.one_of("SLU_MASK_FROZEN_MATH", "fp32", ("fp32", "bf16x3"))
+    return _knobs.get("SLU_MASK_FROZEN_MATH")
 
 
 def _refuse_seq2seq_lengths():
@@ -1632,7 +1631,7 @@ class PretrainedModel(torch.nn.Module):
         """May a guarded evaluation of this model's frozen stages use f16x2?  Default mode, not pinned to bf16x3 by an
         earlier range violation, frozen weights inside fp16's comfortable range (checked once per weight version: one
         launch + one read-back, never under capture)."""
-        if frozen_math_mode() != "auto" or os.environ.get("SLU_DTYPE", "f32") == "bf16":
+        if not _guard_decides():
             return False
         if getattr(self, "_f16x2_pin", None) is not None:
             return False

@@ -23,6 +23,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import knobs as _knobs
+
 
 def world():
     if dist.is_available() and dist.is_initialized():
@@ -34,7 +36,7 @@ def _single_rank_dp():
     """Test aid: SLU_DP_SINGLE=1 treats an initialised ONE-rank process group as data parallel (bucket packing, the
     collective, 1/N in Adam with N = 1), which exercises the whole data-parallel step — including an RCCL all-reduce
     captured inside the step's hipGraph — on a single-GPU box."""
-    return os.environ.get("SLU_DP_SINGLE", "0") == "1"
+    return _knobs.get("SLU_DP_SINGLE")
 
 
 def data_parallel():
@@ -50,13 +52,14 @@ def init_from_env(backend=None):
     local = int(os.environ.get("LOCAL_RANK", "0"))
     # Test aid: SLU_DIST_BACKEND=gloo SLU_LOCAL_DEVICE=0 runs several ranks on ONE GPU (RCCL refuses
     # duplicate devices), which exercises the whole multi-process step path on a single-GPU box.
-    local = int(os.environ.get("SLU_LOCAL_DEVICE", local))
+    if _shared_device():
+        local = _knobs.get("SLU_LOCAL_DEVICE")
     if (ws > 1 or _single_rank_dp()) and not (dist.is_available() and dist.is_initialized()):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29500")
         if backend is None:
             # gloo: the CONTROL plane only (module docstring); the gradient collectives run on the C ABI's communicators
-            backend = os.environ.get("SLU_DIST_BACKEND") or "gloo"
+            backend = _knobs.get("SLU_DIST_BACKEND") or "gloo"       # (empty counts as unset)
         if backend == "nccl":
             torch.cuda.set_device(local)
             dist.init_process_group(backend, rank=rank, world_size=ws, device_id=torch.device("cuda", local))
@@ -192,10 +195,10 @@ class IpcComm:
         from . import lib as _lib
         self._lib, self._L = _lib, _lib.load()
         if payload_bytes is None:
-            payload_bytes = int(os.environ.get("SLU_IPC_PAYLOAD_MB", "8")) << 20      # everything trainable: 5.5 MB
+            payload_bytes = _knobs.get("SLU_IPC_PAYLOAD_MB") << 20      # everything trainable: 5.5 MB
         self.rank, self.world_size, self.device = rank, world_size, device
         self.window_bytes = int(self._L.slu_comm_ipc_window_bytes(payload_bytes))
-        fine = 0 if os.environ.get("SLU_IPC_COARSE", "0") == "1" else 1
+        fine = 0 if _knobs.get("SLU_IPC_COARSE") else 1
         own, handle = ctypes.c_void_p(), (ctypes.c_char * 64)()
         self._own, self._peers = None, {}
         # Every step of the set-up that can fail on ONE rank is followed by an agreement over the control plane, so that
@@ -326,7 +329,7 @@ class IpcComm:
         waits are microseconds, a dead peer should stop the job in seconds, not park 64 spinning workgroups on every
         rank's training partition for minutes.  SLU_IPC_WAIT_POLLS (default 2^22, ~10 s; 0 = keep the start-up bound)."""
         if polls is None:
-            polls = int(os.environ.get("SLU_IPC_WAIT_POLLS", str(1 << 22)))
+            polls = _knobs.get("SLU_IPC_WAIT_POLLS")
         with torch.cuda.device(self.device):
             self._lib.check(self._L.slu_comm_ipc_set_spin_limit(self._own, int(polls)), "slu_comm_ipc_set_spin_limit")
         self.wait_limit_polls = int(polls)
@@ -429,7 +432,7 @@ def _time_plane(comm, device, n=302616, reps=30, world_size=1):
 def _shared_device():
     """Do several ranks of this job sit on ONE GPU (the --share-gpu / SLU_LOCAL_DEVICE test set-up)?  RCCL refuses
     duplicate devices; same-device IPC works."""
-    return "SLU_LOCAL_DEVICE" in os.environ
+    return _knobs.raw("SLU_LOCAL_DEVICE") is not None
 
 
 def make_comm(rank, world_size, device):
@@ -442,7 +445,7 @@ def make_comm(rank, world_size, device):
       torch           None: torch.distributed's own collective on the buckets (gloo stages device tensors through the
                       host — the functional fallback; backend nccl = ProcessGroupNCCL).
     With SLU_DIST_BACKEND=nccl and SLU_COMM unset the round-4 behaviour is kept (torch.distributed's collective)."""
-    mode = os.environ.get("SLU_COMM", "auto")
+    mode = _knobs.get("SLU_COMM")
     if mode not in ("auto", "ipc", "rccl", "torch"):
         raise ValueError("SLU_COMM=%r: expected auto, ipc, rccl or torch" % mode)
     if dist.is_initialized() and world_size > 1 and device.type == "cuda":
@@ -452,8 +455,8 @@ def make_comm(rank, world_size, device):
         sigs = [None] * world_size
         dist.all_gather_object(sigs, mine)
         if len(set(sigs)) != 1:
-            raise RuntimeError("data parallel: the ranks disagree on arithmetic / weight-gradient settings (SLU_WGRAD_BRANCH, "
-                               "SLU_WGRAD_WGS, SLU_TRAIN_MATH, SLU_FROZEN_MATH, SLU_DTYPE, SLU_AUGMENT, SLU_AUGMENT_TEMPO, SLU_CLIP_GRAD_NORM): %s" % sigs)
+            raise RuntimeError("data parallel: the ranks disagree on arithmetic / weight-gradient settings (%s): %s"
+                               % (", ".join(_knobs.RANKS_AGREE), sigs))
     if mode == "torch" or device.type != "cuda" or not dist.is_initialized():
         return None
     if mode == "auto" and dist.get_backend() == "nccl":
@@ -479,7 +482,7 @@ def make_comm(rank, world_size, device):
         ok, us = _selftest(comm, rank, world_size, device)   # verdict agreed inside
         if ok:
             comm.selftest_us = us
-            if world_size > 1 and not _shared_device() and os.environ.get("SLU_COMM_RACE", "1") != "0":
+            if world_size > 1 and not _shared_device() and _knobs.get("SLU_COMM_RACE"):
                 # one GPU per rank: RCCL is available too — time both planes on the step's payload and keep the faster
                 # (the kernel has only ever run on ranks SHARING a GPU in this repository's test environment; on real links
                 # it must earn its place against the library).  Every step that can fail on one rank is AGREED before the
@@ -745,7 +748,7 @@ class GradBucket:
         collective)."""
         if self._in_graph is not None:
             return self._in_graph
-        mode = os.environ.get("SLU_DP_GRAPH", "auto")
+        mode = _knobs.get("SLU_DP_GRAPH")
         ok = mode != "0" and data_parallel() and device.type == "cuda"
         if ok:
             nccl = dist.get_backend() == "nccl"

@@ -10,11 +10,11 @@ arithmetic of the hot path happens in libslu_hip.so; there is no fallback path.
 import contextlib
 import ctypes
 import math
-import os
 import struct
 
 import torch
 
+from . import knobs as _knobs
 from . import lib as _lib
 
 METHODS = {"none": 0, "avg": 1, "max": 2}
@@ -25,7 +25,7 @@ def bf16_mode():
     recurrences — and the backward contractions of the GRU layers (data gradients, and the weight gradients of layers
     with more than TN_SMALL_ROWS rows on slu_gemm_tn_bf16) take bf16 operands on v_mfma_f32_16x16x32_bf16 with fp32
     accumulation; convolution weight gradients, BPTT gate math, loss math, master weights and Adam stay fp32."""
-    return os.environ.get("SLU_DTYPE", "f32") == "bf16"
+    return _knobs.get("SLU_DTYPE") == "bf16"
 
 
 _TRAIN_MATH = {"split": (2, 3), "bf16x3": (3, 3), "fp32": (0, 0)}
@@ -51,10 +51,7 @@ def train_nsplit(grad=False):
     weight gradients, every reduction, the loss and the optimizer."""
     if bf16_mode():
         return 1
-    mode = os.environ.get("SLU_TRAIN_MATH", "fp32")
-    if mode not in _TRAIN_MATH:
-        raise ValueError("SLU_TRAIN_MATH=%r: expected one of %s" % (mode, sorted(_TRAIN_MATH)))
-    return _TRAIN_MATH[mode][1 if grad else 0]
+    return _TRAIN_MATH[_knobs.get("SLU_TRAIN_MATH")][1 if grad else 0]
 
 
 def _stream():
@@ -645,7 +642,7 @@ AUGMENT_FLAGS = {"gain": 1, "crop": 2, "noise": 4}      # flags of slu_wave_augm
 def augment_flags():
     """SLU_AUGMENT: the components a model with augment=True applies to its training waveforms — a comma list of gain,
     crop, noise (default: all three) -> the flags of slu_wave_augment."""
-    text = os.environ.get("SLU_AUGMENT", "gain,crop,noise")
+    text = _knobs.get("SLU_AUGMENT")
     flags = 0
     for name in text.split(","):
         name = name.strip()
@@ -700,10 +697,7 @@ def tempo_enabled():
     """SLU_AUGMENT_TEMPO: does a model with augment=True stretch its training waveforms (wave_tempo) in front of the other
     effects?  0 (the default) or 1.  A knob of its own, off by default: SLU_AUGMENT keeps naming the components of
     slu_wave_augment alone."""
-    text = os.environ.get("SLU_AUGMENT_TEMPO", "0")
-    if text not in ("0", "1"):
-        raise ValueError("SLU_AUGMENT_TEMPO=%r: expected 0 or 1" % text)
-    return text == "1"
+    return _knobs.get("SLU_AUGMENT_TEMPO")
 
 
 def tempo_defaults(fs=16000):
@@ -840,7 +834,7 @@ def gru_pool_fused_ok(H, D, T, p, mask, method, factor):
     pooling over two frames with an in-kernel Philox mask (or no dropout): every layer of the reference cfgs.  Injected
     masks (parity tests) and other pooling modes take the two-launch path.  SLU_FUSE_GRU_POOL=0: off."""
     return (method == "avg" and factor == 2 and mask is None and (D * H) % 32 == 0 and T <= 65535 and 0.0 <= p < 1.0
-            and os.environ.get("SLU_FUSE_GRU_POOL", "1") != "0")
+            and _knobs.get("SLU_FUSE_GRU_POOL"))
 
 
 # CUs a CU-masked stream may use (pipeline.cu_range_stream registers its streams here): what decides between one and two
@@ -857,7 +851,7 @@ def gru_seq_tiles(B, H, D, fused=None, reserve=False, device=None):
     with its neighbour's VALU work far less than the design assumed (csrc/slu_gru_bf16.hip) — hence opt-in."""
     if H != 128 or fused is not None or reserve:
         return 1
-    env = os.environ.get("SLU_GRU_TILES", "1")
+    env = _knobs.get("SLU_GRU_TILES")
     if env in ("1", "2"):
         return int(env)
     cus = STREAM_CUS.get(torch.cuda.current_stream(device).cuda_stream)
@@ -960,13 +954,13 @@ def gru_fused_input_ok(I, H, D, nsplit):
     largest layer is never written); the pipelined loop: 343-346 k against 325-336 k utt/s (same box).  The fused step costs
     1.70 instead of 1.27 us: its 18 extra MFMAs per wave run back to back at the end of the step (interleaving them with
     the gate math by scheduling hints made the step 2.2 us)."""
-    if not (H == 128 and 1 <= I <= 64 and os.environ.get("SLU_FUSE_GRU_INPUT", "1") != "0"):
+    if not (H == 128 and 1 <= I <= 64 and _knobs.get("SLU_FUSE_GRU_INPUT")):
         return False
     # bf16x3 (round 5): instantiated and bit-identical to GEMM + recurrence (tests/test_hip_bf16.py), but with W_hh (144
     # registers) AND the W_ih fragments (72 for K = 60) resident the kernel spills 40-49 VGPRs to scratch at two waves per
     # SIMD, and the loop gets SLOWER: 160.3-160.7 against 190.7-196.8 k utt/s for the driver's 20-step command, 292-293
     # against 345 k steady (same box, alternating runs).  Only when SLU_FUSE_GRU_INPUT3=1 asks for it.
-    return nsplit == 2 or (nsplit == 3 and os.environ.get("SLU_FUSE_GRU_INPUT3", "0") == "1")
+    return nsplit == 2 or (nsplit == 3 and _knobs.get("SLU_FUSE_GRU_INPUT3"))
 
 
 def gru_seq_fwd_bf16(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, T, B, H, D, nsplit, want_reserve=False, fused=None, seq_tiles=None):
@@ -1075,10 +1069,8 @@ def resolve_wgrad():
     backward call: the budget sets the split-K factor, i.e. the summation order; an environment change in mid-run would
     silently lose bit-identity between steps (and between a run and its resumption).  dp.make_comm compares
     wgrad_signature() across the ranks."""
-    mode = os.environ.get("SLU_WGRAD_BRANCH", "layer")
-    if mode not in ("layer", "pass", "0"):
-        raise ValueError("SLU_WGRAD_BRANCH=%r: expected layer, pass or 0" % mode)
-    _WGRAD[0] = (mode, 0 if mode == "0" else int(os.environ.get("SLU_WGRAD_WGS", "216")))
+    mode = _knobs.get("SLU_WGRAD_BRANCH")
+    _WGRAD[0] = (mode, 0 if mode == "0" else _knobs.get("SLU_WGRAD_WGS"))
     return _WGRAD[0]
 
 
@@ -1086,10 +1078,12 @@ def wgrad_signature():
     """What must be EQUAL on every data-parallel rank for the replicas to stay bit-identical: the weight-gradient launch's
     (mode, workgroup budget), the arithmetic modes, the augmentation components, the tempo knob and the gradient-clipping
     threshold (SLU_AUGMENT, SLU_AUGMENT_TEMPO and SLU_CLIP_GRAD_NORM as written: compared, not parsed here)."""
-    mode, budget = wgrad_branch()
-    return "%s/%d/%s/%s/%s/%s/%s/%s" % (mode, budget, os.environ.get("SLU_TRAIN_MATH", "fp32"), os.environ.get("SLU_FROZEN_MATH", "bf16x3"),
-                                        os.environ.get("SLU_DTYPE", "f32"), os.environ.get("SLU_AUGMENT", "gain,crop,noise"),
-                                        os.environ.get("SLU_AUGMENT_TEMPO", "0"), os.environ.get("SLU_CLIP_GRAD_NORM", "off"))
+    parts = ["%s/%d" % wgrad_branch()]
+    for name in _knobs.RANKS_AGREE:
+        if not name.startswith("SLU_WGRAD_"):               # those two as resolved above, not as written
+            v = _knobs.raw(name)
+            parts.append("off" if v is None else v)
+    return "/".join(parts)
 
 
 def gemm_tn_splitk_ok(operands):
@@ -1116,7 +1110,7 @@ def gru_wgrad_plan(T, B, I, H, D, need_ih, need_hh, aligned):
     one_launch = T > 1 and need_ih and all(need_hh) and I % 4 == 0 and H % 4 == 0
     if one_launch and T * B <= TN_SMALL_ROWS:
         return "batched", 0, "0"
-    if (one_launch and T * B >= TN_SPLITK_MIN_ROWS and train_nsplit(True) == 0 and os.environ.get("SLU_TN_SPLITK", "1") != "0"
+    if (one_launch and T * B >= TN_SPLITK_MIN_ROWS and train_nsplit(True) == 0 and _knobs.get("SLU_TN_SPLITK")
             and aligned):
         mode, budget = wgrad_branch()
         return "splitk", budget, mode if budget else "0"
@@ -1173,7 +1167,7 @@ def gru_proj_fused_ok(x2, w_ih, T, B, I, H, D):
     B = 64) 57.7 us against 51.0 for projection + recurrence on the 96-CU training partition, T = 300: 523 against 427
     (profiles/r04_ap_proj_gru_fused.txt): the consumer's write-through loads and counter reads cost more per step than the
     overlap with the projection returns.  Kept as the tested starting point of that fusion."""
-    if os.environ.get("SLU_FUSE_PROJ_GRU", "0") != "1" or not x2.is_cuda or train_nsplit(False) != 0:
+    if not _knobs.get("SLU_FUSE_PROJ_GRU") or not x2.is_cuda or train_nsplit(False) != 0:
         return False
     if not (x2.stride(1) == 1 and w_ih.stride(1) == 1 and x2.dtype == w_ih.dtype == torch.float32):
         return False
@@ -1263,7 +1257,7 @@ def _ticket(dev):
     """A persistent zeroed device word per (device, stream) for kernels whose last workgroup finishes a reduction
     (it leaves the word at zero).  None while a hipGraph capture is running and the word does not exist yet (memory
     allocated during a capture belongs to the graph): the caller then takes the separate-launch path."""
-    if os.environ.get("SLU_HEAD_TICKET", "1") == "0":
+    if not _knobs.get("SLU_HEAD_TICKET"):
         return None
     key = (dev.index, _stream())
     t = _TICKETS.get(key)
@@ -1568,7 +1562,7 @@ def head_dropout_fusable(weight, p, mask, method, factor, h=None):
     unidirectional 50-unit intent layer passed the gate and the head kernel then refused the 50-channel rows).
     h: optionally the head's actual input, checked as well."""
     ok = (p > 0.0 and mask is None and factor == 1 and weight.dim() == 2 and weight.shape[1] % 4 == 0
-          and weight.data_ptr() % 16 == 0 and os.environ.get("SLU_FUSE_HEAD_DROPOUT", "1") != "0")
+          and weight.data_ptr() % 16 == 0 and _knobs.get("SLU_FUSE_HEAD_DROPOUT"))
     if ok and h is not None:
         ok = h.shape[-1] == weight.shape[1] and h.is_contiguous() and h.data_ptr() % 16 == 0
     return ok

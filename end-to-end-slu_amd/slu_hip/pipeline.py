@@ -15,10 +15,10 @@ host a few microseconds instead of ~1 ms of Python dispatch.  Dropout inside a c
 its Philox offset (step*16) from device memory, so every replay draws the masks of its own step.
 """
 import contextlib
-import os
 
 import torch
 
+from . import knobs as _knobs
 from . import ops
 
 
@@ -75,7 +75,7 @@ def cu_split(device=None):
     96 + 20: 296-299, 112 + 16: 311, 128 + 16: 316-321, 128 + 12: 303, 144 + 14: 226, 160 + 12: 257, 80 + 22: 272,
     64 + 24: 253 (the driver's 20-step command: 200 / 192 / 197 / 199 / 188 / 185).  Round 2 (bf16x3 frozen stages):
     96 + 20 was the optimum (278-281; 128: 223).  SLU_CU_SPLIT=n overrides, 0 = off."""
-    v = os.environ.get("SLU_CU_SPLIT", "auto")
+    v = _knobs.get("SLU_CU_SPLIT")
     if v != "auto":
         return int(v)
     if not torch.cuda.is_available():
@@ -134,7 +134,7 @@ class PrefixSlot:
     # super-batches copy their batches into one input.  SLU_MAX_TABLE=63 admits 32 - 63 batches (measured in round 6 with
     # the two-tile recurrence: 40-batch super-batches 347 - 349 k utt/s against 347 - 356 k for the default 20 — no gain, so
     # the default width, and with it the tested envelope of the table, stay where they were)
-    MAX_TABLE = max(1, min(63, int(os.environ.get("SLU_MAX_TABLE", "31"))))
+    MAX_TABLE = _knobs.get("SLU_MAX_TABLE")      # 1 .. 63
 
     def __init__(self, device):
         self.device = device
@@ -159,7 +159,7 @@ class PrefixSlot:
         # SLOWER (0.73 vs 0.56 ms/step; any CU mask for the copy stream: 16 / 32 / 160 CUs or none) than with the copies
         # serialised on the slot's own stream — the host-input path is PCIe-bound either way.  SLU_COPY_CUS=n > 0 enables
         # the separate copy stream on the top n CUs of the look-ahead partition (>= its size: unmasked).
-        n_copy = int(os.environ.get("SLU_COPY_CUS", "0"))
+        n_copy = _knobs.get("SLU_COPY_CUS")
         total = n_compute_units(device)
         if n_copy <= 0:
             self.copy_stream = None
@@ -202,7 +202,7 @@ class PrefixSlot:
         B, T = xs[0].shape
         host = not all(x.is_cuda for x in xs)
         whole = (whole_chip and self.whole is not None and not host and use_graph
-                 and os.environ.get("SLU_RAMP_WHOLE_CHIP", "1") != "0")
+                 and _knobs.get("SLU_RAMP_WHOLE_CHIP"))
         stream = self.stream
         if whole:
             stream = self.whole
@@ -288,7 +288,7 @@ class PrefixSlot:
         pm = getattr(model, "pretrained_model", model)
         # (an augmenting model reads the table in ops.wave_augment, whatever kernel its first block runs on)
         augmenting = getattr(model, "augment", False) and model.training
-        return (os.environ.get("SLU_ROW_TABLE", "1") != "0" and 1 < len(xs) <= self.MAX_TABLE
+        return (_knobs.get("SLU_ROW_TABLE") and 1 < len(xs) <= self.MAX_TABLE
                 and (augmenting or (hasattr(pm, "accepts_row_table") and pm.accepts_row_table()))
                 and xs[0].dtype in (torch.float32, torch.int16)
                 and all(x.is_cuda and x.device == self.device and x.dtype == xs[0].dtype and x.is_contiguous()
@@ -433,8 +433,8 @@ class StepGraph:
 
 
 def _one_graph():
-    return os.environ.get("SLU_ONE_STEP_GRAPH", "1") != "0"
+    return _knobs.get("SLU_ONE_STEP_GRAPH")
 
 
 def graphs_enabled():
-    return os.environ.get("SLU_GRAPHS", "1") != "0"
+    return _knobs.get("SLU_GRAPHS")

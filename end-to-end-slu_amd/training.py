@@ -37,7 +37,7 @@ def models_masks_injected():
 
 def _lookahead_env():
     """SLU_LOOKAHEAD: number of batches per look-ahead super-batch; unset / "auto" -> -1 (by batch size)."""
-    v = os.environ.get("SLU_LOOKAHEAD", "auto")
+    v = _knobs.get("SLU_LOOKAHEAD")
     return -1 if v == "auto" else int(v)
 
 
@@ -45,35 +45,35 @@ def _lookahead_slots():
     """SLU_LOOKAHEAD_SLOTS: look-ahead super-batches in flight, at least 2; default 2."""
     # two slots: one super-batch is consumed while the next is computed (a third slot only reads further ahead:
     # 342 -> 323 k utt/s steady state, profiles/r05_a_sweep.txt)
-    return max(2, int(os.environ.get("SLU_LOOKAHEAD_SLOTS", "2")))
+    return _knobs.get("SLU_LOOKAHEAD_SLOTS")
 
 
 def _max_step_graphs():
     """SLU_MAX_STEP_GRAPHS: distinct step shapes kept as captured hipGraphs (each owns its activations: ~0.2 GB at
     B = 64); default 8."""
-    return int(os.environ.get("SLU_MAX_STEP_GRAPHS", "8"))
+    return _knobs.get("SLU_MAX_STEP_GRAPHS")
 
 
 def _ramp_env():
     """SLU_RAMP: "0" (default) = one capped first super-batch, "auto" = three side by side, "a,b,c" = explicit sizes
     (_ramp_plan has the rule and the measurements)."""
-    return os.environ.get("SLU_RAMP", "0")
+    return _knobs.get("SLU_RAMP")
 
 
 def _ramp_side():
     """SLU_RAMP_SIDE: explicit SLU_RAMP sizes started side by side — 1: all of them; k >= 2: the first k; default 0: none."""
-    return int(os.environ.get("SLU_RAMP_SIDE", "0"))
+    return _knobs.get("SLU_RAMP_SIDE")
 
 
 def _ramp_whole_n():
     """SLU_RAMP_WHOLE_N: of a ramp that starts side by side, how many first super-batches take the whole chip; default 0."""
-    return int(os.environ.get("SLU_RAMP_WHOLE_N", "0"))
+    return _knobs.get("SLU_RAMP_WHOLE_N")
 
 
 def _prefix_chain():
     """SLU_PREFIX_CHAIN: "1" (default) = a super-batch waits for its predecessor; "0" = see below."""
     # SLU_PREFIX_CHAIN=0 (experiment): super-batches of different slots never wait for each other
-    return os.environ.get("SLU_PREFIX_CHAIN", "1") != "0"
+    return _knobs.get("SLU_PREFIX_CHAIN")
 
 
 def _host_wait():
@@ -88,12 +88,12 @@ def _host_wait():
     # profiles/r06_y_host_wait_all.txt).  "first": only the run's first super-batch.  (Queuing the
     # group's first 1 / 2 / 4 steps BEFORE the wait, to hide the host's wake-up: 227 / 228 / 226 k
     # against 230 k utt/s for the 20-step command — not kept.)
-    return os.environ.get("SLU_HOST_WAIT", "all")
+    return _knobs.get("SLU_HOST_WAIT")
 
 
 def _graph_forks():
     """SLU_GRAPH_FORKS: "1" (default) = the steps of a loop with nothing beside them raise ops._Fork.defer; "0" = never."""
-    return os.environ.get("SLU_GRAPH_FORKS", "1") != "0"
+    return _knobs.get("SLU_GRAPH_FORKS")
 
 
 def _param_signature(model):
@@ -161,7 +161,7 @@ def mask_train_enabled():
     """SLU_MASK_TRAIN: "0" (default) — the training loops drop the lengths (_drop_lengths); "1" — they train on them
     (Model.forward(lengths=...)): every step's loss and gradients are the mean of what its utterances give alone, whatever
     the batch was padded to.  Needs SLU_MASK_PADDING=1 (the collate function supplies the lengths)."""
-    on = _knobs.flag("SLU_MASK_TRAIN")
+    on = _knobs.get("SLU_MASK_TRAIN")
     if on and not data_mask_padding_enabled():
         raise ValueError("SLU_MASK_TRAIN=1 needs SLU_MASK_PADDING=1: the lengths come from the collate function")
     return on
@@ -182,7 +182,7 @@ def clip_grad_norm_knob():
     gradient is dropped, inside optimizer.step() on the device (slu_hip/optim.py; "inf" never clips but still measures and
     skips).  -> None or the threshold; anything else is a ValueError.  An environment knob, not a cfg key: read_config
     mirrors the reference's parse."""
-    v = os.environ.get("SLU_CLIP_GRAD_NORM")
+    v = _knobs.get("SLU_CLIP_GRAD_NORM")
     if v is None:
         return None
     from slu_hip.optim import check_max_grad_norm
