@@ -5,178 +5,79 @@ PyTorch fallback: if the shared object is missing, or a call fails, this module 
 """
 import ctypes
 import os
+import re
 
 from . import knobs as _knobs
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SLU_HIP_LIB: another build of the same ABI (the probe build of tools/gru_probe.py); the product never sets it
 LIB_PATH = _knobs.get("SLU_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libslu_hip.so")
+# the header csrc/build.sh compiles every unit against, found the way build.sh finds it; SLU_HIP_LIB changes the .so only
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "slu_hip.h"))
 
-c_i64 = ctypes.c_int64
-c_int = ctypes.c_int
-c_f32 = ctypes.c_float
-c_f64 = ctypes.c_double
-c_u64 = ctypes.c_uint64
-c_sz = ctypes.c_size_t
-vp = ctypes.c_void_p
-
-# name -> (restype, argtypes); mirrors include/slu_hip.h one to one
-SIGNATURES = {
-    "slu_version": (c_int, []),
-    "slu_last_error": (ctypes.c_char_p, []),
-    "slu_device_check": (c_int, []),
-    "slu_device_arch": (ctypes.c_char_p, []),
-    "slu_stream_create_cu_range": (c_int, [c_i64, c_i64, vp]),
-    "slu_store_u64": (c_int, [vp, vp, c_i64, vp]),
-    "slu_stage_inputs": (c_int, [vp, vp, vp, vp, vp, c_i64, vp, c_i64, vp]),
-    "slu_multi_max": (c_int, []),
-    "slu_copy_multi": (c_int, [vp, vp, vp, c_i64, vp]),
-    "slu_scale_multi": (c_int, [vp, vp, c_i64, vp, vp]),
-    "slu_absmax_multi": (c_int, [vp, vp, c_i64, vp, vp]),
-    "slu_pcm16_to_f32": (c_int, [vp, vp, c_i64, c_f32, vp]),
-    "slu_pool_act_fwd": (c_int, [vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_int, c_f32, c_i64, c_i64, vp]),
-    "slu_pool_act_bwd": (c_int, [vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_f32, c_i64, c_i64, vp]),
-    "slu_gru_cell_fwd": (c_int, [vp, vp, vp, c_i64, vp, c_i64, vp, vp, vp, c_f32, c_u64, c_u64, vp, c_u64, c_i64, c_i64, vp]),
-    "slu_gru_cell_bwd": (c_int, [vp, c_i64, vp, vp, vp, c_i64, vp, vp, vp, c_i64, vp, c_f32, c_u64, c_u64, vp, c_u64,
-                                 c_i64, c_i64, vp]),
-    "slu_attention_fwd": (c_int, [vp, c_i64, c_i64, vp, c_i64, c_i64, vp, c_i64, vp, c_i64, vp, c_f32, c_i64, c_i64, c_i64,
-                                  c_i64, vp]),
-    "slu_attention_bwd": (c_int, [vp, c_i64, c_i64, vp, c_i64, c_i64, vp, c_i64, vp, c_i64, vp, vp, vp, vp, c_i64, c_f32,
-                                  c_i64, c_i64, c_i64, c_i64, vp]),
-    "slu_logsoftmax_dot_fwd": (c_int, [vp, vp, c_i64, vp, vp, c_i64, c_i64, vp]),
-    "slu_logsoftmax_dot_bwd": (c_int, [vp, vp, c_i64, vp, vp, c_i64, vp, c_i64, c_i64, vp]),
-    "slu_neg_mean_f32": (c_int, [vp, vp, c_i64, vp]),
-    "slu_fill_scaled_f32": (c_int, [vp, c_i64, vp, c_f32, vp]),
-    "slu_broadcast_rows_f32": (c_int, [vp, vp, c_i64, c_i64, c_i64, vp]),
-    "slu_beam_select": (c_int, [vp, vp, vp, vp, vp, vp, vp, vp, c_i64, vp, c_i64, vp, vp, c_i64, c_i64, c_i64, c_i64, c_i64,
-                                c_i64, c_i64, c_i64, vp]),
-    "slu_beam_select_eos": (c_int, [vp, vp, vp, vp, vp, vp, vp, vp, c_i64, vp, c_i64, vp, vp, c_i64, c_i64, c_i64, c_i64,
-                                    c_i64, c_i64, c_i64, c_i64, c_i64, vp, vp, vp]),
-    "slu_beam_select_lex": (c_int, [vp, vp, vp, vp, vp, vp, vp, vp, c_i64, vp, c_i64, vp, vp, c_i64, c_i64, c_i64, c_i64,
-                                    c_i64, c_i64, c_i64, c_i64, c_i64, vp, vp, vp, vp, vp, c_i64, vp, vp]),
-    "slu_beam_backtrack": (c_int, [vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, vp]),
-    "slu_trie_expand": (c_int, [vp, vp, vp, vp, vp, vp, vp, vp, c_i64, vp, c_i64, vp, vp, vp, vp, c_i64, vp, c_i64, c_i64,
-                                c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, vp]),
-    "slu_trie_finish": (c_int, [vp, vp, vp, vp, c_i64, c_i64, vp]),
-    "slu_sinc_filters_fwd": (c_int, [vp, vp, vp, c_i64, c_i64, c_f64, vp]),
-    "slu_sinc_filters_bwd": (c_int, [vp, vp, vp, vp, vp, c_i64, c_i64, c_f64, vp]),
-    "slu_wconv_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
-    "slu_wconv_fwd": (c_int, [vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int,
-                              c_int, c_f32, c_i64, c_i64, vp, c_sz, vp]),
-    "slu_wconv_bwd_act": (c_int, [vp, vp, vp, vp, c_i64, c_i64, c_i64, c_int, c_int, c_f32, c_i64,
-                                  c_i64, vp]),
-    "slu_wconv_bwd_data": (c_int, [vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_i64, vp, c_sz, vp]),
-    "slu_wconv_bwd_weight_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64, c_i64, c_i64, c_i64]),
-    "slu_wconv_bwd_weight": (c_int, [vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, vp,
-                                     c_sz, vp]),
-    "slu_gemm_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
-    "slu_gemm_plan": (c_int, [c_i64, c_i64, c_i64, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
-    "slu_gemm_f32": (c_int, [vp, c_i64, c_i64, vp, c_i64, c_i64, vp, c_i64, c_i64, vp, c_i64, c_i64,
-                             c_i64, c_int, vp, c_sz, vp]),
-    "slu_split_bf16": (c_int, [vp, c_i64, vp, c_i64, c_i64, c_i64, c_int, vp]),
-    "slu_gemm_bf16_pack_bytes": (c_sz, [c_i64, c_i64, c_int]),
-    "slu_gemm_bf16_pack": (c_int, [vp, c_i64, c_i64, vp, c_i64, c_i64, c_int, vp]),
-    "slu_gemm_bf16": (c_int, [vp, c_i64, c_i64, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_int, vp]),
-    "slu_gemm_bf16_a32": (c_int, [vp, c_i64, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_int, vp]),
-    "slu_gemm_tn_bf16_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
-    "slu_gemm_tn_bf16": (c_int, [vp, c_i64, vp, c_i64, vp, c_i64, c_i64, c_i64, c_i64, c_int, vp, c_sz, vp]),
-    "slu_wconv_bf16_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64, c_int]),
-    "slu_wconv_fwd_bf16": (c_int, [vp, vp, c_i64, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_f32,
-                                   c_i64, c_i64, vp, c_i64, vp, c_sz, c_int, c_int, vp, c_int, c_f32, vp]),
-    "slu_gru_seq_fwd_bf16": (c_int, [vp, vp, vp, vp, vp, vp, vp, vp, c_i64, c_i64, vp, vp, c_i64, c_i64, c_i64, c_i64, c_int,
-                                     c_int, vp]),
-    "slu_gru_seq_fwd_pool_bf16": (c_int, [vp, vp, vp, vp, vp, vp, vp, c_i64, vp, c_f32, vp, c_i64, c_i64, vp, vp, c_i64,
-                                          c_i64, c_i64, c_i64, c_int, c_int, vp]),
-    "slu_dropout_bits": (c_int, [vp, c_f32, c_u64, c_u64, vp, c_i64, c_u64, c_i64, c_i64, c_i64, vp]),
-    "slu_wave_augment": (c_int, [vp, vp, c_i64, c_int, c_f32, vp, vp, c_i64, c_i64, c_int, c_u64, c_u64, vp, c_i64, c_u64, vp]),
-    "slu_wave_tempo": (c_int, [vp, vp, c_i64, c_int, c_f32, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_f32, c_u64, c_u64, vp,
-                               c_i64, c_u64, vp]),
-    "slu_wave_augment_len": (c_int, [vp, vp, c_i64, c_int, c_f32, vp, vp, vp, vp, c_i64, c_i64, c_int, c_u64, c_u64, vp, c_i64,
-                                     c_u64, vp]),
-    "slu_wave_tempo_len": (c_int, [vp, vp, c_i64, c_int, c_f32, vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_f32, c_u64,
-                                   c_u64, vp, c_i64, c_u64, vp]),
-    "slu_mask_rows_len": (c_int, [vp, vp, vp, c_i64, c_i64, vp]),
-    "slu_pool_act_len_fwd": (c_int, [vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_int, c_f32, c_i64, c_i64, vp]),
-    "slu_gru_seq_fwd_len": (c_int, [vp, vp, vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, vp]),
-    "slu_seq_pool_len_fwd": (c_int, [vp, vp, vp, c_int, c_i64, c_i64, c_i64, c_i64, vp]),
-    "slu_gru_seq_fwd_len_bf16": (c_int, [vp, vp, vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_int, vp]),
-    "slu_cls_maxpool_len_fwd": (c_int, [vp, vp, vp, vp, vp, ctypes.POINTER(c_i64), c_i64, vp, vp, vp, vp, vp, c_i64, c_i64,
-                                        c_i64, vp]),
-    "slu_gru_seq_fwd_len_rsv": (c_int, [vp, vp, vp, vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, vp]),
-    "slu_gru_seq_bwd_len": (c_int, [vp, vp, vp, vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, vp]),
-    "slu_dropout_pool_len_fwd": (c_int, [vp, vp, vp, c_i64, c_i64, c_f32, c_u64, c_u64, vp, c_int, c_i64, vp, c_i64, c_i64,
-                                         c_i64, vp]),
-    "slu_dropout_pool_len_bwd": (c_int, [vp, vp, vp, vp, c_i64, c_i64, c_f32, c_u64, c_u64, vp, c_int, c_i64, vp, c_i64,
-                                         c_i64, c_i64, vp]),
-    "slu_cls_maxpool_len_ce_fwd": (c_int, [vp, vp, vp, vp, vp, ctypes.POINTER(c_i64), c_i64, vp, vp, vp, vp, vp, vp, c_i64,
-                                           c_i64, c_i64, vp]),
-    "slu_pool_act_len_fwd_route": (c_int, [vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_int, c_f32, c_i64, c_i64, vp]),
-    "slu_pool_act_len_bwd": (c_int, [vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_f32, c_i64, c_i64, vp]),
-    "slu_attention_len_fwd": (c_int, [vp, c_i64, c_i64, vp, c_i64, c_i64, vp, c_i64, vp, c_i64, vp, vp, c_f32, c_i64, c_i64,
-                                      c_i64, c_i64, vp]),
-    "slu_attention_len_bwd": (c_int, [vp, c_i64, c_i64, vp, c_i64, c_i64, vp, c_i64, vp, c_i64, vp, vp, vp, vp, c_i64, vp,
-                                      c_f32, c_i64, c_i64, c_i64, c_i64, vp]),
-    "slu_frame_pack_len": (c_int, [vp, vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_i64, vp]),
-    "slu_frame_unpack_len": (c_int, [vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, vp]),
-    "slu_ctc_workspace_bytes": (c_sz, [c_i64, c_i64, c_i64]),
-    "slu_ctc_loss_fwd": (c_int, [vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, vp, vp, vp, c_sz, vp]),
-    "slu_ctc_greedy_errors": (c_int, [vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_i64, vp, vp, vp, vp, vp]),
-    "slu_comm_version": (c_int, []),
-    "slu_comm_unique_id": (c_int, [vp]),
-    "slu_comm_init": (c_int, [vp, vp, c_i64, c_i64]),
-    "slu_comm_allreduce_f32": (c_int, [vp, vp, c_i64, vp]),
-    "slu_comm_allreduce_f64": (c_int, [vp, vp, c_i64, vp]),
-    "slu_comm_destroy": (c_int, [vp]),
-    "slu_comm_allreduce_group": (c_int, [vp, vp, c_i64, vp, c_i64, vp]),
-    "slu_comm_ipc_window_bytes": (c_i64, [c_i64]),
-    "slu_comm_ipc_window_create": (c_int, [c_i64, c_i64, vp, vp]),
-    "slu_comm_ipc_window_open": (c_int, [vp, vp]),
-    "slu_comm_ipc_window_close": (c_int, [vp]),
-    "slu_comm_ipc_window_destroy": (c_int, [vp]),
-    "slu_comm_allreduce_ipc": (c_int, [vp, c_i64, c_i64, c_i64, vp, c_i64, vp, c_i64, vp]),
-    "slu_comm_ipc_status": (c_int, [vp, vp]),
-    "slu_comm_ipc_set_spin_limit": (c_int, [vp, c_i64]),
-    "slu_comm_ipc_resident_workgroups": (c_int, [c_i64, vp, vp]),
-    "slu_comm_ipc_max_wait": (c_int, [vp, vp]),
-    "slu_comm_ipc_window_touch": (c_int, [vp, c_i64, c_i64, c_i64, vp]),
-    "slu_gru_proj_supported": (c_int, [c_i64, c_i64, c_i64, c_i64, c_i64]),
-    "slu_gru_proj_state_words": (c_i64, [c_i64, c_i64]),
-    "slu_gru_proj_seq_fwd": (c_int, [vp, c_i64, vp, c_i64, vp, vp, vp, vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, c_i64, vp, c_i64, vp]),
-    "slu_gemm_tn_batched": (c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, c_i64, vp, c_i64, c_i64, vp, vp]),
-    "slu_gemm_tn_splitk_workspace_bytes": (c_sz, [vp, vp, vp, c_i64, c_i64]),
-    "slu_gemm_tn_batched_splitk": (c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, c_i64, vp, c_i64, c_i64, vp, vp, c_sz, vp, c_i64, c_i64, vp]),
-    "slu_gemm_small_batched": (c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, c_i64, vp]),
-    "slu_colsum_f32": (c_int, [vp, c_i64, vp, c_i64, c_i64, c_int, vp]),
-    "slu_gru_reserve_bytes": (c_sz, [c_i64, c_i64, c_i64, c_i64]),
-    "slu_gru_bias_tiles": (c_i64, [c_i64, c_i64, c_i64, c_i64]),
-    "slu_frame_ce_fwd": (c_int, [vp, vp, c_i64, c_i64, c_i64, c_int, vp, vp, vp]),
-    "slu_adam_max_tensors": (c_int, []),
-    "slu_adam_multi": (c_int, [vp, vp, vp, vp, vp, c_i64, c_int, vp, c_f64, c_f64, c_f64, c_f64, c_f64, vp, vp]),
-    "slu_adam_advance_step": (c_int, [vp, c_u64, vp]),
-    "slu_grad_sumsq_chunk": (c_i64, []),
-    "slu_grad_sumsq_workspace_bytes": (c_sz, [vp, c_i64]),
-    "slu_grad_sumsq_multi": (c_int, [vp, vp, c_i64, c_int, vp, c_sz, c_i64, c_int, c_f64, c_f64, vp, vp, vp]),
-    "slu_adam_multi_clip": (c_int, [vp, vp, vp, vp, vp, c_i64, c_int, vp, c_f64, c_f64, c_f64, c_f64, c_f64, vp, vp, vp]),
-    "slu_gru_seq_fwd": (c_int, [vp, vp, vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, vp]),
-    "slu_gru_seq_bwd": (c_int, [vp, vp, vp, vp, vp, vp, vp, c_i64, c_i64, c_i64, c_i64, vp]),
-    "slu_dropout_pool_fwd": (c_int, [vp, vp, c_i64, c_i64, vp, c_f32, c_u64, c_u64, vp, c_i64, c_u64, c_int,
-                                     c_i64, vp, c_i64, c_i64, c_i64, vp]),
-    "slu_dropout_pool_fwd_planes": (c_int, [vp, vp, c_i64, c_i64, vp, c_f32, c_u64, c_u64, vp, c_i64, c_u64, c_int,
-                                            c_i64, vp, c_i64, c_int, c_i64, c_i64, c_i64, vp]),
-    "slu_dropout_pool_bwd": (c_int, [vp, vp, vp, vp, c_i64, c_i64, c_f32, c_u64, c_u64, vp, c_i64, c_u64,
-                                     c_int, c_i64, vp, c_i64, c_i64, c_i64, vp]),
-    "slu_cls_maxpool_ce_fwd": (c_int, [vp, vp, vp, vp, ctypes.POINTER(c_i64), c_i64, vp, vp, vp, vp, vp, vp, vp, vp,
-                                       c_f32, c_u64, c_u64, vp, vp, c_i64, c_i64, c_i64, vp]),
-    "slu_cls_maxpool_ce_bwd": (c_int, [vp, vp, vp, vp, vp, vp, vp, vp, c_f32, c_u64, c_u64, vp, c_i64, c_i64, c_i64, c_i64,
-                                       vp]),
-}
-
-_lib = None
-ABI_VERSION = 10         # SLU_ABI_VERSION of include/slu_hip.h
+_SCALARS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t,
+            "float": ctypes.c_float, "double": ctypes.c_double}
 
 
 class SluHipError(RuntimeError):
     pass
+
+
+def _ctype(ctype, func, returned=False):
+    """The one mapping rule, by C type: any parameter with a `*` is c_void_p (device pointers, host arrays, out-parameters,
+    hipStream_t as void*), a returned const char* is c_char_p, every scalar comes from _SCALARS.  Nothing has a default."""
+    words = " ".join(w for w in ctype.replace("*", " * ").split() if w != "const")
+    if returned and words == "char *":
+        return ctypes.c_char_p
+    if "*" in words and not returned:
+        return ctypes.c_void_p
+    if words not in _SCALARS:
+        raise SluHipError("slu_hip.h: %s: no ctypes mapping for the %s type '%s'"
+                          % (func, "return" if returned else "parameter", " ".join(ctype.split())))
+    return _SCALARS[words]
+
+
+def parse_header(text):
+    """Header text -> ({name: (restype, [argtypes])}, SLU_ABI_VERSION).  Every statement of the header that is not a typedef
+    must be a `RET slu_name(TYPE name, ...);` declaration; anything this cannot read raises SluHipError."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    version = re.search(r"^[ \t]*#[ \t]*define[ \t]+SLU_ABI_VERSION[ \t]+(\d+)[ \t]*$", text, flags=re.M)
+    if not version:
+        raise SluHipError("slu_hip.h: no #define SLU_ABI_VERSION")
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    text = re.sub(r"\btypedef\s+(?:enum|struct)\b[^{};]*\{[^{}]*\}[^{};]*;", "", text)
+    text = re.sub(r'\bextern\s+"C"\s*\{|\}\s*\Z', "", text)
+    table = {}
+    for stmt in filter(None, (s.strip() for s in text.split(";"))):
+        m = re.fullmatch(r"([\w\s*]+?)\b(slu_\w+)\s*\((.*)\)", stmt, flags=re.S)
+        if not m:
+            raise SluHipError("slu_hip.h: not a function declaration: '%s'" % " ".join(stmt.split()))
+        ret, func, params = m.groups()
+        if func in table:
+            raise SluHipError("slu_hip.h: %s is declared twice" % func)
+        args = []
+        for param in ([] if params.strip() == "void" else params.split(",")):
+            p = re.fullmatch(r"\s*(\w[\w\s*]*[\s*])(\w+)\s*", param)
+            if not p:                  # function pointers and arrays have ( ) [ ]; an unnamed one has no trailing identifier
+                raise SluHipError("slu_hip.h: %s: parameter '%s' is not `TYPE name`" % (func, " ".join(param.split())))
+            args.append(_ctype(p.group(1), func))
+        table[func] = (_ctype(ret, func, returned=True), args)
+    return table, int(version.group(1))
+
+
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return f.read()
+    except OSError as e:
+        raise SluHipError("the C ABI header %s cannot be read (%s); the binding table is derived from it"
+                          % (HEADER_PATH, e)) from None
+
+
+# name -> (restype, argtypes), and SLU_ABI_VERSION: both read from include/slu_hip.h at import
+SIGNATURES, ABI_VERSION = parse_header(_read_header())
+
+_lib = None
 
 
 def load():

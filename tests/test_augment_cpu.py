@@ -13,6 +13,8 @@ import torch
 
 from oracle import slu_oracle as O
 
+import abi_header
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 GAIN, CROP, NOISE = 1, 2, 4
@@ -121,10 +123,8 @@ def test_philox_mirror_known_answers():
 
 def test_symbol_in_header_binding_and_library():
     from slu_hip import lib
-    header = open(os.path.join(ROOT, "include", "slu_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    m = re.search(r"int\s+slu_wave_augment\s*\(([^)]*)\)", code)
-    assert m and len(m.group(1).split(",")) == len(lib.SIGNATURES["slu_wave_augment"][1]) == 16
+    assert re.search(r"int\s+slu_wave_augment\s*\(", abi_header.code())
+    assert abi_header.arg_counts()["slu_wave_augment"] == len(lib.SIGNATURES["slu_wave_augment"][1]) == 16
     L = lib.load()
     assert hasattr(L, "slu_wave_augment")
     assert L.slu_version() == lib.ABI_VERSION == 10

@@ -2,12 +2,11 @@
 binding table and the shared library under ABI version 10, refuses bad arguments before anything touches a device (its
 own: eos outside [0, V), null lengths / n_done; and every refusal slu_beam_select makes); the SLU_BEAM_EOS knob validates
 its value."""
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import abi_header
 
 
 def _lib():
@@ -27,11 +26,10 @@ def _select_eos(L, W=4, batch=3, V=20, Ld=2, Dd=32, U=5, ptr=0x1000, **kw):
 
 def test_header_binding_table_and_library_have_the_eos_entry_point_at_abi_10():
     lib, L = _lib()
-    header = open(os.path.join(ROOT, "include", "slu_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    assert re.search(r"\bint\s+slu_beam_select_eos\s*\(", code)
-    assert int(re.search(r"#define\s+SLU_ABI_VERSION\s+(\d+)", header).group(1)) == 10
+    assert re.search(r"\bint\s+slu_beam_select_eos\s*\(", abi_header.code())
+    assert abi_header.abi_version() == 10
     assert "slu_beam_select_eos" in lib.SIGNATURES
+    assert len(lib.SIGNATURES["slu_beam_select_eos"][1]) == abi_header.arg_counts()["slu_beam_select_eos"]
     # slu_beam_select's arguments, then eos, lengths, n_done in front of the stream
     old, new = lib.SIGNATURES["slu_beam_select"], lib.SIGNATURES["slu_beam_select_eos"]
     assert new[0] == old[0] and new[1][:len(old[1]) - 1] == old[1][:-1] and len(new[1]) == len(old[1]) + 3

@@ -6,7 +6,6 @@
     of tests/test_augment_cpu.py and tests/test_tempo_cpu.py;
   * SLU_MASK_AUGMENT: parsing, its dependency on SLU_MASK_TRAIN, and what Model.forward(lengths=...) refuses with it.
 """
-import os
 import re
 
 import pytest
@@ -19,8 +18,7 @@ import training
 from slu_hip import lib, ops
 from test_augment_cpu import row_params
 from test_tempo_cpu import out_len, tempo_factor
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import abi_header
 
 
 def _sy(vps):
@@ -47,14 +45,12 @@ LENS = (1, 2, 9, 10, 11, 909, 910, 1000)        # the clamp to T = 1000 (Lmax of
 
 
 def test_symbols_in_header_binding_and_library():
-    header = open(os.path.join(ROOT, "include", "slu_hip.h")).read()
-    assert "#define SLU_ABI_VERSION 10" in header
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    assert abi_header.abi_version() == 10
     L = lib.load()
     assert L.slu_version() == lib.ABI_VERSION == 10
     for name, dense, nargs in (("slu_wave_augment_len", "slu_wave_augment", 18), ("slu_wave_tempo_len", "slu_wave_tempo", 22)):
-        m = re.search(r"int\s+%s\s*\(([^)]*)\)" % name, code)
-        assert m and len(m.group(1).split(",")) == len(lib.SIGNATURES[name][1]) == nargs, name
+        m = re.search(r"int\s+%s\s*\(([^)]*)\)" % name, abi_header.code())
+        assert m and abi_header.arg_counts()[name] == len(lib.SIGNATURES[name][1]) == nargs, name
         assert nargs == len(lib.SIGNATURES[dense][1]) + 2                    # the sibling's arguments + lengths, lengths_out
         assert "const int32_t* lengths" in m.group(1) and "int32_t* lengths_out" in m.group(1)
         assert hasattr(L, name)

@@ -19,6 +19,7 @@ import data
 import models
 import training
 from slu_hip import lib
+from abi_header import arg_counts
 
 
 def _sy(vps):
@@ -140,7 +141,7 @@ def test_library_has_the_length_entry_points():
             "slu_cls_maxpool_len_fwd": 16}
     for name, nargs in want.items():
         assert hasattr(raw, name), name
-        assert len(lib.SIGNATURES[name][1]) == nargs, name
+        assert len(lib.SIGNATURES[name][1]) == nargs == arg_counts()[name], name
     # argument checks that need no device: NULL lengths / NULL pointers are refused before any launch
     assert L.slu_gru_seq_fwd_len(1, 1, 1, 1, 1, 1, None, 4, 2, 16, 2, None) == -1
     assert b"lengths" in L.slu_last_error()

@@ -10,7 +10,6 @@ the seq2seq head").
 """
 import ctypes
 import os
-import re
 import types
 
 import pytest
@@ -21,15 +20,9 @@ from oracle import slu_oracle as O
 import models
 import training
 from slu_hip import lib
+from abi_header import arg_counts, header_functions
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LABELS = ["<sos>", "a", "b", "c", "<eos>"]
-
-
-def header_functions():
-    text = open(os.path.join(ROOT, "include", "slu_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(slu_[a-z0-9_]+)\s*\(", text)))
 
 
 def tiny_seq2seq_cfg(folder, **kw):
@@ -61,7 +54,7 @@ def test_library_has_the_length_aware_attention_entry_points():
     for name, nargs in NEW.items():
         assert name in header_functions(), name
         assert hasattr(raw, name), name
-        assert len(lib.SIGNATURES[name][1]) == nargs, name
+        assert len(lib.SIGNATURES[name][1]) == nargs == arg_counts()[name], name
         dense = name.replace("_len", "")
         assert len(lib.SIGNATURES[dense][1]) == nargs - 1, name         # the dense call's arguments plus n
     one = ctypes.c_int32(1)

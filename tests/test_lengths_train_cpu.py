@@ -6,8 +6,6 @@
   * SLU_MASK_TRAIN: needs SLU_MASK_PADDING, keeps the lengths in the training loop and hands them to the model.
 """
 import ctypes
-import os
-import re
 
 import pytest
 import torch
@@ -17,14 +15,7 @@ from oracle import slu_oracle as O
 import models
 import training
 from slu_hip import lib
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def header_functions():
-    text = open(os.path.join(ROOT, "include", "slu_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(slu_[a-z0-9_]+)\s*\(", text)))
+from abi_header import arg_counts, header_functions
 
 
 def _sy(vps):
@@ -57,7 +48,7 @@ def test_library_has_the_masked_training_entry_points():
     raw = ctypes.CDLL(lib.LIB_PATH)
     for name, nargs in NEW.items():
         assert hasattr(raw, name), name
-        assert len(lib.SIGNATURES[name][1]) == nargs, name
+        assert len(lib.SIGNATURES[name][1]) == nargs == arg_counts()[name], name
     one = ctypes.c_int32(1)
     n1 = ctypes.addressof(one)
     # NULL lengths: refused before any launch

@@ -2,16 +2,14 @@
 slu_trie_expand): the level ranges, the inner lists, slot and width on hand-made and seeded random tries; a numpy mirror of
 the sweep rule against the brute-force per-entry sum, bit for bit; the two entry points in the header, the binding table and
 the library, and their refusals without a device; the SLU_LEXICON_EXACT knob."""
-import os
 import re
 
 import numpy as np
 import pytest
 
+import abi_header
 import lexicon_exact_ref as R
 from slu_hip.lexicon import Lexicon
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def lexicons():
@@ -110,12 +108,10 @@ def test_tree_rows_tell_reduction_orders_apart_whatever_expf_rounds_to():
 def test_header_binding_table_and_library_have_the_trie_entry_points_at_abi_10():
     from slu_hip import lib
     L = lib.load()
-    header = open(os.path.join(ROOT, "include", "slu_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    assert int(re.search(r"#define\s+SLU_ABI_VERSION\s+(\d+)", header).group(1)) == 10 == lib.ABI_VERSION
+    assert abi_header.abi_version() == 10 == lib.ABI_VERSION
     for name in ("slu_trie_expand", "slu_trie_finish"):
-        proto = re.search(r"\bint\s+%s\s*\((.*?)\)\s*;" % name, code, flags=re.S).group(1)
-        assert len(proto.split(",")) == len(lib.SIGNATURES[name][1]) and hasattr(L, name)
+        assert re.search(r"\bint\s+%s\s*\(" % name, abi_header.code())
+        assert abi_header.arg_counts()[name] == len(lib.SIGNATURES[name][1]) and hasattr(L, name)
 
 
 def _expand(L, ptr=0x1000, **kw):
