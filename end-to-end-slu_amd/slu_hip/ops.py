@@ -1155,7 +1155,10 @@ def gru_seq_fwd(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, T, B, H, D, want_reserve):
     return out, reserve
 
 
-_PROJ_STATE = {}          # (device, stream, T, B) -> hand-off counters of slu_gru_proj_seq_fwd (zeroed once, then launch-owned)
+# (device, stream, T, B, H, D) -> hand-off counters of slu_gru_proj_seq_fwd (zeroed once, then launch-owned).  The counters never
+# reset: a launch expects (launches so far + 1) * (D * 3H / 64) arrivals per row tile, so launches that share a state must share
+# D and H — two layers of one (T, B) with different D on one state let the second one read gx before it is written.
+_PROJ_STATE = {}
 
 
 def gru_proj_fused_ok(x2, w_ih, T, B, I, H, D):
@@ -1176,7 +1179,7 @@ def gru_proj_fused_ok(x2, w_ih, T, B, I, H, D):
     from . import pipeline as _pl
     if 0 < _pl.cu_split() < 64:         # consumers (<= 32 workgroups) + producers must be co-resident on the training partition
         return False
-    key = (x2.device.index, _stream(), T, B)
+    key = (x2.device.index, _stream(), T, B, H, D)
     return key in _PROJ_STATE or not torch.cuda.is_current_stream_capturing()
 
 
@@ -1185,7 +1188,7 @@ def gru_proj_seq_fwd(x2, w_ih, b_ih, w_hh_f, w_hh_r, b_hh_f, b_hh_r, T, B, I, H,
     to gemm + gru_seq_fwd."""
     L = _lib.load()
     dev = x2.device
-    key = (dev.index, _stream(), T, B)
+    key = (dev.index, _stream(), T, B, H, D)
     st = _PROJ_STATE.get(key)
     if st is None:
         st = _PROJ_STATE[key] = torch.zeros(L.slu_gru_proj_state_words(T, B), dtype=torch.int32, device=dev)

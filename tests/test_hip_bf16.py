@@ -130,8 +130,9 @@ def test_gemm_tn_bf16_vs_float64(ops, K, M, N, nsplit):
 @pytest.mark.parametrize("T,B,H", [(40, 64, 128), (23, 37, 128), (9, 5, 64), (300, 768, 128)])
 @pytest.mark.parametrize("nsplit", [3, 2, 1])
 def test_gru_bf16_vs_exact_fp32_kernel(ops, T, B, H, nsplit):
-    """slu_gru_seq_fwd_bf16 against the exact-fp32 persistent kernel (itself held to the oracle in
-    test_hip_ops / test_hip_bench_path): nsplit = 3 must agree to fp32 round-off accumulated over T steps."""
+    """slu_gru_seq_fwd_bf16 against the exact-fp32 persistent kernel: closeness of the two kernels to EACH OTHER — nsplit = 3
+    must agree to fp32 round-off accumulated over T steps.  Both are held to the float64 reference directly, on every
+    regime and at T = 300, in test_hip_gru_conformance.py."""
     torch.manual_seed(T + B)
     D = 2
     gx = torch.randn(T, B, D * 3 * H).cuda()
