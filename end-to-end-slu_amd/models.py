@@ -300,6 +300,42 @@ def _require_device(t):
 
 
 # ------------------------------------------------------------------------------------------------
+# weight-derived caches (DESIGN.md section 7 "Weight-derived caches"): ONE signature decides "did these weights change?"
+# ------------------------------------------------------------------------------------------------
+def thaw_count(module):
+    """How often `module` (a GRU / Conv1d / SincLayer) was seen TRAINABLE after a frozen-weight cache had been derived from
+    it (note_trainable).  Part of every weight signature: HipAdam writes parameters through raw pointers — under graph
+    replay with no Python at all — so a layer that was frozen, thawed, trained and frozen again comes back with the
+    (data_ptr, _version) it was cached under."""
+    return module.__dict__.get("_thaws", 0)
+
+
+def weight_signature(module, names=None, params=None):
+    """What every cache derived from FROZEN weights of `module` is keyed on: its thaw count and (data_ptr, _version) of its
+    own parameters (`names`: of those only; `params`: the caller already holds the list of ALL of them and spares the walk
+    of the module tree) — the Parameter objects themselves, never a tensor that merely shares their memory (a view made
+    through .data has a version counter of its own, which load_state_dict and in-place ops on the parameter do not move).
+    Host attribute reads only; works on CPU tensors."""
+    if params is None:
+        params = module.parameters() if names is None else (getattr(module, n) for n in names)
+    return (thaw_count(module),) + tuple((q.data_ptr(), q._version) for q in params)
+
+
+def note_frozen_cache(module):
+    """A cache derived from the frozen weights of `module` exists (or is about to) from now on."""
+    module.__dict__["_cached_frozen"] = True
+
+
+def note_trainable(module):
+    """`module` runs with (or was given) a trainable parameter: whatever was derived from its frozen weights is void.
+    Counted once per frozen -> trainable transition, so the signatures of a layer that keeps training do not move."""
+    if module.__dict__.get("_cached_frozen"):
+        module.__dict__["_cached_frozen"] = False
+        module.__dict__["_thaws"] = thaw_count(module) + 1
+        module.__dict__.pop("_packed_ih", None)
+
+
+# ------------------------------------------------------------------------------------------------
 # thin layer modules (API/state_dict compatibility; each also runs stand-alone)
 # ------------------------------------------------------------------------------------------------
 class Downsample(torch.nn.Module):
@@ -454,6 +490,20 @@ class GRU(torch.nn.Module):
             self._ih_storage = (W, b)
         return self._ih_storage
 
+    def packed_ih(self, w_ih, nsplit):
+        """bf16 planes of the frozen stacked W_ih (`w_ih` = _stacked_ih()[0], linked) in MFMA fragment order, rebuilt when
+        the weight changes: keyed on the layer's own ih PARAMETERS (weight_signature), not on the stacked storage, whose
+        version counter neither load_state_dict nor an in-place op on a parameter moves.  (The cache lives with the
+        weight's owner: a global table keyed by address would outlive the tensor.)"""
+        key = (nsplit,) + self.ih_signature()
+        if self.__dict__.get("_packed_ih", (None, None))[0] != key:
+            note_frozen_cache(self)
+            self.__dict__["_packed_ih"] = (key, _ops.gemm_bf16_pack(w_ih.detach(), nsplit))
+        return self.__dict__["_packed_ih"][1]
+
+    def ih_signature(self):
+        return weight_signature(self, ("weight_ih_l0", "weight_ih_l0_reverse") if self.bidirectional else ("weight_ih_l0",))
+
     def split_frozen(self):
         """nsplit (1 / 2 / 3) when this layer runs FROZEN on the split-precision kernels, else 0."""
         if any(q.requires_grad for q in self.parameters()):
@@ -466,13 +516,10 @@ class GRU(torch.nn.Module):
         frozen = not any(q.requires_grad for q in self.parameters())
         nsplit = contraction_nsplit(frozen)
         packed = None
+        if not frozen:
+            note_trainable(self)
         if nsplit and frozen and _ops.split_path_supported(self.hidden_size, 2 if self.bidirectional else 1):
-            # bf16 planes of the frozen W_ih in MFMA fragment order, rebuilt when the weight changes (the cache
-            # lives with the weight's owner: a global table keyed by address would outlive the tensor)
-            key = (nsplit, w_ih.data_ptr(), w_ih._version)
-            if getattr(self, "_packed_ih", (None, None))[0] != key:
-                self._packed_ih = (key, _ops.gemm_bf16_pack(w_ih.detach(), nsplit))
-            packed = self._packed_ih[1]
+            packed = self.packed_ih(w_ih, nsplit)
             if nsplit == 2 and _FrozenMath.scope is not None and not isinstance(xt, _ops.SplitAct):
                 # guarded f16x2 fed by an fp32 tensor no convolution launch has watched (a last CNN block with dropout,
                 # pool 2 or a channel count without plane output hands fp32 over): raise the guard's last word to this
@@ -1338,6 +1385,8 @@ class _ConvStage:
         drop = self.drop > 0.0 and training
         tm = self.time_major and not drop
         if any(q.requires_grad for q in self.parameters()) or h.requires_grad:
+            if any(q.requires_grad for q in self.parameters()):
+                note_trainable(self.conv)
             if self.is_sinc:
                 h = _ops.SincBlockLenFn.apply(h, self.conv.filt_b1, self.conv.filt_band, n_conv, self.conv.Filt_dim,
                                               self.conv.fs, self.conv.stride, self.pool, self.slope, tm, self.do_abs)
@@ -1367,7 +1416,8 @@ class _ConvStage:
         fragment order.  Kept per (weight version, arithmetic, HIP stream): a look-ahead slot's graph reads its own
         copy, built by that stream's first (eager) call, so no stream ever waits for another one's pack."""
         key = (nsplit, torch.cuda.current_stream().cuda_stream)
-        version = tuple((q.data_ptr(), q._version) for q in self.parameters())
+        version = weight_signature(self.conv)
+        note_frozen_cache(self.conv)
         caches = self.__dict__.setdefault("_caches", {})
         c = caches.get(key)
         if c is None or c["version"] != version:
@@ -1403,6 +1453,8 @@ class _ConvStage:
         # (a TRAINABLE block in bf16 mode takes bf16 operands inside ops.SincBlockFn / ConvBlockFn: forward on the bf16
         # kernel with the route bits, fp32 backward)
         nsplit = contraction_nsplit(True) if not any(q.requires_grad for q in self.parameters()) else 0
+        if any(q.requires_grad for q in self.parameters()):
+            note_trainable(self.conv)
         c_in = 1 if (self.is_sinc or h.dim() == 2) else h.shape[2]
         k_t = self.conv.Filt_dim if self.is_sinc else self.conv.kernel_size
         if (nsplit and fused_pool and not h.requires_grad
@@ -1475,10 +1527,7 @@ class _RnnStage:
         g, N = self.gru, w_ih.shape[0]
         if not _ops.gemm_a32_ok(x2, N, x2.shape[1]):
             return _ops.gemm(x2, w_ih.detach().t(), b_ih.detach())
-        key = (3, w_ih.data_ptr(), w_ih._version)
-        if getattr(g, "_packed_ih", (None, None))[0] != key:
-            g._packed_ih = (key, _ops.gemm_bf16_pack(w_ih.detach(), 3))
-        return _ops.gemm_a32(x2, g._packed_ih[1], b_ih.detach(), N, 3)
+        return _ops.gemm_a32(x2, g.packed_ih(w_ih, 3), b_ih.detach(), N, 3)
 
     def _recur_len(self, xt, n_in, reserve_op):
         """Projection + recurrence of the layer outside autograd (the caller holds no_grad): xt time-major (T, B, I), n_in
@@ -1515,6 +1564,8 @@ class _RnnStage:
         g = self.gru
         p, mask, seed, offset = _dropout_args(self.drop_name, self.site, self.p, training)
         if any(q.requires_grad for q in g.parameters()) or xt.requires_grad:
+            if any(q.requires_grad for q in g.parameters()):
+                note_trainable(g)
             w_ih, b_ih = g._stacked_ih()
             if g.bidirectional:
                 ih = (g.weight_ih_l0, g.weight_ih_l0_reverse, g.bias_ih_l0, g.bias_ih_l0_reverse)
@@ -1635,7 +1686,7 @@ class PretrainedModel(torch.nn.Module):
             return False
         if getattr(self, "_f16x2_pin", None) is not None:
             return False
-        sig = tuple((q.data_ptr(), q._version, q.requires_grad) for q in self.parameters())
+        sig = self.f16x2_signature()
         cached = getattr(self, "_f16x2_weights", None)
         if cached is None or cached[0] != sig:
             if torch.cuda.is_current_stream_capturing() or not next(self.parameters()).is_cuda:
@@ -1646,8 +1697,46 @@ class PretrainedModel(torch.nn.Module):
             if not ok:
                 print("frozen stages on bf16x3: a frozen weight tensor's largest entry (%.3g) is outside the f16x2 "
                       "scheme's range [%.3g, %.0f)" % (worst, _guard.WEIGHT_MIN, _guard.F16X2_LIMIT))
+            self._note_f16x2_verdict()
             cached = self._f16x2_weights = (sig, ok)
         return cached[1]
+
+    def _note_f16x2_verdict(self):
+        """The verdict is derived from the FROZEN stages' tensors alone (_frozen_split_tensors): only they are marked.  A
+        stage that trains beside them must not count a thaw at its next forward — its count is part of the verdict's own
+        signature and of the step-graph key, and either would move with every step."""
+        for m, ps in zip(self.stage_modules(), self.stage_parameters()):
+            if not any(q.requires_grad for q in ps):
+                note_frozen_cache(m)
+
+    def f16x2_signature(self):
+        """What the verdict of f16x2_allowed on the frozen weights' range is kept under."""
+        return (tuple((q.data_ptr(), q._version, q.requires_grad) for q in self.parameters()), self.thaw_signature())
+
+    def stage_modules(self):
+        """The parameter owner of every fused stage, in stage order: what weight_signature / thaw_count are asked of."""
+        mods = self.__dict__.get("_stage_mods")       # fixed after construction, like stage_parameters: built once
+        if mods is None:
+            mods = self.__dict__["_stage_mods"] = [st.conv if isinstance(st, _ConvStage) else st.gru for st in self._stages()]
+        return mods
+
+    def thaw_signature(self, n_stages=None):
+        """The thaw counts of the first n_stages stages (None: all)."""
+        return tuple(thaw_count(m) for m in self.stage_modules()[:n_stages])
+
+    def prefix_signature(self, n_prefix):
+        """What a captured look-ahead graph of stages [0, n_prefix) is kept under (pipeline.PrefixSlot.signature)."""
+        # from the cached parameter lists: the trainer asks in front of a run's first launch, where a walk of the module
+        # tree is host time the device idles through
+        return tuple(weight_signature(m, params=ps) for m, ps in zip(self.stage_modules()[:n_prefix], self.stage_parameters()))
+
+    def note_trainable_stages(self):
+        """Report every stage that is trainable NOW (note_trainable).  The trainer asks once per run, in front of its steps
+        (training._param_signature): a flag flipped by hand is otherwise seen by the stage's next trainable forward only,
+        and the replay of a step graph captured for an earlier thaw of the same layers runs none."""
+        for m, ps in zip(self.stage_modules(), self.stage_parameters()):
+            if any(q.requires_grad for q in ps):
+                note_trainable(m)
 
     def pin_bf16x3(self, why):
         """A range violation was observed: this model's frozen stages stay on bf16x3 from now on."""
@@ -1956,8 +2045,11 @@ def freeze_layer(layer):
 
 
 def unfreeze_layer(layer):
-    for param in layer.parameters():
+    params = list(layer.parameters())
+    for param in params:
         param.requires_grad = True
+    if params:                      # (the schedule also walks Dropout, pooling, ...: nothing is derived from those)
+        note_trainable(layer)       # (a flag flipped by hand: the layer's next trainable forward, or the trainer's next run)
 
 
 def has_params(layer):
@@ -2028,6 +2120,17 @@ class Model(torch.nn.Module):
         self.intent_layers = torch.nn.ModuleList(intent_layers)
         if self.is_cuda:
             self.cuda()
+
+    def thaw_signature(self):
+        """The encoder's thaw counts and the intent layers' (training._param_signature)."""
+        return self.pretrained_model.thaw_signature() + tuple(thaw_count(st.gru) for st in self._intent_stages)
+
+    def note_trainable_stages(self):
+        """PretrainedModel.note_trainable_stages, and the same of the intent layers."""
+        self.pretrained_model.note_trainable_stages()
+        for st in self._intent_stages:
+            if any(q.requires_grad for q in st.gru.parameters()):
+                note_trainable(st.gru)
 
     # -- freezing schedule (reference models.py:738-795) -----------------------------------------
     def freeze_all_layers(self):

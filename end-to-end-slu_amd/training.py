@@ -98,8 +98,15 @@ def _graph_forks():
 
 def _param_signature(model):
     """Per parameter: None = trainable, else the frozen tensor's version.  (Not True for trainable: True == 1, so a
-    parameter frozen at version 1 and the same parameter unfrozen gave equal — and equally hashed — signatures.)"""
-    return tuple(None if p.requires_grad else p._version for p in model.parameters())
+    parameter frozen at version 1 and the same parameter unfrozen gave equal — and equally hashed — signatures.)
+    Behind them the stages' thaw counts (models.thaw_count): the optimiser's kernels move no version, so a layer that was
+    trained and frozen again differs from its earlier frozen self by that count alone.  Asked once per run, in front of its
+    steps; the stages that are trainable now are reported first (note_trainable_stages): a step graph captured for an
+    earlier thaw of the same layers would otherwise be found under this key and replayed, and a replay runs no forward
+    that could report them."""
+    getattr(model, "note_trainable_stages", tuple)()
+    thaws = getattr(model, "thaw_signature", tuple)()
+    return tuple(None if p.requires_grad else p._version for p in model.parameters()) + (thaws,)
 
 
 def _lookahead_width(depth, batch_size):
@@ -721,7 +728,7 @@ class Trainer:
         pm = self.model.pretrained_model
         with torch.cuda.stream(main):
             pm.warm_weight_caches()
-        signature = tuple(p._version for ps in pm.stage_parameters()[:n_prefix] for p in ps)
+        signature = pm.prefix_signature(n_prefix)
         for slot in self._slots:
             if slot.signature != signature:          # frozen weights were reloaded: re-capture
                 slot.invalidate()
