@@ -39,20 +39,27 @@ from slu_hip import lexicon as _lexicon
 
 # ------------------------------------------------------------------------------------------------
 # dropout control (train-mode masks): Philox in-kernel by default, injected masks for parity tests
+# What a site draws is ONE value, ops.DropStream(seed, offset, offset_dev, sub_batch), derived by _rng_stream(site) alone
+# for the step of the `with _rng_step(step, sub_batch):` scope around it, which alone writes current / current_dev / sub_batch.
 # ------------------------------------------------------------------------------------------------
 class _DropoutState:
     masks = None        # dict: layer name ("phone_dropout0", ...) -> float {0,1} mask, logical (B,T,C)
     seed = None         # None -> torch.initial_seed()
     step = 0            # index of the last top-level forward; Philox offset = step * 16 + dropout site
-    current = 0         # step the stages running right now belong to
-    current_dev = None  # or: 1-element int64 CUDA tensor holding step*16 (hipGraph-captured stages)
-    sub_batch = 0       # > 0: the batch is several steps' batches concatenated (consecutive steps)
+    current = 0         # step of the last _rng_step scope entered with a host step (kept once it is left)
+    current_dev = None  # inside a scope of a captured step: 1-element int64 CUDA tensor holding step*16
+    sub_batch = 0       # inside a scope, > 0: the batch is several steps' batches concatenated (consecutive steps)
 
 
 def set_dropout_masks(masks):
     """Parity hook: use these keep-masks (as `torch.nn.Dropout` would have drawn them, logical
     shape (B,T,C)) instead of the in-kernel Philox stream.  Pass None to restore Philox."""
     _DropoutState.masks = masks
+
+
+def dropout_masks_injected():
+    """Are set_dropout_masks' masks in force (no Philox draw, so nothing for a captured or pipelined step to replay)?"""
+    return _DropoutState.masks is not None
 
 
 def set_dropout_seed(seed):
@@ -70,21 +77,52 @@ def next_rng_step():
     return _DropoutState.step
 
 
-def _dropout_args(name, site, p, training, cnn=False):
-    """-> (p_eff, mask_time_major_or_None, seed, offset)"""
-    if not training or p == 0.0:
-        return 0.0, None, 0, 0
-    if _DropoutState.masks is not None:
-        m = _DropoutState.masks[name]
-        if cnn:                                    # reference shape (B,C,L) -> channels-last (B,L,C)
-            return p, m.transpose(1, 2).contiguous(), 0, 0
-        return p, m.transpose(0, 1), 0, 0          # (T,B,C) view; kernel takes its strides
+@contextlib.contextmanager
+def rng_step_held():
+    """What runs inside reserves no dropout step of the run around it: the step counter is put back on the way out."""
+    step = _DropoutState.step
+    try:
+        yield
+    finally:
+        _DropoutState.step = step
+
+
+@contextlib.contextmanager
+def _rng_step(rng_step=None, sub_batch=0):
+    """The enclosed stages belong to dropout step `rng_step`: an integer; None = the next one; anything else is taken, on
+    purpose unchecked, as the device word of a captured step (1-element int64 CUDA tensor holding step*16; the host only
+    hands it on, so host-side tests pass a stand-in).  On the way out, normally or not, the word and the sub-batch are what
+    they were outside (None, 0); `current` KEEPS its value: _enter_len's callers and a stand-alone DecoderRNN.forward use it."""
+    S = _DropoutState
+    outer = (S.current_dev, S.sub_batch)
+    if rng_step is None or isinstance(rng_step, int):
+        S.current, S.current_dev = (next_rng_step() if rng_step is None else rng_step), None
+    else:
+        S.current_dev = rng_step
+    S.sub_batch = sub_batch
+    try:
+        yield
+    finally:
+        S.current_dev, S.sub_batch = outer
+
+
+def _rng_stream(site, key=0):
+    """-> ops.DropStream of site `site` for the enclosing _rng_step scope: offset = step*16 + site, or site beside its device word"""
     seed = _DropoutState.seed if _DropoutState.seed is not None else torch.initial_seed()
+    seed = (seed & 0xFFFFFFFFFFFFFFFF) ^ key
     if _DropoutState.current_dev is not None:
-        return p, None, seed & 0xFFFFFFFFFFFFFFFF, (site, _DropoutState.current_dev, _DropoutState.sub_batch)
-    if _DropoutState.sub_batch:
-        return p, None, seed & 0xFFFFFFFFFFFFFFFF, (_DropoutState.current * 16 + site, None, _DropoutState.sub_batch)
-    return p, None, seed & 0xFFFFFFFFFFFFFFFF, _DropoutState.current * 16 + site
+        return _ops.DropStream(seed, site, _DropoutState.current_dev, _DropoutState.sub_batch)
+    return _ops.DropStream(seed, _DropoutState.current * 16 + site, None, _DropoutState.sub_batch)
+
+
+def _dropout_args(name, site, p, training, cnn=False):
+    """-> (p_eff, mask_time_major_or_None, stream); ops.NO_STREAM where nothing is drawn"""
+    if not training or p == 0.0:
+        return 0.0, None, _ops.NO_STREAM
+    if _DropoutState.masks is not None:
+        m = _DropoutState.masks[name]    # cnn: reference shape (B,C,L) -> channels-last (B,L,C); else a (T,B,C) view (strided)
+        return p, m.transpose(1, 2).contiguous() if cnn else m.transpose(0, 1), _ops.NO_STREAM
+    return p, None, _rng_stream(site)
 
 
 # 16 dropout sites per step (Philox offset = step * 16 + site).  The seq2seq head replaces the intent stack, so its encoder
@@ -119,12 +157,7 @@ def _augment(x, training_augment):
     same stream: its factor comes from a Philox block of its own, so the other effects' draws do not move."""
     if not training_augment:
         return x
-    seed = (_DropoutState.seed if _DropoutState.seed is not None else torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
-    flags = _ops.augment_flags()
-    if _DropoutState.current_dev is not None:
-        stream = (seed ^ AUGMENT_KEY, 0, _DropoutState.current_dev, _DropoutState.sub_batch)
-    else:
-        stream = (seed ^ AUGMENT_KEY, _DropoutState.current * 16, None, _DropoutState.sub_batch)
+    flags, stream = _ops.augment_flags(), _rng_stream(0, AUGMENT_KEY)
     with torch.no_grad():
         if _ops.tempo_enabled():                  # SLU_AUGMENT_TEMPO=1: the reference's order tempo -> gain -> crop -> noise
             x = _ops.wave_tempo(x, *stream)
@@ -378,20 +411,18 @@ class _DropOnlyFn(torch.autograd.Function):
     factor 1.  The kernel's (T,B,C) indexing is applied to the tensor as it lies in memory."""
 
     @staticmethod
-    def forward(ctx, x, p, mask, seed, offset):
-        offset, offset_dev, sub_batch = offset if isinstance(offset, tuple) else (offset, None, 0)
-        if sub_batch:
+    def forward(ctx, x, p, mask, stream):
+        if stream.sub_batch:
             raise NotImplementedError("CNN dropout inside a look-ahead super-batch")
-        ctx.cfg = (p, seed, offset)
-        ctx.offset_dev = offset_dev
+        ctx.cfg = (p, stream)                      # stream.offset_dev: a persistent buffer, not a graph tensor
         ctx.save_for_backward(x, mask)
-        return _ops.dropout_pool_fwd(x, mask, p, seed, offset, "none", 1, offset_dev, 0)
+        return _ops.dropout_pool_fwd(x, mask, p, stream.seed, stream.offset, "none", 1, stream.offset_dev, 0)
 
     @staticmethod
     def backward(ctx, dy):
-        p, seed, offset = ctx.cfg
+        p, stream = ctx.cfg
         x, mask = ctx.saved_tensors
-        return _ops.dropout_pool_bwd(dy, x, mask, p, seed, offset, "none", 1, ctx.offset_dev), None, None, None, None
+        return _ops.dropout_pool_bwd(dy, x, mask, p, stream.seed, stream.offset, "none", 1, stream.offset_dev), None, None, None
 
 
 class SincLayer(torch.nn.Module):
@@ -511,7 +542,7 @@ class GRU(torch.nn.Module):
         nsplit = contraction_nsplit(True)
         return nsplit if _ops.split_path_supported(self.hidden_size, 2 if self.bidirectional else 1) else 0
 
-    def run_time_major(self, xt, p=0.0, mask=None, seed=0, offset=0, method="none", factor=1, out_planes=False):
+    def run_time_major(self, xt, p=0.0, mask=None, stream=_ops.NO_STREAM, method="none", factor=1, out_planes=False):
         w_ih, b_ih = self._stacked_ih()
         frozen = not any(q.requires_grad for q in self.parameters())
         nsplit = contraction_nsplit(frozen)
@@ -530,7 +561,7 @@ class GRU(torch.nn.Module):
                 rev = (self.weight_hh_l0_reverse, self.bias_hh_l0_reverse) if self.bidirectional else (None, None)
                 with torch.no_grad():
                     return _ops.gru_layer_frozen(xt, w_ih, b_ih, packed, self.weight_hh_l0, self.bias_hh_l0, rev[0],
-                                                 rev[1], p, mask, seed, offset, method, factor, nsplit, out_planes)
+                                                 rev[1], p, mask, stream, method, factor, nsplit, out_planes)
         if self.bidirectional:
             ih = (self.weight_ih_l0, self.weight_ih_l0_reverse, self.bias_ih_l0, self.bias_ih_l0_reverse)
             rev = (self.weight_hh_l0_reverse, self.bias_hh_l0_reverse)
@@ -538,7 +569,7 @@ class GRU(torch.nn.Module):
             ih = (self.weight_ih_l0, None, self.bias_ih_l0, None)
             rev = (None, None)
         return _ops.GRULayerFn.apply(xt, w_ih.detach(), b_ih.detach(), *ih, self.weight_hh_l0, self.bias_hh_l0,
-                                     rev[0], rev[1], p, mask, seed, offset, method, factor, nsplit, packed)
+                                     rev[0], rev[1], p, mask, *stream[:2], method, factor, nsplit, packed, *stream[2:])
 
     def forward(self, x):
         _require_device(x)
@@ -612,8 +643,8 @@ class Seq2SeqEncoder(torch.nn.Module):
     def forward(self, x):
         """(B, T, C) -> (B, T, 2 * encoder_dim)"""
         _require_device(x)
-        _DropoutState.current = next_rng_step()
-        return self.run_time_major(x.transpose(0, 1), self.training).transpose(0, 1)
+        with _rng_step():
+            return self.run_time_major(x.transpose(0, 1), self.training).transpose(0, 1)
 
 
 class Attention(torch.nn.Module):
@@ -688,8 +719,7 @@ class DecoderRNN(torch.nn.Module):
             B = x_in.shape[0]
             dev = x_in.device
             state = torch.empty(B, Lc, Dd, dtype=torch.float32, device=dev)
-            seed = _DropoutState.seed if _DropoutState.seed is not None else torch.initial_seed()
-            offset = _DropoutState.current * 16 + _DECODER_SITE
+            stream = _rng_stream(_DECODER_SITE)          # the last step's: a stand-alone call reserves none
             for l, cell in enumerate(cells):
                 gi = torch.empty(B, 3 * Dd, dtype=torch.float32, device=dev)
                 gh = torch.empty(B, 3 * Dd, dtype=torch.float32, device=dev)
@@ -697,8 +727,7 @@ class DecoderRNN(torch.nn.Module):
                                          (prev[:, l], cell.weight_hh.detach(), cell.bias_hh.detach(), gh, 0, 0)])
                 p = self.dropout if (self.training and l < Lc - 1) else 0.0
                 drop = torch.empty(B, Dd, dtype=torch.float32, device=dev) if p > 0.0 else None
-                _ops.gru_cell_fwd(gi, gh, prev[:, l], state[:, l], None, drop, None, p, seed & 0xFFFFFFFFFFFFFFFF, offset,
-                                  None, l * B * Dd)
+                _ops.gru_cell_fwd(gi, gh, prev[:, l], state[:, l], None, drop, None, p, *stream[:3], l * B * Dd)
                 x_in = drop if drop is not None else state[:, l]
         return state
 
@@ -749,7 +778,7 @@ class _StepScratch:
         self.q, self.inp0, self.att_w, self.logits = f(R, Kd), f(R, E + Vd), f(R, T), f(R, V)
         self.gi, self.gh, self.drop = f(R, 3 * Dd), f(Lc, R, 3 * Dd), [f(R, Dd) for _ in range(Lc - 1)]
         self.n_rows = torch.full((R,), T, dtype=torch.int32, device=dev) if with_lengths else None
-        self.no_dropout = (0.0, None, 0, 0, None, R * Dd)               # ops.decoder_step's drop_cfg
+        self.no_dropout = (0.0, None, _ops.NO_STREAM, R * Dd)           # ops.decoder_step's drop_cfg
 
     def fill_memory(self, P, enc2, T, W, bsz, n_host):
         """The encoder memory of a call: keys / values once, replicated per slot; the rows' frame counts (one copy)."""
@@ -772,7 +801,7 @@ class _StepScratch:
         for name, dim in self.ROW_DIM.items():
             t = getattr(self, name)
             setattr(v, name, None if t is None else t.narrow(dim, 0, r))
-        v.drop, v.no_dropout = [t[:r] for t in self.drop], self.no_dropout[:5] + (r * self.Dd,)
+        v.drop, v.no_dropout = [t[:r] for t in self.drop], self.no_dropout[:3] + (r * self.Dd,)
         return v
 
     def step(self, P, y_prev=None, step=0):
@@ -839,24 +868,13 @@ class Seq2SeqDecoder(torch.nn.Module):
 
     def teacher_forced(self, enc_tm, y, n_dev=None):
         """enc_tm time-major (T, B, 2 * encoder_dim), y (B, U, num_labels) -> (loss_acc (2) = [-mean log p, 0],
-        log_p (B)) on the current dropout step (models._DropoutState).  n_dev (None: dense): int32 device tensor of B
+        log_p (B)) on the dropout step of the _rng_step scope around the call.  n_dev (None: dense): int32 device tensor of B
         encoder frame counts, already validated -> the attention of row b ranges over its first n_dev[b] frames."""
         p = self.rnn.dropout if self.training else 0.0
-        masks, seed, offset, offset_dev = None, 0, 0, None
-        if p > 0.0:
-            if _DropoutState.masks is not None:
-                masks = _DropoutState.masks
-            else:
-                seed = (_DropoutState.seed if _DropoutState.seed is not None else torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
-                if _DropoutState.current_dev is not None:
-                    offset, offset_dev = _DECODER_SITE, _DropoutState.current_dev
-                else:
-                    offset = _DropoutState.current * 16 + _DECODER_SITE
+        masks = _DropoutState.masks if p > 0.0 else None
+        stream = _rng_stream(_DECODER_SITE) if p > 0.0 and masks is None else _ops.NO_STREAM
         names, tensors = self._params()
-        meta = (names, self.SOS, p, masks, seed, offset, offset_dev)
-        if n_dev is not None:
-            meta += (n_dev,)
-        return _ops.Seq2SeqDecoderFn.apply(enc_tm, y, meta, *tensors)
+        return _ops.Seq2SeqDecoderFn.apply(enc_tm, y, (names, self.SOS, p, masks, stream, n_dev), *tensors)
 
     def forward(self, encoder_outputs, y, y_lengths=None, enc_lengths=None):
         """encoder_outputs (B, T, 2 * encoder_dim), y (B, U, num_labels) one-hot, padded with <eos> -> log p(y|x) (B)
@@ -869,8 +887,8 @@ class Seq2SeqDecoder(torch.nn.Module):
         _require_device(encoder_outputs)
         if n is not None:
             n = torch.tensor(n, dtype=torch.int32).to(encoder_outputs.device, non_blocking=True)
-        _DropoutState.current = next_rng_step()
-        _, log_p = self.teacher_forced(encoder_outputs.transpose(0, 1), y, n)
+        with _rng_step():
+            _, log_p = self.teacher_forced(encoder_outputs.transpose(0, 1), y, n)
         return log_p
 
     def _decode_setup(self, encoder_outputs, Sy, eos, y_lengths, enc_lengths, lexicon, want_lengths, sweep=False):
@@ -1253,21 +1271,19 @@ def _enter_len(pm, x, lengths, stages, train_ok=False, rng_step=None, augment=Fa
         _refuse_trainable_cnn_lengths(pm._cnn_stages)
     (x,) = pm._to_device(x)
     pm._cnn_stages[-1].time_major = True
-    if train_ok:
-        _DropoutState.current = next_rng_step() if rng_step is None else rng_step
-    with torch.no_grad():
+    with _rng_step(rng_step) if train_ok else contextlib.nullcontext(), torch.no_grad():
         if not (augment and x.dtype == torch.int16):
             x = _ops.pcm16_to_f32(x) if x.dtype == torch.int16 else x.float()
         n_dev = torch.tensor(host, dtype=torch.int32).to(x.device, non_blocking=True)
         if not augment:
             return _ops.mask_rows_len(x, n_dev), host                # the first stage's input tail
-        seed = ((_DropoutState.seed if _DropoutState.seed is not None else torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF) ^ AUGMENT_KEY
-        flags, offset, sub = _ops.augment_flags(), _DropoutState.current * 16, _DropoutState.sub_batch
+        flags, stream = _ops.augment_flags(), _rng_stream(0, AUGMENT_KEY)
+        mirror = (stream.seed, stream.offset, stream.sub_batch)      # a host step (above): no device word to mirror
         if _ops.tempo_enabled():
-            x, n_dev = _ops.wave_tempo_len(x, n_dev, seed, offset, None, sub)
-            host = _ops.tempo_out_lengths(host, T, seed, offset, sub)
-        x, _ = _ops.wave_augment_len(x, n_dev, flags, seed, offset, None, sub)
-        return x, _ops.augment_out_lengths(host, T, flags, seed, offset, sub)
+            x, n_dev = _ops.wave_tempo_len(x, n_dev, *stream)
+            host = _ops.tempo_out_lengths(host, T, *mirror)
+        x, _ = _ops.wave_augment_len(x, n_dev, flags, *stream)
+        return x, _ops.augment_out_lengths(host, T, flags, *mirror)
 
 
 # what _run_stages_len returns: the last stage's output, its valid lengths on the host and on the device (a row of the
@@ -1407,8 +1423,7 @@ class _ConvStage:
         the channels-last tensor, from the same step-indexed Philox stream as the RNN sites (or the injected mask, given in
         the reference's (B,C,L) shape) — then the hand-over to time-major where the kernels did not write it (tm)."""
         if self.drop > 0.0 and training:
-            p, mask, seed, offset = _dropout_args(self.drop_name, self.site, self.drop, training, cnn=True)
-            h = _DropOnlyFn.apply(h.contiguous(), p, mask, seed, offset)
+            h = _DropOnlyFn.apply(h.contiguous(), *_dropout_args(self.drop_name, self.site, self.drop, training, cnn=True))
         return h.transpose(0, 1).contiguous() if self.time_major and not tm else h
 
     def _frozen_cache(self, nsplit):
@@ -1507,8 +1522,8 @@ class _RnnStage:
 
     def run(self, xt, training, out_planes=False):
         """out_planes: the consumer is another frozen split-precision GRU layer: hand over bf16 planes."""
-        p, mask, seed, offset = _dropout_args(self.drop_name, self.site, self.p, training)
-        return self.gru.run_time_major(xt, p, mask, seed, offset, self.method, self.factor, out_planes)
+        p, mask, stream = _dropout_args(self.drop_name, self.site, self.p, training)
+        return self.gru.run_time_major(xt, p, mask, stream, self.method, self.factor, out_planes)
 
     def out_len(self, n):
         """Valid frames behind the layer's Downsample: ceil(n / factor) for every method (the GRU keeps n)."""
@@ -1562,7 +1577,7 @@ class _RnnStage:
         ops.GRULayerLenFn (exact fp32); a frozen one runs the same kernels outside autograd, without a reserve — or, as in
         run_len, its projection and recurrence on bf16x3 (the dropout + pooling launch, and so every draw, is the same)."""
         g = self.gru
-        p, mask, seed, offset = _dropout_args(self.drop_name, self.site, self.p, training)
+        p, mask, stream = _dropout_args(self.drop_name, self.site, self.p, training)
         if any(q.requires_grad for q in g.parameters()) or xt.requires_grad:
             if any(q.requires_grad for q in g.parameters()):
                 note_trainable(g)
@@ -1573,13 +1588,12 @@ class _RnnStage:
             else:
                 ih, rev = (g.weight_ih_l0, None, g.bias_ih_l0, None), (None, None)
             return _ops.GRULayerLenFn.apply(xt, w_ih.detach(), b_ih.detach(), *ih, g.weight_hh_l0, g.bias_hh_l0, rev[0],
-                                            rev[1], n_in, p, mask, seed, offset, self.method, self.factor)
+                                            rev[1], n_in, p, mask, *stream[:2], self.method, self.factor, *stream[2:])
         with torch.no_grad():
             out = self._recur_len(xt, n_in, True)
             if p > 0.0 or self.factor > 1:
-                offset, offset_dev, sub_batch = offset if isinstance(offset, tuple) else (offset, None, 0)
-                assert sub_batch == 0
-                out = _ops.dropout_pool_len_fwd(out, n_in, mask, p, seed, offset, self.method, self.factor, offset_dev)
+                assert stream.sub_batch == 0
+                out = _ops.dropout_pool_len_fwd(out, n_in, mask, p, *stream[:2], self.method, self.factor, stream.offset_dev)
             return out
 
 
@@ -1869,11 +1883,7 @@ class PretrainedModel(torch.nn.Module):
         if lengths is not None:
             return self._forward_len(x, y_phoneme, y_word, lengths, rng_step)
         x, y_phoneme, y_word = self._to_device(x, y_phoneme, y_word)
-        if torch.is_tensor(rng_step):
-            _DropoutState.current_dev = rng_step
-        else:
-            _DropoutState.current = next_rng_step() if rng_step is None else rng_step
-        try:
+        with _rng_step(rng_step):
             ph_tm = self._phoneme_features_tm(x)                         # (T',B,C)
             # Linear + cross-entropy(ignore_index=-1) + frame accuracy: slu_gemm_f32 + slu_frame_ce_fwd
             pl = self.phoneme_linear
@@ -1884,8 +1894,6 @@ class PretrainedModel(torch.nn.Module):
             wl = self.word_linear
             word_loss, word_acc = _ops.FrameHeadFn.apply(wd_tm, wl.weight, wl.bias, y_word)
             return phoneme_loss, word_loss, phoneme_acc, word_acc
-        finally:
-            _DropoutState.current_dev = None
 
     def _forward_len(self, x, y_phoneme, y_word, lengths, rng_step):
         """forward with per-utterance lengths (DESIGN.md section 7 "Lengths through ASR pre-training"): the waveform tail
@@ -1993,9 +2001,9 @@ class PretrainedModel(torch.nn.Module):
         if lengths is not None:
             return self._posteriors_len(x, lengths)
         (x,) = self._to_device(x)
-        _DropoutState.current = next_rng_step()
-        ph_tm = self._phoneme_features_tm(x)
-        wd_tm = self._word_features_tm(ph_tm)
+        with _rng_step():
+            ph_tm = self._phoneme_features_tm(x)
+            wd_tm = self._word_features_tm(ph_tm)
 
         def head(lin, h_tm):                       # Linear on every frame: slu_gemm_f32 (no gradient path: inference)
             T, B, C = h_tm.shape
@@ -2026,8 +2034,8 @@ class PretrainedModel(torch.nn.Module):
         if lengths is not None:
             return self._features_tm_len(x, lengths).out.transpose(0, 1)
         (x,) = self._to_device(x)
-        _DropoutState.current = next_rng_step()
-        return self._features_tm(x).transpose(0, 1)
+        with _rng_step():
+            return self._features_tm(x).transpose(0, 1)
 
 
 def _as_int_list(lengths):
@@ -2163,10 +2171,10 @@ class Model(torch.nn.Module):
 
     # -- forward paths ---------------------------------------------------------------------------
     def _intent_features_tm(self, x):
-        _DropoutState.current = next_rng_step()
-        h = self.pretrained_model._features_tm(self.pretrained_model._to_device(x)[0])
-        for st in self._intent_stages:
-            h = st.run(h, self.training)
+        with _rng_step():
+            h = self.pretrained_model._features_tm(self.pretrained_model._to_device(x)[0])
+            for st in self._intent_stages:
+                h = st.run(h, self.training)
         return h                                                 # (T,B,C) time-major
 
     def _intent_features_tm_len(self, x, lengths):
@@ -2184,8 +2192,8 @@ class Model(torch.nn.Module):
         if lengths is None:
             return self._intent_features_tm(x), None, None
         out = self._intent_features_tm_len(x, lengths)
-        _DropoutState.current = next_rng_step()
-        return out
+        with _rng_step():                # nothing to enclose: the scope only reserves the call's step and sets `current`
+            return out
 
     # -- split execution for the trainer's encoder look-ahead pipeline ---------------------------
     def frozen_prefix_len(self):
@@ -2200,27 +2208,14 @@ class Model(torch.nn.Module):
         dropout kernels then read the step from device memory at replay time).
         sub_batch > 0: x is the concatenation of several upcoming batches of that size belonging to
         consecutive steps rng_step, rng_step+1, ...; each draws its own step's dropout masks."""
-        with torch.no_grad():
-            if torch.is_tensor(rng_step):
-                _DropoutState.current_dev = rng_step
-            else:
-                _DropoutState.current = rng_step
-            _DropoutState.sub_batch = sub_batch
-            try:
-                x = _augment(self.pretrained_model._to_device(x)[0], self.augment and self.training)
-                return self.pretrained_model.run_stages(x, 0, n_stages)
-            finally:
-                _DropoutState.current_dev = None
-                _DropoutState.sub_batch = 0
+        with torch.no_grad(), _rng_step(rng_step, sub_batch):
+            x = _augment(self.pretrained_model._to_device(x)[0], self.augment and self.training)
+            return self.pretrained_model.run_stages(x, 0, n_stages)
 
     def forward_from(self, h, n_stages, y_intent, rng_step):
         """The rest of Model.forward given the output of stages [0, n_stages)."""
         pm = self.pretrained_model
-        if torch.is_tensor(rng_step):              # hipGraph capture: step*16 lives on the device
-            _DropoutState.current_dev = rng_step
-        else:
-            _DropoutState.current = rng_step
-        try:
+        with _rng_step(rng_step):                  # a tensor under hipGraph capture: step*16 lives on the device
             if n_stages == 0:
                 h = _augment(h, self.augment and self.training)
             h = pm.run_stages(h, n_stages, len(pm._stages()))
@@ -2230,18 +2225,15 @@ class Model(torch.nn.Module):
                 if last:
                     # the Dropout in front of the classifier is drawn inside the head kernels (same Philox stream, same
                     # bits as the stand-alone launch; two launches fewer per step) where ops.head_dropout_fusable allows
-                    p, mask, seed, offset = _dropout_args(st.drop_name, st.site, st.p, self.training)
-                    if _ops.head_dropout_fusable(self.intent_layers[-2].weight, p, mask, st.method, st.factor):
-                        off, off_dev, sub = offset if isinstance(offset, tuple) else (offset, None, 0)
-                        if sub == 0:
-                            drop = (p, seed, off, off_dev)
-                            h = st.gru.run_time_major(h, 0.0, None, 0, 0, st.method, st.factor, False)
-                            continue
+                    p, mask, stream = _dropout_args(st.drop_name, st.site, st.p, self.training)
+                    fusable = _ops.head_dropout_fusable(self.intent_layers[-2].weight, p, mask, st.method, st.factor)
+                    if fusable and stream.sub_batch == 0:
+                        drop = (p,) + stream[:3]
+                        h = st.gru.run_time_major(h, 0.0, None, _ops.NO_STREAM, st.method, st.factor, False)
+                        continue
                 h = st.run(h, self.training)
             if self.seq2seq:                       # teacher-forced decoder on the same dropout step
                 loss_acc, _ = self.decoder.teacher_forced(h, y_intent.to(h.device))
-        finally:
-            _DropoutState.current_dev = None
         if self.seq2seq:
             # loss = -mean log p(y|x); the reference returns a host zero for the accuracy (models.py:825-828)
             self.last_loss_acc = loss_acc
@@ -2265,7 +2257,7 @@ class Model(torch.nn.Module):
             return self._forward_len(x, y_intent, lengths, rng_step, n_prefix)
         if n_prefix == 0:
             x = self.pretrained_model._to_device(x)[0]
-        return self.forward_from(x, n_prefix, y_intent, next_rng_step() if rng_step is None else rng_step)
+        return self.forward_from(x, n_prefix, y_intent, rng_step)
 
     def _forward_len(self, x, y_intent, lengths, rng_step, n_prefix):
         """Model.forward with per-utterance lengths (DESIGN.md section 7 "Lengths"): the waveform tail is zeroed, every

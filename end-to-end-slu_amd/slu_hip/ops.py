@@ -7,6 +7,7 @@ Layouts used between kernels (the host mirror in models.py converts at the modul
 torch is plumbing here: it owns the device buffers, the stream and the autograd tape.  All
 arithmetic of the hot path happens in libslu_hip.so; there is no fallback path.
 """
+import collections
 import contextlib
 import ctypes
 import math
@@ -18,6 +19,16 @@ from . import knobs as _knobs
 from . import lib as _lib
 
 METHODS = {"none": 0, "avg": 1, "max": 2}
+
+# A site's Philox stream for one step (models._rng_stream), C ABI order; offset_dev: a persistent buffer, never save_for_backward
+DropStream = collections.namedtuple("DropStream", "seed offset offset_dev sub_batch")
+NO_STREAM = DropStream(0, 0, None, 0)
+
+
+def _step_word_ok(p, mask, offset_dev):
+    """GRULayerFn / GRULayerLenFn: a captured Philox draw without the step's device word would replay ONE step's mask for ever."""
+    if p > 0.0 and mask is None and offset_dev is None and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("a Philox dropout draw inside a graph capture needs the step's device word: pass *stream[2:] too")
 
 
 def bf16_mode():
@@ -887,7 +898,7 @@ def gru_seq_fwd_pool_bf16(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, T, B, H, D, nsplit
     return SplitAct(planes, T_out, B, D * H) if out_planes else out
 
 
-def gru_layer_frozen(x, w_ih, b_ih, packed_ih, w_hh_f, b_hh_f, w_hh_r, b_hh_r, p, mask, seed, offset, method, factor,
+def gru_layer_frozen(x, w_ih, b_ih, packed_ih, w_hh_f, b_hh_f, w_hh_r, b_hh_r, p, mask, stream, method, factor,
                      nsplit, out_planes):
     """A FROZEN GRU layer + Dropout + Downsample on the split-precision kernels, outside autograd.
     x: fp32 (T, B, I) or a SplitAct; out_planes: return a SplitAct for the next frozen layer (when the pooled
@@ -903,10 +914,9 @@ def gru_layer_frozen(x, w_ih, b_ih, packed_ih, w_hh_f, b_hh_f, w_hh_r, b_hh_r, p
     packed = packed_ih if packed_ih is not None else gemm_bf16_pack(w_ih, nsplit)
     # the mask of a frozen layer is a bit stream (dropout_bits) whichever kernel applies it; injected float masks (parity
     # tests) and channel counts without whole 32-bit words keep the in-kernel Philox / float-mask forms
-    off, off_dev, sub = offset if isinstance(offset, tuple) else (offset, None, 0)
     keep = None
     if p > 0.0 and mask is None and (D * H) % 32 == 0 and T <= 65535:
-        keep = dropout_bits(T, B, D * H, p, seed, off, off_dev, sub, w_hh_f.device)
+        keep = dropout_bits(T, B, D * H, p, *stream, w_hh_f.device)
     if gru_pool_fused_ok(H, D, T, p, mask, method, factor):
         # Dropout + Downsample(avg, 2) in the recurrence's epilogue: no fp32 (T, B, D*H) output, no pool launch
         to_planes = bool(out_planes) and -(-T // factor) <= 65535
@@ -923,10 +933,10 @@ def gru_layer_frozen(x, w_ih, b_ih, packed_ih, w_hh_f, b_hh_f, w_hh_r, b_hh_r, p
         gx = gemm_bf16(planes, packed, b_ih, D * 3 * H, I)
         raw, _ = gru_seq_fwd_bf16(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, T, B, H, D, nsplit, False)
     if out_planes and (D * H) % 32 == 0 and -(-T // factor) <= 65535:
-        return dropout_pool_fwd_planes(raw, mask, p, seed, off, method, factor, nsplit, off_dev, sub, keep_bits=keep)
+        return dropout_pool_fwd_planes(raw, mask, p, *stream[:2], method, factor, nsplit, *stream[2:], keep_bits=keep)
     if p == 0.0 and factor == 1:
         return raw
-    return dropout_pool_fwd(raw, mask, p, seed, off, method, factor, off_dev, sub, keep_bits=keep)
+    return dropout_pool_fwd(raw, mask, p, *stream[:2], method, factor, *stream[2:], keep_bits=keep)
 
 
 def absmax_into(t, word_ptr):
@@ -1601,8 +1611,8 @@ class IntentHeadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, weight, bias, y, values_per_slot, drop=None):
-        """drop: None, or (p, seed, offset, offset_dev): h is the RAW output of the last intent GRU layer and the
-        Dropout in front of the classifier (models.py:700) is drawn inside the head kernels (forward and backward)."""
+        """drop: None, or (p, seed, offset, offset_dev) = (p, *stream[:3]): h is the RAW output of the last intent GRU layer
+        and the Dropout in front of the classifier (models.py:700) is drawn inside the head kernels (forward and backward)."""
         h = h.contiguous()
         y = y.contiguous()
         need = any(ctx.needs_input_grad[:3])
@@ -2267,10 +2277,11 @@ class GRULayerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w_ih, b_ih, w_ih_f, w_ih_r, b_ih_f, b_ih_r, w_hh_f, b_hh_f, w_hh_r, b_hh_r,
-                p, mask, seed, offset, method, factor, nsplit=0, packed_ih=None):
-        """nsplit: 0 = exact fp32 MFMA; 3 / 1 = the two contractions of the FORWARD pass (x W_ih^T and the
-        recurrence's h W_hh^T) on the split-precision bf16 MFMA kernels (csrc/slu_bf16.h) — 3: fp32-class (used
-        for frozen layers), 1: plain bf16 (BASELINE configs[4]); the backward pass is exact fp32 either way."""
+                p, mask, seed, offset, method, factor, nsplit=0, packed_ih=None, offset_dev=None, sub_batch=0):
+        """seed .. sub_batch: a DropStream, splatted.  nsplit: 0 = exact fp32 MFMA; 3 / 1 = the two contractions of the
+        FORWARD pass (x W_ih^T and the recurrence's h W_hh^T) on the split-precision bf16 MFMA kernels (csrc/slu_bf16.h)
+        — 3: fp32-class (used for frozen layers), 1: plain bf16 (BASELINE configs[4]); the backward pass is exact fp32."""
+        _step_word_ok(p, mask, offset_dev)
         x = x.contiguous()
         T, B, I = x.shape
         H = w_hh_f.shape[1]
@@ -2290,7 +2301,6 @@ class GRULayerFn(torch.autograd.Function):
             else:
                 gx = gemm_nt(x2, w_ih, b_ih)                              # (T*B, D*3H); train_nsplit arithmetic
                 raw, reserve = gru_seq_fwd(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, T, B, H, D, need)
-        offset, offset_dev, sub_batch = offset if isinstance(offset, tuple) else (offset, None, 0)
         if p == 0.0 and (factor == 1):
             y = raw
         else:
@@ -2298,20 +2308,19 @@ class GRULayerFn(torch.autograd.Function):
         if need:
             ctx.save_for_backward(x, raw, reserve, mask, w_ih, w_hh_f, w_hh_r)
             assert sub_batch == 0, "sub-batched dropout streams are for no-grad (frozen) stages"
-            ctx.offset_dev = offset_dev          # not a graph tensor: a persistent 1-element buffer
-            ctx.cfg = (T, B, I, H, D, p, seed, offset, method, factor)
+            ctx.cfg = (T, B, I, H, D, p, DropStream(seed, offset, offset_dev, sub_batch), method, factor)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        T, B, I, H, D, p, seed, offset, method, factor = ctx.cfg
+        T, B, I, H, D, p, stream, method, factor = ctx.cfg
         x, raw, reserve, mask, w_ih, w_hh_f, w_hh_r = ctx.saved_tensors
         if p == 0.0 and factor == 1:
             d_raw = dy
         else:
-            d_raw = dropout_pool_bwd(dy, raw, mask, p, seed, offset, method, factor, ctx.offset_dev)
+            d_raw = dropout_pool_bwd(dy, raw, mask, p, *stream[:2], method, factor, stream.offset_dev)
         d_gx, d_gh, dbp = gru_seq_bwd(d_raw, reserve, w_hh_f, w_hh_r, T, B, H, D)
-        return tuple(_gru_layer_grads(ctx.needs_input_grad[:11], x, raw, d_gx, d_gh, dbp, w_ih, T, B, I, H, D) + [None] * 8)
+        return tuple(_gru_layer_grads(ctx.needs_input_grad[:11], x, raw, d_gx, d_gh, dbp, w_ih, T, B, I, H, D) + [None] * 10)
 
 
 def _gru_layer_grads(ng, x, raw, d_gx, d_gh, dbp, w_ih, T, B, I, H, D):
@@ -2352,7 +2361,8 @@ class GRULayerLenFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w_ih, b_ih, w_ih_f, w_ih_r, b_ih_f, b_ih_r, w_hh_f, b_hh_f, w_hh_r, b_hh_r,
-                lengths, p, mask, seed, offset, method, factor):
+                lengths, p, mask, seed, offset, method, factor, offset_dev=None, sub_batch=0):
+        _step_word_ok(p, mask, offset_dev)
         x = x.contiguous()
         T, B, I = x.shape
         H = w_hh_f.shape[1]
@@ -2360,7 +2370,6 @@ class GRULayerLenFn(torch.autograd.Function):
         need = any(ctx.needs_input_grad[:11])
         gx = gemm(x.view(T * B, I), w_ih.t(), b_ih)
         raw, reserve = gru_seq_fwd_len_rsv(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lengths, T, B, H, D, need)
-        offset, offset_dev, sub_batch = offset if isinstance(offset, tuple) else (offset, None, 0)
         assert sub_batch == 0, "sub-batched dropout streams are for the look-ahead pipeline, which has no masked steps"
         if p == 0.0 and factor == 1:
             y = raw                                      # already zero at t >= lengths[b]
@@ -2368,20 +2377,19 @@ class GRULayerLenFn(torch.autograd.Function):
             y = dropout_pool_len_fwd(raw, lengths, mask, p, seed, offset, method, factor, offset_dev)
         if need:
             ctx.save_for_backward(x, raw, reserve, mask, w_ih, w_hh_f, w_hh_r, lengths)
-            ctx.offset_dev = offset_dev
-            ctx.cfg = (T, B, I, H, D, p, seed, offset, method, factor)
+            ctx.cfg = (T, B, I, H, D, p, DropStream(seed, offset, offset_dev, 0), method, factor)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        T, B, I, H, D, p, seed, offset, method, factor = ctx.cfg
+        T, B, I, H, D, p, stream, method, factor = ctx.cfg
         x, raw, reserve, mask, w_ih, w_hh_f, w_hh_r, lengths = ctx.saved_tensors
         if p == 0.0 and factor == 1:
             d_raw = dy                                   # the BPTT kernel does not use d_out at t >= lengths[b]
         else:
-            d_raw = dropout_pool_len_bwd(dy, raw, lengths, mask, p, seed, offset, method, factor, ctx.offset_dev)
+            d_raw = dropout_pool_len_bwd(dy, raw, lengths, mask, p, *stream[:2], method, factor, stream.offset_dev)
         d_gx, d_gh, dbp = gru_seq_bwd_len(d_raw, reserve, w_hh_f, w_hh_r, lengths, T, B, H, D)
-        return tuple(_gru_layer_grads(ctx.needs_input_grad[:11], x, raw, d_gx, d_gh, dbp, w_ih, T, B, I, H, D) + [None] * 7)
+        return tuple(_gru_layer_grads(ctx.needs_input_grad[:11], x, raw, d_gx, d_gh, dbp, w_ih, T, B, I, H, D) + [None] * 9)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2620,7 +2628,7 @@ def decoder_step(P, keys, values, state_prev, state_next, y_prev, q, inp0, att_w
     """One decoding step (models.py:528-536) on the HIP kernels, shared by the teacher-forced forward and the beam
     search: attention on the top layer's state, embedding of the previous label, the GRUCell stack (+ dropout between
     the cells), output logits.  P: parameter dict (detached tensors); state_* (B, L, Dd); save / drop: per-layer
-    buffers or None (inference); drop_cfg = (p, masks or None, seed, offset, offset_dev, B * Dd).
+    buffers or None (inference); drop_cfg = (p, masks or None, DropStream, B * Dd).
     y_prev None: the embedding half of inp0 is already filled; logits None: the caller computes them later (teacher
     forcing knows every input label up front and needs the logits only after the loop: both become ONE GEMM over all
     steps instead of one small launch per step).
@@ -2628,7 +2636,7 @@ def decoder_step(P, keys, values, state_prev, state_next, y_prev, q, inp0, att_w
     batch -> the length-aware attention (attention_len_fwd); nothing else in the step looks at the encoder."""
     Lc, Dd = state_prev.shape[1], state_prev.shape[2]
     E = P["embed.weight"].shape[0]
-    p, masks, seed, offset, offset_dev, bd = drop_cfg
+    p, masks, stream, bd = drop_cfg
     # everything that depends on the previous state only, in ONE grouped launch: the attention query and every cell's
     # hidden-to-hidden product (gh is (Lc, B, 3 Dd))
     group = [(state_prev[:, Lc - 1], P["query.weight"], P["query.bias"], q, 0, 0)]
@@ -2646,8 +2654,7 @@ def decoder_step(P, keys, values, state_prev, state_next, y_prev, q, inp0, att_w
         last = l == Lc - 1
         mask = None if (masks is None or last) else masks["decoder_dropout_u%d_l%d" % (step, l)]
         gru_cell_fwd(gi, gh[l], state_prev[:, l], state_next[:, l], None if save is None else save[l],
-                     None if last else drop[l], mask, 0.0 if last else p, seed, offset, offset_dev,
-                     (step * Lc + l) * bd)
+                     None if last else drop[l], mask, 0.0 if last else p, *stream[:3], (step * Lc + l) * bd)
         if not last:
             x_in = drop[l]
     if logits is not None:
@@ -2660,16 +2667,16 @@ class Seq2SeqDecoderFn(torch.autograd.Function):
     (B, U, V) float (one-hot rows, padded with <eos>).  One autograd node for the whole decoder: the backward is a
     hand-written BPTT over the U steps on the same kernels (every Linear's weight gradient is ONE GEMM over the
     (U * B)-row history).  Returns (loss_acc (2) = [loss, 0], log_p (B)); only loss_acc[0] carries a gradient.
-    meta may carry an eighth entry, n_rows (int32 CUDA tensor of B encoder frame counts): row b's attention then ranges over
-    its first n_rows[b] frames at every step, forward and backward (attention_len_fwd / _bwd).  d_keys / d_values start
-    zeroed and stay so at the padded frames, hence d_enc is exactly 0 there and key / value.weight.grad receive nothing
-    from them; the 1 / B of the loss is the padded batch's B.  Everything else is the dense path, call for call."""
+    meta = (parameter names, SOS, p, injected masks or None, DropStream, n_rows); n_rows (None, or an int32 CUDA tensor of
+    B encoder frame counts): row b's attention then ranges over its first n_rows[b] frames at every step, forward and
+    backward (attention_len_fwd / _bwd).  d_keys / d_values start zeroed and stay so at the padded frames, hence d_enc is
+    exactly 0 there and key / value.weight.grad receive nothing from them; the 1 / B of the loss is the padded batch's B.
+    Everything else is the dense path, call for call."""
     NAMES = None    # set per call: parameter names in argument order
 
     @staticmethod
     def forward(ctx, enc, y, meta, *params):
-        names, SOS, p, masks, seed, offset, offset_dev = meta[:7]
-        n_rows = meta[7] if len(meta) > 7 else None
+        names, SOS, p, masks, stream, n_rows = meta
         P = {n: t.detach() for n, t in zip(names, params)}
         dev = enc.device
         enc = _f32c(enc, "encoder output")
@@ -2697,7 +2704,7 @@ class Seq2SeqDecoderFn(torch.autograd.Function):
         logits, lse = f(U, B, V), f(U, B)
         logp = torch.zeros(B, dtype=torch.float32, device=dev)
         gi, gh = f(B, 3 * Dd), f(Lc, B, 3 * Dd)
-        dcfg = (p, masks, seed, offset, offset_dev, B * Dd)
+        dcfg = (p, masks, stream, B * Dd)
         # teacher forcing: the embeddings of ALL steps' input labels in one GEMM (rows (u, b)), straight into inp0
         gemm(yprev.view(U * B, V), P["embed.weight"].t(), P["embed.bias"], out=inp0.view(U * B, E + Vd)[:, :E])
         for u in range(U):
@@ -2713,7 +2720,7 @@ class Seq2SeqDecoderFn(torch.autograd.Function):
         loss_acc = torch.zeros(2, dtype=torch.float32, device=dev)
         L = _lib.load()
         _lib.check(L.slu_neg_mean_f32(logp.data_ptr(), loss_acc.data_ptr(), B, _stream()), "slu_neg_mean_f32")
-        ctx.meta = (names, p, masks, seed, offset, offset_dev, (T, B, E2, U, V, Lc, Dd, E, Kd, Vd), P["inv_scale"], n_rows)
+        ctx.meta = (names, p, masks, stream, (T, B, E2, U, V, Lc, Dd, E, Kd, Vd), P["inv_scale"], n_rows)
         ctx.save_for_backward(enc, ycat, yprev, keys, values, state, q, att_w, inp0, save, drop, logits, lse, *params)
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(logp)
@@ -2721,7 +2728,7 @@ class Seq2SeqDecoderFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_loss_acc, _d_logp):
-        names, p, masks, seed, offset, offset_dev, dims, inv_scale, n_rows = ctx.meta
+        names, p, masks, stream, dims, inv_scale, n_rows = ctx.meta
         T, B, E2, U, V, Lc, Dd, E, Kd, Vd = dims
         n_par = len(names)
         if d_loss_acc is None:
@@ -2751,7 +2758,7 @@ class Seq2SeqDecoderFn(torch.autograd.Function):
                 mask = None if (masks is None or last) else masks["decoder_dropout_u%d_l%d" % (u, l)]
                 # top cell: d_drop = this step's logits gradient (keep-factor 1: there is no dropout after the last cell)
                 gru_cell_bwd(d_state[:, l], g_top[u] if last else d_x, save[u, l], state[u][:, l], d_gi[l, u], d_gh[l, u],
-                             d_state[:, l], mask, 0.0 if last else p, seed, offset, offset_dev, (u * Lc + l) * B * Dd)
+                             d_state[:, l], mask, 0.0 if last else p, *stream[:3], (u * Lc + l) * B * Dd)
                 # one grouped launch: the recurrent part of d h_{u-1} (accumulated) and the gradient of the cell's input
                 gemm_small_batched([(d_gh[l, u], P["w_hh%d" % l], None, d_state[:, l], 1, 1),
                                     (d_gi[l, u], P["w_ih%d" % l], None, d_x if l > 0 else d_inp0[u], 1, 0)])

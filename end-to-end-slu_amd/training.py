@@ -26,13 +26,9 @@ from tqdm import tqdm
 from data import SLUDataset, ASRDataset, mask_padding_enabled as data_mask_padding_enabled
 from data import asr_ctc_enabled, mask_asr_enabled
 from models import PretrainedModel, Model, next_rng_step, mask_augment_enabled as models_mask_augment_enabled
+from models import dropout_masks_injected, rng_step_held
 from slu_hip import dp, ops, pipeline
 from slu_hip import knobs as _knobs
-
-
-def models_masks_injected():
-    import models
-    return models._DropoutState.masks is not None
 
 
 def _lookahead_env():
@@ -490,7 +486,7 @@ class Trainer:
         depth = _lookahead_env()
         if not train or asr or depth in (0, 1) or not hasattr(self.model, "prefix_features"):
             return 0, 0
-        if not self._on_gpu() or models_masks_injected():
+        if not self._on_gpu() or dropout_masks_injected():
             return 0, 0
         n = self.model.frozen_prefix_len()
         # a CNN-block dropout inside the frozen prefix has no per-sub-batch stream (all shipped cfgs have
@@ -505,7 +501,7 @@ class Trainer:
         """Captured steps need the HIP optimiser (device-resident step counters), fixed gradient addresses
         (the bucket) and the in-kernel Philox dropout (injected masks change per call)."""
         return (pipeline.graphs_enabled() and self.bucket is not None and self._hip_adam
-                and not models_masks_injected() and self._on_gpu())
+                and not dropout_masks_injected() and self._on_gpu())
 
     def graph_stats(self):
         """{"step_graphs": captured optimisation steps, "prefix_graphs": captured look-ahead super-batch
@@ -831,7 +827,7 @@ class Trainer:
                 return
             loader = _drop_lengths(loader)
         depth, n_prefix = self.lookahead_depth(train, asr)
-        group_eval = (not train and not asr and hasattr(self.model, "eval_group") and not models_masks_injected()
+        group_eval = (not train and not asr and hasattr(self.model, "eval_group") and not dropout_masks_injected()
                       and not getattr(self.model, "seq2seq", False)
                       and self._on_gpu()
                       and _lookahead_env() not in (0, 1))
@@ -943,17 +939,15 @@ class Trainer:
     def _say_seq2seq_sample(self, batch):
         """Reference training.py:103-112: decode the first utterance of the batch the step just consumed."""
         x, y = batch[:2]
-        import models
         was_training = self.model.training
-        step = models._DropoutState.step          # the sample must not shift the training run's dropout streams
         self.model.eval()
         try:
-            print("seq2seq output")
-            print("guess: " + self.model.decode_intents(x[:1], *[l[:1] for l in self._seq2seq_lengths(batch)])[0])
-            print("truth: " + self.model.one_hot_to_string(y[0].cpu(), self.model.Sy_intent))
+            with rng_step_held():                 # the sample must not shift the training run's dropout streams
+                print("seq2seq output")
+                print("guess: " + self.model.decode_intents(x[:1], *[l[:1] for l in self._seq2seq_lengths(batch)])[0])
+                print("truth: " + self.model.one_hot_to_string(y[0].cpu(), self.model.Sy_intent))
         finally:
             self.model.train(was_training)
-            models._DropoutState.step = step
 
     # -- reference API -----------------------------------------------------------------------------
     def train(self, dataset, print_interval=100):

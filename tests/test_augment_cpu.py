@@ -203,7 +203,7 @@ def test_augmentation_key_is_a_stream_no_dropout_site_uses():
     try:
         for module, n in (("phone", 4), ("word", 4), ("intent", 4), ("cnn", 4), ("intent_encoder", 3)):
             for idx in range(2 * n):
-                _, _, seed, _ = models._dropout_args("x", models._site(module, idx), 0.5, True)
+                seed = models._dropout_args("x", models._site(module, idx), 0.5, True)[2].seed
                 assert seed == 77 and seed ^ key != seed
     finally:
         models.set_dropout_seed(None)
@@ -215,19 +215,17 @@ def test_augmentation_key_is_a_stream_no_dropout_site_uses():
     try:
         for seed in (77, 0, (1 << 64) - 1, key):
             models.set_dropout_seed(seed)
-            models._DropoutState.current, models._DropoutState.sub_batch = 5, 8
-            assert models._augment("x", False) == "x" and not calls
-            assert models._augment("x", True) == "augmented"
+            with models._rng_step(5, 8):
+                assert models._augment("x", False) == "x" and not calls
+                assert models._augment("x", True) == "augmented"
             x, a, k = calls.pop()
             assert x == "x" and a == (7, seed ^ key, 80, None, 8) and not k and a[1] != seed
-            models._DropoutState.current_dev = "step word"
-            assert models._augment("x", True) == "augmented"
+            with models._rng_step("step word", 8):
+                assert models._augment("x", True) == "augmented"
             x, a, k = calls.pop()
             assert a == (7, seed ^ key, 0, "step word", 8)
-            models._DropoutState.current_dev = None
     finally:
         models._ops.wave_augment = real
-        models._DropoutState.current_dev, models._DropoutState.sub_batch = None, 0
         models.set_dropout_seed(None)
     # and the keyed stream's words differ from the seed's at the same counters
     a = philox_blocks(77, 16, np.arange(8, dtype=np.uint64))

@@ -354,6 +354,52 @@ def test_philox_dropout_training_step_runs_and_is_seeded(models_mod, tmp_path):
     assert all(torch.isfinite(p.grad).all() for p in model.parameters() if p.grad is not None)
 
 
+@pytest.mark.parametrize("seq2seq", [False, True])
+def test_host_step_and_device_word_draw_the_same_step(models_mod, tmp_path, seq2seq):
+    """Model.forward of step 5 given as rng_step=5 (offset = 80 + site) and as the device word [80] (offset = site beside
+    it), from identical weights, everything trainable, every dropout probability 0.5: the loss and every parameter gradient
+    bit for bit.  One step takes both forms through the CNN blocks' dropout, the GRU layers' forward and backward and the
+    head's dropout (fused or, with SLU_FUSE_HEAD_DROPOUT=0, the stand-alone launch); seq2seq: through the decoder's site."""
+    drops = dict(cnn_drop=[0.5, 0.5, 0.5], phone_rnn_drop=[0.5, 0.5], word_rnn_drop=[0.5, 0.5], intent_rnn_drop=[0.5])
+    g = torch.Generator().manual_seed(9)
+    B = 5
+    x = 0.1 * torch.randn(B, 2000, generator=g)
+    if seq2seq:
+        import data
+        from test_hip_seq2seq import one_hot, seq2seq_cfg
+        labels = list(data.SYNTHETIC_SEQ2SEQ_LABELS)
+        cfg = seq2seq_cfg(tmp_path, labels, **drops)
+        y = one_hot(torch.randint(1, len(labels) - 1, (B, 6), generator=g), len(labels))
+    else:
+        cfg = tiny_cfg(tmp_path, **drops)
+        y = torch.stack([torch.randint(0, n, (B,), generator=g) for n in cfg.values_per_slot], dim=1)
+    torch.manual_seed(3)
+    model = models_mod.Model(cfg)
+    for p in model.parameters():
+        p.requires_grad = True
+    model.train()
+    models_mod.set_dropout_masks(None)
+    models_mod.set_dropout_seed(77)
+    try:
+        runs = []
+        for step in (5, torch.tensor([80], dtype=torch.int64, device="cuda")):
+            model.zero_grad(set_to_none=True)
+            loss, _ = model(x, y, rng_step=step)
+            loss.backward()
+            torch.cuda.synchronize()
+            runs.append((loss.detach().clone(), {k: p.grad.clone() for k, p in model.named_parameters() if p.grad is not None}))
+    finally:
+        models_mod.set_dropout_seed(None)
+    (loss_a, grads_a), (loss_b, grads_b) = runs
+    assert torch.isfinite(loss_a) and torch.equal(loss_a, loss_b)
+    # every parameter the forward uses has a gradient (the encoder's two ASR heads do not take part)
+    unused = {k for k, _ in model.named_parameters() if k not in grads_a}
+    assert unused and all("phoneme_linear" in k or "word_linear" in k for k in unused), sorted(unused)
+    assert sorted(grads_a) == sorted(grads_b)
+    for k in grads_a:
+        assert torch.equal(grads_a[k], grads_b[k]), k
+
+
 def test_layerwise_iteration_matches_fused_path(models_mod, tmp_path):
     """The reference iterates `for layer in phoneme_layers: out = layer(out)` (models.py:354-359); the
     ModuleList mirror supports the same loop and agrees with the fused stage plan."""

@@ -29,7 +29,7 @@ def models_mod():
     lib.require_gfx950()
     yield models
     models.set_dropout_masks(None)
-    models._DropoutState.seed = None
+    models.set_dropout_seed(None)
 
 
 def _setenv(monkeypatch, env):

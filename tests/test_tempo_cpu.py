@@ -195,22 +195,21 @@ def test_tempo_runs_in_front_of_the_other_effects_on_the_same_stream(monkeypatch
     key = models.AUGMENT_KEY
     models.set_dropout_seed(77)
     try:
-        models._DropoutState.current, models._DropoutState.sub_batch = 5, 8
-        monkeypatch.setenv("SLU_AUGMENT_TEMPO", "0")
-        assert models._augment("x", True) == "augmented"
-        assert calls == [("augment", "x", (7, 77 ^ key, 80, None, 8), {})]
-        del calls[:]
-        monkeypatch.setenv("SLU_AUGMENT_TEMPO", "1")
-        assert models._augment("x", False) == "x" and not calls
-        assert models._augment("x", True) == "augmented"
-        assert calls == [("tempo", "x", (77 ^ key, 80, None, 8), {}), ("augment", "stretched", (7, 77 ^ key, 80, None, 8), {})]
-        del calls[:]
-        models._DropoutState.current_dev = "step word"
-        assert models._augment("x", True) == "augmented"
+        with models._rng_step(5, 8):
+            monkeypatch.setenv("SLU_AUGMENT_TEMPO", "0")
+            assert models._augment("x", True) == "augmented"
+            assert calls == [("augment", "x", (7, 77 ^ key, 80, None, 8), {})]
+            del calls[:]
+            monkeypatch.setenv("SLU_AUGMENT_TEMPO", "1")
+            assert models._augment("x", False) == "x" and not calls
+            assert models._augment("x", True) == "augmented"
+            assert calls == [("tempo", "x", (77 ^ key, 80, None, 8), {}), ("augment", "stretched", (7, 77 ^ key, 80, None, 8), {})]
+            del calls[:]
+        with models._rng_step("step word", 8):
+            assert models._augment("x", True) == "augmented"
         assert calls == [("tempo", "x", (77 ^ key, 0, "step word", 8), {}),
                          ("augment", "stretched", (7, 77 ^ key, 0, "step word", 8), {})]
     finally:
-        models._DropoutState.current_dev, models._DropoutState.sub_batch = None, 0
         models.set_dropout_seed(None)
 
 
