@@ -751,153 +751,117 @@ static int gru_check(const char* who, int64_t T, int64_t B, int64_t H, int64_t D
   return SLU_OK;
 }
 
+// One direction's persistent kernels, dense or LEN: the 16-sequence family by H = 16, 32, 64, 128 (4H threads), the
+// 4-sequence family by H = 64, 128 (2H threads), and the names their launch checks report.
+template <class P> struct GruKernels {
+  void (*seq16[4])(const P);
+  void (*seq4[2])(const P, const int);
+  const char *name16, *name4;
+};
+template <bool LEN> static const GruKernels<GruFwdParams> gru_fwd_kernels = {
+    {gru_seq_fwd_kernel<16, LEN>, gru_seq_fwd_kernel<32, LEN>, gru_seq_fwd_kernel<64, LEN>, gru_seq_fwd_kernel<128, LEN>},
+    {gru_seq_fwd4_kernel<64, LEN>, gru_seq_fwd4_kernel<128, LEN>},
+    LEN ? "gru_seq_fwd_kernel<LEN>" : "gru_seq_fwd_kernel", LEN ? "gru_seq_fwd4_kernel<LEN>" : "gru_seq_fwd4_kernel"};
+template <bool LEN> static const GruKernels<GruBwdParams> gru_bwd_kernels = {
+    {gru_seq_bwd_kernel<16, LEN>, gru_seq_bwd_kernel<32, LEN>, gru_seq_bwd_kernel<64, LEN>, gru_seq_bwd_kernel<128, LEN>},
+    {gru_seq_bwd4_kernel<64, LEN>, gru_seq_bwd4_kernel<128, LEN>},
+    LEN ? "gru_seq_bwd_kernel<LEN>" : "gru_seq_bwd_kernel", LEN ? "gru_seq_bwd4_kernel<LEN>" : "gru_seq_bwd4_kernel"};
+
+// The one launch of a persistent H: the seq4 / seq16 choice and the choice by H, for either direction
+template <class P> static int gru_go(const GruKernels<P>& k, const P& p, int64_t H, hipStream_t st) {
+  const int hi = H == 16 ? 0 : H == 32 ? 1 : H == 64 ? 2 : 3;
+  if (gru_use_seq4(p.B, H, p.D)) {
+    hipLaunchKernelGGL(k.seq4[hi - 2], dim3((unsigned)cdiv(p.B, 4), (unsigned)p.D), dim3((unsigned)(2 * H)), 0, st, p,
+                       (int)cdiv(p.B, 16));
+    SLU_CHECK_LAUNCH(k.name4);
+  } else {
+    hipLaunchKernelGGL(k.seq16[hi], dim3((unsigned)cdiv(p.B, 16), (unsigned)p.D), dim3((unsigned)(4 * H)), 0, st, p);
+    SLU_CHECK_LAUNCH(k.name16);
+  }
+  return SLU_OK;
+}
+
+// What the five entry points check alike, and the fields the two Params share.  `ptrs` / `rev`: the entry point's own
+// required pointers / reverse weights are all there.  A length-aware call (`len`) has no step-wise kernel to fall back on.
+template <class P>
+static int gru_args(const char* who, P& p, bool len, bool ptrs, bool rev, const float* w_hh_fwd, const float* w_hh_rev,
+                    const int32_t* lengths, int64_t T, int64_t B, int64_t H, int64_t D) {
+  SLU_REQUIRE(ptrs, "%s: null pointer", who);
+  SLU_REQUIRE(!len || lengths, "%s: null lengths", who);
+  SLU_REQUIRE(D == 1 || rev, "%s: reverse weights missing", who);
+  int rc = gru_check(who, T, B, H, D);
+  if (rc) return rc;
+  if (len && !gru_persistent(H))
+    SLU_FAIL(SLU_ERR_UNSUPPORTED, "%s: hidden size %lld has no length-aware kernel (16, 32, 64 or 128)", who, (long long)H);
+  p.w_hh[0] = w_hh_fwd; p.w_hh[1] = w_hh_rev; p.T = (int)T; p.B = (int)B; p.D = (int)D;
+  p.lengths = len ? (const int*)lengths : nullptr;
+  return SLU_OK;
+}
+
+// The LEN instantiations write the reserve like the plain ones — the gates a step computed and the h_{t-1} it blended
+// with, which is the masked h of the step before: 0 for direction 1 at t = n_b - 1.  Reserve contents at t >= n_b are
+// unspecified (NaN where gx is).  slu_gru_seq_fwd_len is slu_gru_seq_fwd_len_rsv with reserve = null.
+template <bool LEN>
+static int gru_fwd(const char* who, const float* gx, const float* w_hh_fwd, const float* w_hh_rev, const float* b_hh_fwd,
+                   const float* b_hh_rev, float* out, float* reserve, const int32_t* lengths, int64_t T, int64_t B,
+                   int64_t H, int64_t D, void* stream) {
+  GruFwdParams p;
+  int rc = gru_args(who, p, LEN, gx && w_hh_fwd && b_hh_fwd && out, w_hh_rev && b_hh_rev, w_hh_fwd, w_hh_rev, lengths, T, B,
+                    H, D);
+  if (rc) return rc;
+  p.gx = gx; p.b_hh[0] = b_hh_fwd; p.b_hh[1] = b_hh_rev; p.out = out; p.reserve = reserve;
+  if (!gru_persistent(H)) return gru_step_fwd(gx, p.w_hh, p.b_hh, out, reserve, T, B, H, D, (hipStream_t)stream);
+  return gru_go(gru_fwd_kernels<LEN>, p, H, (hipStream_t)stream);
+}
+
+template <bool LEN>
+static int gru_bwd(const char* who, const float* d_out, const float* reserve, const float* w_hh_fwd, const float* w_hh_rev,
+                   float* d_gx, float* d_gh, float* d_bias_part, const int32_t* lengths, int64_t T, int64_t B, int64_t H,
+                   int64_t D, void* stream) {
+  GruBwdParams p;
+  int rc = gru_args(who, p, LEN, d_out && reserve && w_hh_fwd && d_gx && d_gh, w_hh_rev != nullptr, w_hh_fwd, w_hh_rev,
+                    lengths, T, B, H, D);
+  if (rc) return rc;
+  p.d_out = d_out; p.reserve = reserve; p.d_gx = d_gx; p.d_gh = d_gh; p.d_bias_part = d_bias_part;
+  if (!gru_persistent(H))
+    return gru_step_bwd(d_out, reserve, p.w_hh, d_gx, d_gh, d_bias_part, T, B, H, D, (hipStream_t)stream);
+  return gru_go(gru_bwd_kernels<LEN>, p, H, (hipStream_t)stream);
+}
+
 extern "C" int slu_gru_seq_fwd(const float* gx, const float* w_hh_fwd, const float* w_hh_rev,
                                const float* b_hh_fwd, const float* b_hh_rev, float* out,
                                float* reserve, int64_t T, int64_t B, int64_t H, int64_t D,
                                void* stream) {
-  SLU_REQUIRE(gx && w_hh_fwd && b_hh_fwd && out, "slu_gru_seq_fwd: null pointer");
-  SLU_REQUIRE(D == 1 || (w_hh_rev && b_hh_rev), "slu_gru_seq_fwd: reverse weights missing");
-  int rc = gru_check("slu_gru_seq_fwd", T, B, H, D);
-  if (rc) return rc;
-  GruFwdParams p;
-  p.gx = gx; p.w_hh[0] = w_hh_fwd; p.w_hh[1] = w_hh_rev; p.b_hh[0] = b_hh_fwd; p.b_hh[1] = b_hh_rev;
-  p.out = out; p.reserve = reserve; p.T = (int)T; p.B = (int)B; p.D = (int)D; p.lengths = nullptr;
-  hipStream_t st = (hipStream_t)stream;
-  if (!gru_persistent(H)) return gru_step_fwd(gx, p.w_hh, p.b_hh, out, reserve, T, B, H, D, st);
-  if (gru_use_seq4(B, H, D)) {
-    dim3 grid4((unsigned)cdiv(B, 4), (unsigned)D);
-    const int nbt16 = (int)cdiv(B, 16);
-    if (H == 64) hipLaunchKernelGGL(gru_seq_fwd4_kernel<64>, grid4, dim3(128), 0, st, p, nbt16);
-    else hipLaunchKernelGGL(gru_seq_fwd4_kernel<128>, grid4, dim3(256), 0, st, p, nbt16);
-    SLU_CHECK_LAUNCH("gru_seq_fwd4_kernel");
-    return SLU_OK;
-  }
-  dim3 grid((unsigned)cdiv(B, 16), (unsigned)D);
-  switch (H) {
-    case 16: hipLaunchKernelGGL(gru_seq_fwd_kernel<16>, grid, dim3(64), 0, st, p); break;
-    case 32: hipLaunchKernelGGL(gru_seq_fwd_kernel<32>, grid, dim3(128), 0, st, p); break;
-    case 64: hipLaunchKernelGGL(gru_seq_fwd_kernel<64>, grid, dim3(256), 0, st, p); break;
-    default: hipLaunchKernelGGL(gru_seq_fwd_kernel<128>, grid, dim3(512), 0, st, p); break;
-  }
-  SLU_CHECK_LAUNCH("gru_seq_fwd_kernel");
-  return SLU_OK;
-}
-
-// slu_gru_seq_fwd_len (reserve = null) and slu_gru_seq_fwd_len_rsv: the LEN instantiations write the reserve like the
-// plain ones — the gates a step computed and the h_{t-1} it blended with, which is the masked h of the step before: 0
-// for direction 1 at t = n_b - 1.  Reserve contents at t >= n_b are unspecified (NaN where gx is).
-static int gru_fwd_len_launch(const char* who, const float* gx, const float* w_hh_fwd, const float* w_hh_rev,
-                              const float* b_hh_fwd, const float* b_hh_rev, float* out, float* reserve,
-                              const int32_t* lengths, int64_t T, int64_t B, int64_t H, int64_t D, void* stream) {
-  SLU_REQUIRE(gx && w_hh_fwd && b_hh_fwd && out, "%s: null pointer", who);
-  SLU_REQUIRE(lengths, "%s: null lengths", who);
-  SLU_REQUIRE(D == 1 || (w_hh_rev && b_hh_rev), "%s: reverse weights missing", who);
-  int rc = gru_check(who, T, B, H, D);
-  if (rc) return rc;
-  if (!gru_persistent(H))
-    SLU_FAIL(SLU_ERR_UNSUPPORTED, "%s: hidden size %lld has no length-aware kernel (16, 32, 64 or 128)", who, (long long)H);
-  GruFwdParams p;
-  p.gx = gx; p.w_hh[0] = w_hh_fwd; p.w_hh[1] = w_hh_rev; p.b_hh[0] = b_hh_fwd; p.b_hh[1] = b_hh_rev;
-  p.out = out; p.reserve = reserve; p.T = (int)T; p.B = (int)B; p.D = (int)D; p.lengths = (const int*)lengths;
-  hipStream_t st = (hipStream_t)stream;
-  if (gru_use_seq4(B, H, D)) {
-    dim3 grid4((unsigned)cdiv(B, 4), (unsigned)D);
-    const int nbt16 = (int)cdiv(B, 16);
-    if (H == 64) hipLaunchKernelGGL((gru_seq_fwd4_kernel<64, true>), grid4, dim3(128), 0, st, p, nbt16);
-    else hipLaunchKernelGGL((gru_seq_fwd4_kernel<128, true>), grid4, dim3(256), 0, st, p, nbt16);
-    SLU_CHECK_LAUNCH("gru_seq_fwd4_kernel<LEN>");
-    return SLU_OK;
-  }
-  dim3 grid((unsigned)cdiv(B, 16), (unsigned)D);
-  switch (H) {
-    case 16: hipLaunchKernelGGL((gru_seq_fwd_kernel<16, true>), grid, dim3(64), 0, st, p); break;
-    case 32: hipLaunchKernelGGL((gru_seq_fwd_kernel<32, true>), grid, dim3(128), 0, st, p); break;
-    case 64: hipLaunchKernelGGL((gru_seq_fwd_kernel<64, true>), grid, dim3(256), 0, st, p); break;
-    default: hipLaunchKernelGGL((gru_seq_fwd_kernel<128, true>), grid, dim3(512), 0, st, p); break;
-  }
-  SLU_CHECK_LAUNCH("gru_seq_fwd_kernel<LEN>");
-  return SLU_OK;
+  return gru_fwd<false>("slu_gru_seq_fwd", gx, w_hh_fwd, w_hh_rev, b_hh_fwd, b_hh_rev, out, reserve, nullptr, T, B, H, D,
+                        stream);
 }
 
 extern "C" int slu_gru_seq_fwd_len(const float* gx, const float* w_hh_fwd, const float* w_hh_rev,
                                    const float* b_hh_fwd, const float* b_hh_rev, float* out,
                                    const int32_t* lengths, int64_t T, int64_t B, int64_t H, int64_t D,
                                    void* stream) {
-  return gru_fwd_len_launch("slu_gru_seq_fwd_len", gx, w_hh_fwd, w_hh_rev, b_hh_fwd, b_hh_rev, out, nullptr, lengths, T, B, H,
-                            D, stream);
+  return gru_fwd<true>("slu_gru_seq_fwd_len", gx, w_hh_fwd, w_hh_rev, b_hh_fwd, b_hh_rev, out, nullptr, lengths, T, B, H, D,
+                       stream);
 }
 
 extern "C" int slu_gru_seq_fwd_len_rsv(const float* gx, const float* w_hh_fwd, const float* w_hh_rev,
                                        const float* b_hh_fwd, const float* b_hh_rev, float* out, float* reserve,
                                        const int32_t* lengths, int64_t T, int64_t B, int64_t H, int64_t D,
                                        void* stream) {
-  return gru_fwd_len_launch("slu_gru_seq_fwd_len_rsv", gx, w_hh_fwd, w_hh_rev, b_hh_fwd, b_hh_rev, out, reserve, lengths, T,
-                            B, H, D, stream);
+  return gru_fwd<true>("slu_gru_seq_fwd_len_rsv", gx, w_hh_fwd, w_hh_rev, b_hh_fwd, b_hh_rev, out, reserve, lengths, T, B, H,
+                       D, stream);
 }
 
 extern "C" int slu_gru_seq_bwd(const float* d_out, const float* reserve, const float* w_hh_fwd,
                                const float* w_hh_rev, float* d_gx, float* d_gh, float* d_bias_part,
                                int64_t T, int64_t B, int64_t H, int64_t D, void* stream) {
-  SLU_REQUIRE(d_out && reserve && w_hh_fwd && d_gx && d_gh, "slu_gru_seq_bwd: null pointer");
-  SLU_REQUIRE(D == 1 || w_hh_rev, "slu_gru_seq_bwd: reverse weights missing");
-  int rc = gru_check("slu_gru_seq_bwd", T, B, H, D);
-  if (rc) return rc;
-  GruBwdParams p;
-  p.d_out = d_out; p.reserve = reserve; p.w_hh[0] = w_hh_fwd; p.w_hh[1] = w_hh_rev;
-  p.d_gx = d_gx; p.d_gh = d_gh; p.d_bias_part = d_bias_part; p.T = (int)T; p.B = (int)B; p.D = (int)D;
-  p.lengths = nullptr;
-  hipStream_t st = (hipStream_t)stream;
-  if (!gru_persistent(H)) return gru_step_bwd(d_out, reserve, p.w_hh, d_gx, d_gh, d_bias_part, T, B, H, D, st);
-  if (gru_use_seq4(B, H, D)) {
-    dim3 grid4((unsigned)cdiv(B, 4), (unsigned)D);
-    const int nbt16 = (int)cdiv(B, 16);
-    if (H == 64) hipLaunchKernelGGL(gru_seq_bwd4_kernel<64>, grid4, dim3(128), 0, st, p, nbt16);
-    else hipLaunchKernelGGL(gru_seq_bwd4_kernel<128>, grid4, dim3(256), 0, st, p, nbt16);
-    SLU_CHECK_LAUNCH("gru_seq_bwd4_kernel");
-    return SLU_OK;
-  }
-  dim3 grid((unsigned)cdiv(B, 16), (unsigned)D);
-  switch (H) {
-    case 16: hipLaunchKernelGGL(gru_seq_bwd_kernel<16>, grid, dim3(64), 0, st, p); break;
-    case 32: hipLaunchKernelGGL(gru_seq_bwd_kernel<32>, grid, dim3(128), 0, st, p); break;
-    case 64: hipLaunchKernelGGL(gru_seq_bwd_kernel<64>, grid, dim3(256), 0, st, p); break;
-    default: hipLaunchKernelGGL(gru_seq_bwd_kernel<128>, grid, dim3(512), 0, st, p); break;
-  }
-  SLU_CHECK_LAUNCH("gru_seq_bwd_kernel");
-  return SLU_OK;
+  return gru_bwd<false>("slu_gru_seq_bwd", d_out, reserve, w_hh_fwd, w_hh_rev, d_gx, d_gh, d_bias_part, nullptr, T, B, H, D,
+                        stream);
 }
 
 extern "C" int slu_gru_seq_bwd_len(const float* d_out, const float* reserve, const float* w_hh_fwd,
                                    const float* w_hh_rev, float* d_gx, float* d_gh, float* d_bias_part,
                                    const int32_t* lengths, int64_t T, int64_t B, int64_t H, int64_t D, void* stream) {
-  SLU_REQUIRE(d_out && reserve && w_hh_fwd && d_gx && d_gh, "slu_gru_seq_bwd_len: null pointer");
-  SLU_REQUIRE(lengths, "slu_gru_seq_bwd_len: null lengths");
-  SLU_REQUIRE(D == 1 || w_hh_rev, "slu_gru_seq_bwd_len: reverse weights missing");
-  int rc = gru_check("slu_gru_seq_bwd_len", T, B, H, D);
-  if (rc) return rc;
-  if (!gru_persistent(H))
-    SLU_FAIL(SLU_ERR_UNSUPPORTED, "slu_gru_seq_bwd_len: hidden size %lld has no length-aware kernel (16, 32, 64 or 128)",
-             (long long)H);
-  GruBwdParams p;
-  p.d_out = d_out; p.reserve = reserve; p.w_hh[0] = w_hh_fwd; p.w_hh[1] = w_hh_rev;
-  p.d_gx = d_gx; p.d_gh = d_gh; p.d_bias_part = d_bias_part; p.T = (int)T; p.B = (int)B; p.D = (int)D;
-  p.lengths = (const int*)lengths;
-  hipStream_t st = (hipStream_t)stream;
-  if (gru_use_seq4(B, H, D)) {
-    dim3 grid4((unsigned)cdiv(B, 4), (unsigned)D);
-    const int nbt16 = (int)cdiv(B, 16);
-    if (H == 64) hipLaunchKernelGGL((gru_seq_bwd4_kernel<64, true>), grid4, dim3(128), 0, st, p, nbt16);
-    else hipLaunchKernelGGL((gru_seq_bwd4_kernel<128, true>), grid4, dim3(256), 0, st, p, nbt16);
-    SLU_CHECK_LAUNCH("gru_seq_bwd4_kernel<LEN>");
-    return SLU_OK;
-  }
-  dim3 grid((unsigned)cdiv(B, 16), (unsigned)D);
-  switch (H) {
-    case 16: hipLaunchKernelGGL((gru_seq_bwd_kernel<16, true>), grid, dim3(64), 0, st, p); break;
-    case 32: hipLaunchKernelGGL((gru_seq_bwd_kernel<32, true>), grid, dim3(128), 0, st, p); break;
-    case 64: hipLaunchKernelGGL((gru_seq_bwd_kernel<64, true>), grid, dim3(256), 0, st, p); break;
-    default: hipLaunchKernelGGL((gru_seq_bwd_kernel<128, true>), grid, dim3(512), 0, st, p); break;
-  }
-  SLU_CHECK_LAUNCH("gru_seq_bwd_kernel<LEN>");
-  return SLU_OK;
+  return gru_bwd<true>("slu_gru_seq_bwd_len", d_out, reserve, w_hh_fwd, w_hh_rev, d_gx, d_gh, d_bias_part, lengths, T, B, H,
+                       D, stream);
 }

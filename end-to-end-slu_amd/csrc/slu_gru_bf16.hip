@@ -1016,26 +1016,26 @@ gru_bf_fwd_rs_kernel(const GruBfParams p) {
   }
 }
 
-template <int H, int NS, int KI, int EPI, bool LEN = false>
-static void gru_bf_launch(dim3 grid, hipStream_t st, const GruBfParams& p) {
-  constexpr int lds = GruLds<H, NS, KI, EPI>::BYTES;
-  static bool raised = false;      // > 64 KiB of dynamic LDS needs the function attribute (once per instantiation)
+// > 64 KiB of dynamic LDS needs the function attribute: raised once per instantiation (the flag is KERNEL's own), then launch
+template <auto KERNEL>
+static void gru_bf_lds_launch(dim3 grid, dim3 block, int lds, hipStream_t st, const GruBfParams& p) {
+  static bool raised = false;
   if (lds > 64 * 1024 && !raised) {
-    (void)hipFuncSetAttribute((const void*)gru_bf_fwd_kernel<H, NS, KI, EPI, LEN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     raised = true;
   }
-  hipLaunchKernelGGL((gru_bf_fwd_kernel<H, NS, KI, EPI, LEN>), grid, dim3(H * 4), lds, st, p);
+  hipLaunchKernelGGL(KERNEL, grid, block, lds, st, p);
+}
+
+template <int H, int NS, int KI, int EPI, bool LEN = false>
+static void gru_bf_launch(dim3 grid, hipStream_t st, const GruBfParams& p) {
+  gru_bf_lds_launch<gru_bf_fwd_kernel<H, NS, KI, EPI, LEN>>(grid, dim3(H * 4), GruLds<H, NS, KI, EPI>::BYTES, st, p);
 }
 
 template <int H, int NS, int EPI>
 static void gru_bf2_launch(hipStream_t st, const GruBfParams& p) {
-  constexpr int lds = Gru2Lds<H, NS, EPI>::BYTES;
-  static bool raised = false;
-  if (lds > 64 * 1024 && !raised) {
-    (void)hipFuncSetAttribute((const void*)gru_bf2_fwd_kernel<H, NS, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    raised = true;
-  }
-  hipLaunchKernelGGL((gru_bf2_fwd_kernel<H, NS, EPI>), dim3((unsigned)cdiv(p.B, 32), (unsigned)p.D), dim3(H * 4), lds, st, p);
+  gru_bf_lds_launch<gru_bf2_fwd_kernel<H, NS, EPI>>(dim3((unsigned)cdiv(p.B, 32), (unsigned)p.D), dim3(H * 4),
+                                                    Gru2Lds<H, NS, EPI>::BYTES, st, p);
 }
 
 template <int H, int EPI>
@@ -1181,9 +1181,7 @@ extern "C" int slu_gru_seq_fwd_len_bf16(const float* gx, const float* w_hh_fwd, 
   SLU_REQUIRE(D == 1 || b_hh_rev, "%s: null b_hh_rev (D = 2)", who);
   if (nsplit != 3)
     SLU_FAIL(SLU_ERR_UNSUPPORTED, "%s: the length-aware recurrence is instantiated for bf16x3 only (nsplit 3, got %d)", who, nsplit);
-  if (H != 64 && H != 128)
-    SLU_FAIL(SLU_ERR_UNSUPPORTED, "%s: hidden size %lld not instantiated (64, 128)", who, (long long)H);
-  GruBfParams p;
+  GruBfParams p;      // every check above differs from gru_bf_common's in status or text; the H check did not, and is its
   int rc = gru_bf_common(who, p, gx, w_hh_fwd, w_hh_rev, b_hh_fwd, b_hh_rev, nullptr, 0, 0, nullptr, nullptr, T, B, H, D,
                          nsplit, false, 1);
   if (rc) return rc;

@@ -1153,16 +1153,31 @@ def colsum(x2d, out=None, accumulate=False):
     return out
 
 
-def gru_seq_fwd(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, T, B, H, D, want_reserve):
+# Dense and length-aware twins are ONE private body with lengths=None (attention: n=None): what the length-aware call adds
+# (its refusals, a contiguity copy) stands under `is not None`, the library entry point is chosen last; public names forward.
+def _gru_seq_fwd(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, T, B, H, D, want_reserve, lengths=None, rsv=False):
+    """rsv: the masked-training form of the length-aware call (slu_gru_seq_fwd_len_rsv, with or without a reserve); the
+    inference form (slu_gru_seq_fwd_len) refuses tensors that require a gradient and has no reserve."""
     L = _lib.load()
+    if lengths is not None:
+        _len_check(lengths, B, gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, grad_ok=rsv)
+        _len_hidden_ok(H)
     out = torch.empty(T, B, D * H, dtype=torch.float32, device=gx.device)
-    reserve = None
-    if want_reserve:
-        reserve = torch.empty(L.slu_gru_reserve_bytes(T, B, H, D) // 4, dtype=torch.float32, device=gx.device)
-    _lib.check(L.slu_gru_seq_fwd(gx.data_ptr(), w_hh_f.data_ptr(), _ptr(w_hh_r), b_hh_f.data_ptr(),
-                                 _ptr(b_hh_r), out.data_ptr(), _ptr(reserve), T, B, H, D, _stream()),
-               "slu_gru_seq_fwd")
+    rsv_floats = L.slu_gru_reserve_bytes(T, B, H, D) // 4 if want_reserve else 0
+    reserve = torch.empty(rsv_floats, dtype=torch.float32, device=gx.device) if want_reserve else None
+    io = (gx.data_ptr(), w_hh_f.data_ptr(), _ptr(w_hh_r), b_hh_f.data_ptr(), _ptr(b_hh_r), out.data_ptr())
+    if lengths is None:
+        _lib.check(L.slu_gru_seq_fwd(*io, _ptr(reserve), T, B, H, D, _stream()), "slu_gru_seq_fwd")
+    elif rsv:
+        _lib.check(L.slu_gru_seq_fwd_len_rsv(*io, _ptr(reserve), lengths.data_ptr(), T, B, H, D, _stream()),
+                   "slu_gru_seq_fwd_len_rsv")
+    else:
+        _lib.check(L.slu_gru_seq_fwd_len(*io, lengths.data_ptr(), T, B, H, D, _stream()), "slu_gru_seq_fwd_len")
     return out, reserve
+
+
+def gru_seq_fwd(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, T, B, H, D, want_reserve):
+    return _gru_seq_fwd(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, T, B, H, D, want_reserve)
 
 
 # (device, stream, T, B, H, D) -> hand-off counters of slu_gru_proj_seq_fwd (zeroed once, then launch-owned).  The counters never
@@ -1213,18 +1228,28 @@ def gru_proj_seq_fwd(x2, w_ih, b_ih, w_hh_f, w_hh_r, b_hh_f, b_hh_r, T, B, I, H,
     return out, reserve
 
 
-def gru_seq_bwd(d_out, reserve, w_hh_f, w_hh_r, T, B, H, D):
+def _gru_seq_bwd(d_out, reserve, w_hh_f, w_hh_r, T, B, H, D, lengths=None):
     L = _lib.load()
+    if lengths is not None:
+        _len_ok(lengths, B)
+        _len_hidden_ok(H)
     d_out = _f32c(d_out, "d_out")
     dev = d_out.device
     d_gx = torch.empty(T, B, D * 3 * H, dtype=torch.float32, device=dev)
     d_gh = torch.empty(T, B, D * 3 * H, dtype=torch.float32, device=dev)
     nbt = int(L.slu_gru_bias_tiles(T, B, H, D))
     d_bias_part = torch.empty(nbt, D, 6 * H, dtype=torch.float32, device=dev)
-    _lib.check(L.slu_gru_seq_bwd(d_out.data_ptr(), reserve.data_ptr(), w_hh_f.data_ptr(), _ptr(w_hh_r),
-                                 d_gx.data_ptr(), d_gh.data_ptr(), d_bias_part.data_ptr(), T, B, H, D,
-                                 _stream()), "slu_gru_seq_bwd")
+    io = (d_out.data_ptr(), reserve.data_ptr(), w_hh_f.data_ptr(), _ptr(w_hh_r), d_gx.data_ptr(), d_gh.data_ptr(),
+          d_bias_part.data_ptr())
+    if lengths is None:
+        _lib.check(L.slu_gru_seq_bwd(*io, T, B, H, D, _stream()), "slu_gru_seq_bwd")
+    else:
+        _lib.check(L.slu_gru_seq_bwd_len(*io, lengths.data_ptr(), T, B, H, D, _stream()), "slu_gru_seq_bwd_len")
     return d_gx, d_gh, d_bias_part
+
+
+def gru_seq_bwd(d_out, reserve, w_hh_f, w_hh_r, T, B, H, D):
+    return _gru_seq_bwd(d_out, reserve, w_hh_f, w_hh_r, T, B, H, D)
 
 
 def _mask_args(mask, T, B, C):
@@ -1235,32 +1260,59 @@ def _mask_args(mask, T, B, C):
     return mask.data_ptr(), mask.stride(0), mask.stride(1)
 
 
+def _seq_pool(x, method, factor, drop, lengths=None, sub_batch=0, keep_bits=None):
+    """drop: (mask, p, seed, offset, offset_dev) — slu_dropout_pool_fwd, with lengths slu_dropout_pool_len_fwd — or None:
+    slu_seq_pool_len_fwd, the inference form of the length-aware stage (no dropout; refuses a gradient)."""
+    L = _lib.load()
+    if lengths is not None:
+        _len_check(lengths, x.shape[1], x, grad_ok=drop is not None)
+        x = _f32c(x, "x")       # the dense form makes no such copy: it takes x as the recurrence kernels left it
+    T, B, C = x.shape
+    y = torch.empty(-(-T // factor), B, C, dtype=torch.float32, device=x.device)
+    if drop is None:
+        _lib.check(L.slu_seq_pool_len_fwd(x.data_ptr(), y.data_ptr(), lengths.data_ptr(), METHODS[method], factor, T, B, C,
+                                          _stream()), "slu_seq_pool_len_fwd")
+        return y
+    mask, p, seed, offset, offset_dev = drop
+    mp, mst, msb = _mask_args(mask, T, B, C)
+    if lengths is None:
+        _lib.check(L.slu_dropout_pool_fwd(x.data_ptr(), mp, mst, msb, _ptr(keep_bits), float(p), int(seed), int(offset),
+                                          _ptr(offset_dev), int(sub_batch), 16, METHODS[method], factor, y.data_ptr(),
+                                          T, B, C, _stream()), "slu_dropout_pool_fwd")
+    else:
+        _lib.check(L.slu_dropout_pool_len_fwd(x.data_ptr(), lengths.data_ptr(), mp, mst, msb, float(p), int(seed), int(offset),
+                                              _ptr(offset_dev), METHODS[method], factor, y.data_ptr(), T, B, C, _stream()),
+                   "slu_dropout_pool_len_fwd")
+    return y
+
+
 def dropout_pool_fwd(x, mask, p, seed, offset, method, factor, offset_dev=None, sub_batch=0, keep_bits=None):
     """offset_dev: optional 1-element int64 CUDA tensor added to `offset` on the device;
     sub_batch > 0: B is sub-batches of that size, sub-batch k uses offset + 16 k (consecutive steps);
     keep_bits: the 1-bit mask of dropout_bits instead of in-kernel Philox draws (frozen layers)."""
-    L = _lib.load()
-    T, B, C = x.shape
-    T_out = -(-T // factor)
-    y = torch.empty(T_out, B, C, dtype=torch.float32, device=x.device)
-    mp, mst, msb = _mask_args(mask, T, B, C)
-    _lib.check(L.slu_dropout_pool_fwd(x.data_ptr(), mp, mst, msb, _ptr(keep_bits), float(p), int(seed), int(offset),
-                                      _ptr(offset_dev), int(sub_batch), 16, METHODS[method], factor, y.data_ptr(),
-                                      T, B, C, _stream()),
-               "slu_dropout_pool_fwd")
-    return y
+    return _seq_pool(x, method, factor, (mask, p, seed, offset, offset_dev), None, sub_batch, keep_bits)
 
 
-def dropout_pool_bwd(dy, x, mask, p, seed, offset, method, factor, offset_dev=None):
+def _dropout_pool_bwd(dy, x, mask, p, seed, offset, method, factor, offset_dev=None, lengths=None):
     L = _lib.load()
     T, B, C = x.shape
+    if lengths is not None:
+        _len_ok(lengths, B)
     dy = _f32c(dy, "dy")
     dx = torch.empty(T, B, C, dtype=torch.float32, device=x.device)
     mp, mst, msb = _mask_args(mask, T, B, C)
-    _lib.check(L.slu_dropout_pool_bwd(dy.data_ptr(), x.data_ptr(), 0, mp, mst, msb, float(p), int(seed),
-                                      int(offset), _ptr(offset_dev), 0, 16, METHODS[method], factor, dx.data_ptr(), T, B, C,
-                                      _stream()), "slu_dropout_pool_bwd")
+    drop = (mp, mst, msb, float(p), int(seed), int(offset), _ptr(offset_dev))
+    if lengths is None:
+        _lib.check(L.slu_dropout_pool_bwd(dy.data_ptr(), x.data_ptr(), 0, *drop, 0, 16, METHODS[method], factor, dx.data_ptr(),
+                                          T, B, C, _stream()), "slu_dropout_pool_bwd")
+    else:
+        _lib.check(L.slu_dropout_pool_len_bwd(dy.data_ptr(), x.data_ptr(), lengths.data_ptr(), *drop, METHODS[method], factor,
+                                              dx.data_ptr(), T, B, C, _stream()), "slu_dropout_pool_len_bwd")
     return dx
+
+
+def dropout_pool_bwd(dy, x, mask, p, seed, offset, method, factor, offset_dev=None):
+    return _dropout_pool_bwd(dy, x, mask, p, seed, offset, method, factor, offset_dev)
 
 
 _TICKETS = {}
@@ -1281,6 +1333,19 @@ def _ticket(dev):
     return t
 
 
+def _head_outputs(B, values_per_slot, dev, want_d_logits, labelled):
+    """What both intent-head forwards write -> (logits, argmax_t, pred, d_logits, row_stats, loss_acc, vps, S)"""
+    S, V = len(values_per_slot), int(sum(values_per_slot))
+    logits = torch.empty(B, V, dtype=torch.float32, device=dev)
+    argmax_t = torch.empty(B, V, dtype=torch.int32, device=dev)
+    pred = torch.empty(B, S, dtype=torch.int64, device=dev)
+    d_logits = torch.empty(B, V, dtype=torch.float32, device=dev) if want_d_logits else None
+    row_stats = torch.empty(B, 2, dtype=torch.float32, device=dev) if labelled else None
+    loss_acc = torch.empty(2, dtype=torch.float32, device=dev) if labelled else None
+    vps = (ctypes.c_int64 * S)(*[int(v) for v in values_per_slot])
+    return logits, argmax_t, pred, d_logits, row_stats, loss_acc, vps, S
+
+
 def cls_maxpool_ce_fwd(h, weight, bias, y, values_per_slot, want_grad, epoch_sums=None, drop=None):
     """-> (loss_acc (2) or None, logits (B,V), pred (B,S), argmax_t (B,V) int32, d_logits or None[, h_drop])
     epoch_sums: optional float64 (2) device tensor; B * (loss, acc) is added to it by the same launch.
@@ -1288,16 +1353,9 @@ def cls_maxpool_ce_fwd(h, weight, bias, y, values_per_slot, want_grad, epoch_sum
     then the raw GRU output; the dropped activations are returned as a sixth value)."""
     L = _lib.load()
     T, B, C = h.shape
-    S = len(values_per_slot)
-    V = int(sum(values_per_slot))
     dev = h.device
-    logits = torch.empty(B, V, dtype=torch.float32, device=dev)
-    argmax_t = torch.empty(B, V, dtype=torch.int32, device=dev)
-    pred = torch.empty(B, S, dtype=torch.int64, device=dev)
-    d_logits = torch.empty(B, V, dtype=torch.float32, device=dev) if (want_grad and y is not None) else None
-    row_stats = torch.empty(B, 2, dtype=torch.float32, device=dev) if y is not None else None
-    loss_acc = torch.empty(2, dtype=torch.float32, device=dev) if y is not None else None
-    vps = (ctypes.c_int64 * S)(*[int(v) for v in values_per_slot])
+    logits, argmax_t, pred, d_logits, row_stats, loss_acc, vps, S = _head_outputs(
+        B, values_per_slot, dev, want_grad and y is not None, y is not None)
     p, seed, offset, offset_dev = drop if drop else (0.0, 0, 0, None)
     h_drop = torch.empty_like(h) if drop else None
     _lib.check(L.slu_cls_maxpool_ce_fwd(h.data_ptr(), weight.data_ptr(), bias.data_ptr(), _ptr(y), vps, S,
@@ -1336,6 +1394,12 @@ def _len_check(lengths, B, *tensors, grad_ok=False):
             raise RuntimeError("the length-aware kernels are inference only (no backward): call them under torch.no_grad() "
                                "with detached tensors")
     _len_ok(lengths, B)
+
+
+def _given(lengths):      # a length-aware public form never runs dense: None is refused like any other non-tensor
+    if lengths is None:
+        _len_ok(lengths, 0)
+    return lengths
 
 
 def _len_hidden_ok(H):
@@ -1419,27 +1483,9 @@ def mask_frames_len_(x, lengths_flat):
     return x
 
 
-def _gru_seq_fwd_len(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lengths, T, B, H, D, rsv, want_reserve=False):
-    """rsv: the masked-training form (slu_gru_seq_fwd_len_rsv, with or without a reserve)."""
-    L = _lib.load()
-    _len_check(lengths, B, gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, grad_ok=rsv)
-    _len_hidden_ok(H)
-    out = torch.empty(T, B, D * H, dtype=torch.float32, device=gx.device)
-    io = (gx.data_ptr(), w_hh_f.data_ptr(), _ptr(w_hh_r), b_hh_f.data_ptr(), _ptr(b_hh_r), out.data_ptr())
-    sizes = (lengths.data_ptr(), T, B, H, D, _stream())
-    if not rsv:
-        _lib.check(L.slu_gru_seq_fwd_len(*io, *sizes), "slu_gru_seq_fwd_len")
-        return out, None
-    reserve = None
-    if want_reserve:
-        reserve = torch.empty(L.slu_gru_reserve_bytes(T, B, H, D) // 4, dtype=torch.float32, device=gx.device)
-    _lib.check(L.slu_gru_seq_fwd_len_rsv(*io, _ptr(reserve), *sizes), "slu_gru_seq_fwd_len_rsv")
-    return out, reserve
-
-
 def gru_seq_fwd_len(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lengths, T, B, H, D):
     """gru_seq_fwd (no reserve) with per-sequence lengths -> out (T, B, D*H), zero at t >= lengths[b]."""
-    return _gru_seq_fwd_len(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lengths, T, B, H, D, False)[0]
+    return _gru_seq_fwd(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, T, B, H, D, False, _given(lengths))[0]
 
 
 LEN_BF16_HIDDEN_SIZES = (64, 128)          # hidden sizes slu_gru_seq_fwd_len_bf16 takes (the split-precision recurrence)
@@ -1461,28 +1507,9 @@ def gru_seq_fwd_len_bf16(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lengths, T, B, H, D
     return out
 
 
-def _seq_pool_len(x, lengths, method, factor, drop=None):
-    """drop: None (slu_seq_pool_len_fwd), or (mask, p, seed, offset, offset_dev) of the masked-training form."""
-    L = _lib.load()
-    _len_check(lengths, x.shape[1], x, grad_ok=drop is not None)
-    x = _f32c(x, "x")
-    T, B, C = x.shape
-    y = torch.empty(-(-T // factor), B, C, dtype=torch.float32, device=x.device)
-    if drop is None:
-        _lib.check(L.slu_seq_pool_len_fwd(x.data_ptr(), y.data_ptr(), lengths.data_ptr(), METHODS[method], factor, T, B, C,
-                                          _stream()), "slu_seq_pool_len_fwd")
-        return y
-    mask, p, seed, offset, offset_dev = drop
-    mp, mst, msb = _mask_args(mask, T, B, C)
-    _lib.check(L.slu_dropout_pool_len_fwd(x.data_ptr(), lengths.data_ptr(), mp, mst, msb, float(p), int(seed), int(offset),
-                                          _ptr(offset_dev), METHODS[method], factor, y.data_ptr(), T, B, C, _stream()),
-               "slu_dropout_pool_len_fwd")
-    return y
-
-
 def seq_pool_len_fwd(x, lengths, method, factor):
     """Downsample(method, factor) of a time-major (T, B, C) activation with per-sequence lengths."""
-    return _seq_pool_len(x, lengths, method, factor)
+    return _seq_pool(x, method, factor, None, _given(lengths))
 
 
 def _cls_maxpool_len(h, weight, bias, lengths, y, values_per_slot, want_grad):
@@ -1491,16 +1518,8 @@ def _cls_maxpool_len(h, weight, bias, lengths, y, values_per_slot, want_grad):
     _len_check(lengths, h.shape[1], h, weight, bias, grad_ok=want_grad)
     h, weight, bias = _f32c(h, "h"), _f32c(weight, "weight"), _f32c(bias, "bias")
     T, B, C = h.shape
-    S = len(values_per_slot)
-    V = int(sum(values_per_slot))
-    dev = h.device
-    logits = torch.empty(B, V, dtype=torch.float32, device=dev)
-    argmax_t = torch.empty(B, V, dtype=torch.int32, device=dev)
-    pred = torch.empty(B, S, dtype=torch.int64, device=dev)
-    d_logits = torch.empty(B, V, dtype=torch.float32, device=dev) if want_grad else None
-    row_stats = torch.empty(B, 2, dtype=torch.float32, device=dev) if y is not None else None
-    loss_acc = torch.empty(2, dtype=torch.float32, device=dev) if y is not None else None
-    vps = (ctypes.c_int64 * S)(*[int(v) for v in values_per_slot])
+    logits, argmax_t, pred, d_logits, row_stats, loss_acc, vps, S = _head_outputs(
+        B, values_per_slot, h.device, want_grad, y is not None)
     head = (h.data_ptr(), weight.data_ptr(), bias.data_ptr(), lengths.data_ptr(), _ptr(y), vps, S, logits.data_ptr(),
             argmax_t.data_ptr(), pred.data_ptr())
     tail = (_ptr(row_stats), _ptr(loss_acc), T, B, C, _stream())
@@ -1521,45 +1540,24 @@ def cls_maxpool_len_fwd(h, weight, bias, lengths, y, values_per_slot):
 def gru_seq_fwd_len_rsv(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lengths, T, B, H, D, want_reserve):
     """gru_seq_fwd with per-sequence lengths -> (out (T, B, D*H), zero at t >= lengths[b]; reserve or None).  The reserve
     has gru_seq_fwd's layout; at t >= lengths[b] its contents are unspecified (gru_seq_bwd_len does not use them)."""
-    return _gru_seq_fwd_len(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lengths, T, B, H, D, True, want_reserve)
+    return _gru_seq_fwd(gx, w_hh_f, w_hh_r, b_hh_f, b_hh_r, T, B, H, D, want_reserve, _given(lengths), rsv=True)
 
 
 def gru_seq_bwd_len(d_out, reserve, w_hh_f, w_hh_r, lengths, T, B, H, D):
     """gru_seq_bwd for a reserve of gru_seq_fwd_len_rsv -> (d_gx, d_gh, d_bias_part): rows t >= lengths[b] are exactly zero
     whatever d_out holds there."""
-    L = _lib.load()
-    _len_ok(lengths, B)
-    _len_hidden_ok(H)
-    d_out = _f32c(d_out, "d_out")
-    dev = d_out.device
-    d_gx = torch.empty(T, B, D * 3 * H, dtype=torch.float32, device=dev)
-    d_gh = torch.empty(T, B, D * 3 * H, dtype=torch.float32, device=dev)
-    nbt = int(L.slu_gru_bias_tiles(T, B, H, D))
-    d_bias_part = torch.empty(nbt, D, 6 * H, dtype=torch.float32, device=dev)
-    _lib.check(L.slu_gru_seq_bwd_len(d_out.data_ptr(), reserve.data_ptr(), w_hh_f.data_ptr(), _ptr(w_hh_r), d_gx.data_ptr(),
-                                     d_gh.data_ptr(), d_bias_part.data_ptr(), lengths.data_ptr(), T, B, H, D, _stream()),
-               "slu_gru_seq_bwd_len")
-    return d_gx, d_gh, d_bias_part
+    return _gru_seq_bwd(d_out, reserve, w_hh_f, w_hh_r, T, B, H, D, _given(lengths))
 
 
 def dropout_pool_len_fwd(x, lengths, mask, p, seed, offset, method, factor, offset_dev=None):
     """dropout_pool_fwd with windows clipped to t < lengths[b]: zero at to >= ceil(lengths[b] / factor).  The keep factor of
     element (t, b, c) is dropout_pool_fwd's (the dense batch's stream)."""
-    return _seq_pool_len(x, lengths, method, factor, (mask, p, seed, offset, offset_dev))
+    return _seq_pool(x, method, factor, (mask, p, seed, offset, offset_dev), _given(lengths))
 
 
 def dropout_pool_len_bwd(dy, x, lengths, mask, p, seed, offset, method, factor, offset_dev=None):
     """-> dx (T, B, C), exactly zero at t >= lengths[b] whatever dy holds beyond the valid outputs."""
-    L = _lib.load()
-    T, B, C = x.shape
-    _len_ok(lengths, B)
-    dy = _f32c(dy, "dy")
-    dx = torch.empty(T, B, C, dtype=torch.float32, device=x.device)
-    mp, mst, msb = _mask_args(mask, T, B, C)
-    _lib.check(L.slu_dropout_pool_len_bwd(dy.data_ptr(), x.data_ptr(), lengths.data_ptr(), mp, mst, msb, float(p), int(seed),
-                                          int(offset), _ptr(offset_dev), METHODS[method], factor, dx.data_ptr(), T, B, C,
-                                          _stream()), "slu_dropout_pool_len_bwd")
-    return dx
+    return _dropout_pool_bwd(dy, x, mask, p, seed, offset, method, factor, offset_dev, _given(lengths))
 
 
 def cls_maxpool_len_ce_fwd(h, weight, bias, lengths, y, values_per_slot):
@@ -1584,22 +1582,36 @@ def head_dropout_fusable(weight, p, mask, method, factor, h=None):
 # ------------------------------------------------------------------------------------------------
 # autograd Functions (one per fused stage of the encoder)
 # ------------------------------------------------------------------------------------------------
-def _intent_head_bwd(saved, d_loss, need_h, need_w, drop=None):
-    """The backward pass of both intent heads (slu_cls_maxpool_ce_bwd): saved = (h, weight, argmax_t, d_logits) of the
-    forward pass, drop = IntentHeadFn's (p, seed, offset, offset_dev) or None -> (dh, dW, db), None where not needed."""
+def _intent_head_tail(ctx, loss_acc, logits, pred):
+    """The end of both intent heads' forward -> (loss, acc, logits, pred), only `loss` differentiable."""
+    ctx.set_materialize_grads(False)       # no zero-filled gradients for acc / logits / pred
+    ctx.mark_non_differentiable(logits, pred)
+    acc = loss_acc[1]
+    ctx.mark_non_differentiable(acc)
+    IntentHeadFn.last_loss_acc = loss_acc  # (2,) float32 [loss, acc]: one-kernel metric accumulation
+    return loss_acc[0], acc, logits, pred
+
+
+def _intent_head_backward(ctx, d_loss, ih, iw, ib, drop=None):
+    """The backward pass of both intent heads (slu_cls_maxpool_ce_bwd); ih, iw, ib: the positions of h, weight and bias among
+    forward's six inputs, drop: IntentHeadFn's (p, seed, offset, offset_dev) or None."""
+    grads = [None] * 6
+    if d_loss is None:
+        return tuple(grads)
     L = _lib.load()
-    h, weight, argmax_t, d_logits = saved
+    h, weight, argmax_t, d_logits = ctx.saved_tensors
     p, seed, offset, offset_dev = drop if drop else (0.0, 0, 0, None)
     T, B, C = h.shape
     V = weight.shape[0]
     g = d_loss.contiguous().float()
-    dh = torch.empty_like(h) if need_h else None
-    dW = torch.empty_like(weight) if need_w else None
-    db = torch.empty(V, dtype=torch.float32, device=h.device) if need_w else None
+    need_w = ctx.needs_input_grad[iw] or ctx.needs_input_grad[ib]
+    dh = grads[ih] = torch.empty_like(h) if ctx.needs_input_grad[ih] else None
+    dW = grads[iw] = torch.empty_like(weight) if need_w else None
+    db = grads[ib] = torch.empty(V, dtype=torch.float32, device=h.device) if need_w else None
     _lib.check(L.slu_cls_maxpool_ce_bwd(d_logits.data_ptr(), argmax_t.data_ptr(), h.data_ptr(), weight.data_ptr(),
                                         g.data_ptr(), _ptr(dh), _ptr(dW), _ptr(db), float(p), int(seed), int(offset),
                                         _ptr(offset_dev), T, B, C, V, _stream()), "slu_cls_maxpool_ce_bwd")
-    return dh, dW, db
+    return tuple(grads)
 
 
 class IntentHeadFn(torch.autograd.Function):
@@ -1624,20 +1636,11 @@ class IntentHeadFn(torch.autograd.Function):
         ctx.drop = drop
         if need:
             ctx.save_for_backward(res[5] if drop else h, weight, argmax_t, d_logits)
-        ctx.set_materialize_grads(False)       # no zero-filled gradients for acc / logits / pred
-        ctx.mark_non_differentiable(logits, pred)
-        acc = loss_acc[1]
-        ctx.mark_non_differentiable(acc)
-        IntentHeadFn.last_loss_acc = loss_acc  # (2,) float32 [loss, acc]: one-kernel metric accumulation
-        return loss_acc[0], acc, logits, pred
+        return _intent_head_tail(ctx, loss_acc, logits, pred)
 
     @staticmethod
     def backward(ctx, d_loss, _d_acc, _d_logits, _d_pred):
-        if d_loss is None:
-            return None, None, None, None, None, None
-        need = ctx.needs_input_grad
-        dh, dW, db = _intent_head_bwd(ctx.saved_tensors, d_loss, need[0], need[1] or need[2], ctx.drop)
-        return dh, dW, db, None, None, None
+        return _intent_head_backward(ctx, d_loss, 0, 1, 2, ctx.drop)
 
 
 class IntentHeadLenFn(torch.autograd.Function):
@@ -1652,20 +1655,11 @@ class IntentHeadLenFn(torch.autograd.Function):
         loss_acc, logits, pred, argmax_t, d_logits = cls_maxpool_len_ce_fwd(h, weight, bias, lengths, y, values_per_slot)
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
             ctx.save_for_backward(h, weight, argmax_t, d_logits)
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(logits, pred)
-        acc = loss_acc[1]
-        ctx.mark_non_differentiable(acc)
-        IntentHeadFn.last_loss_acc = loss_acc
-        return loss_acc[0], acc, logits, pred
+        return _intent_head_tail(ctx, loss_acc, logits, pred)
 
     @staticmethod
     def backward(ctx, d_loss, _d_acc, _d_logits, _d_pred):
-        if d_loss is None:
-            return None, None, None, None, None, None
-        need = ctx.needs_input_grad
-        dh, dW, db = _intent_head_bwd(ctx.saved_tensors, d_loss, need[0], need[2] or need[3])
-        return dh, None, dW, db, None, None
+        return _intent_head_backward(ctx, d_loss, 0, 2, 3)
 
 
 def _frame_head_fwd(rows, weight, bias, y_rows, need):
@@ -2313,14 +2307,20 @@ class GRULayerFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        T, B, I, H, D, p, stream, method, factor = ctx.cfg
-        x, raw, reserve, mask, w_ih, w_hh_f, w_hh_r = ctx.saved_tensors
-        if p == 0.0 and factor == 1:
-            d_raw = dy
-        else:
-            d_raw = dropout_pool_bwd(dy, raw, mask, p, *stream[:2], method, factor, stream.offset_dev)
-        d_gx, d_gh, dbp = gru_seq_bwd(d_raw, reserve, w_hh_f, w_hh_r, T, B, H, D)
-        return tuple(_gru_layer_grads(ctx.needs_input_grad[:11], x, raw, d_gx, d_gh, dbp, w_ih, T, B, I, H, D) + [None] * 10)
+        return _gru_layer_bwd(ctx, dy, None)
+
+
+def _gru_layer_bwd(ctx, dy, lengths):
+    """backward of GRULayerFn (lengths None) and GRULayerLenFn; None for every forward input after the eleven tensors"""
+    T, B, I, H, D, p, stream, method, factor = ctx.cfg
+    x, raw, reserve, mask, w_ih, w_hh_f, w_hh_r = ctx.saved_tensors[:7]
+    if p == 0.0 and factor == 1:
+        d_raw = dy                                       # LEN: the BPTT kernel does not use d_out at t >= lengths[b]
+    else:
+        d_raw = _dropout_pool_bwd(dy, raw, mask, p, *stream[:2], method, factor, stream.offset_dev, lengths)
+    d_gx, d_gh, dbp = _gru_seq_bwd(d_raw, reserve, w_hh_f, w_hh_r, T, B, H, D, lengths)
+    grads = _gru_layer_grads(ctx.needs_input_grad[:11], x, raw, d_gx, d_gh, dbp, w_ih, T, B, I, H, D)
+    return tuple(grads + [None] * (len(ctx.needs_input_grad) - 11))
 
 
 def _gru_layer_grads(ng, x, raw, d_gx, d_gh, dbp, w_ih, T, B, I, H, D):
@@ -2382,14 +2382,7 @@ class GRULayerLenFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        T, B, I, H, D, p, stream, method, factor = ctx.cfg
-        x, raw, reserve, mask, w_ih, w_hh_f, w_hh_r, lengths = ctx.saved_tensors
-        if p == 0.0 and factor == 1:
-            d_raw = dy                                   # the BPTT kernel does not use d_out at t >= lengths[b]
-        else:
-            d_raw = dropout_pool_len_bwd(dy, raw, lengths, mask, p, *stream[:2], method, factor, stream.offset_dev)
-        d_gx, d_gh, dbp = gru_seq_bwd_len(d_raw, reserve, w_hh_f, w_hh_r, lengths, T, B, H, D)
-        return tuple(_gru_layer_grads(ctx.needs_input_grad[:11], x, raw, d_gx, d_gh, dbp, w_ih, T, B, I, H, D) + [None] * 9)
+        return _gru_layer_bwd(ctx, dy, ctx.saved_tensors[7])
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2413,52 +2406,53 @@ def gru_cell_bwd(d_h, d_drop, save, h_prev, d_gi, d_gh, d_h_prev, mask, p, seed,
                                   _stream()), "slu_gru_cell_bwd")
 
 
-def attention_fwd(keys, values, query, ctx, weights, inv_scale):
-    """keys (T, B, Kd) / values (T, B, Vd) time-major contiguous; query (B, Kd), ctx (B, Vd) row-strided views."""
+def _attention_fwd(keys, values, query, ctx, weights, inv_scale, n=None):
     L = _lib.load()
     T, B, Kd = keys.shape
     Vd = values.shape[2]
-    _lib.check(L.slu_attention_fwd(keys.data_ptr(), keys.stride(0), keys.stride(1), values.data_ptr(), values.stride(0),
-                                   values.stride(1), query.data_ptr(), query.stride(0), ctx.data_ptr(), ctx.stride(0),
-                                   weights.data_ptr(), float(inv_scale), B, T, Kd, Vd, _stream()), "slu_attention_fwd")
+    io = (keys.data_ptr(), keys.stride(0), keys.stride(1), values.data_ptr(), values.stride(0), values.stride(1),
+          query.data_ptr(), query.stride(0), ctx.data_ptr(), ctx.stride(0), weights.data_ptr())
+    if n is None:
+        _lib.check(L.slu_attention_fwd(*io, float(inv_scale), B, T, Kd, Vd, _stream()), "slu_attention_fwd")
+    else:
+        _len_ok(n, B)
+        _lib.check(L.slu_attention_len_fwd(*io, n.data_ptr(), float(inv_scale), B, T, Kd, Vd, _stream()), "slu_attention_len_fwd")
+
+
+def _attention_bwd(keys, values, query, d_ctx, weights, d_keys, d_values, d_query, inv_scale, n=None):
+    L = _lib.load()
+    T, B, Kd = keys.shape
+    Vd = values.shape[2]
+    if n is not None:
+        _len_ok(n, B)
+    assert d_keys.stride() == keys.stride() and d_values.stride() == values.stride()
+    io = (keys.data_ptr(), keys.stride(0), keys.stride(1), values.data_ptr(), values.stride(0), values.stride(1),
+          query.data_ptr(), query.stride(0), d_ctx.data_ptr(), d_ctx.stride(0), weights.data_ptr(), d_keys.data_ptr(),
+          d_values.data_ptr(), d_query.data_ptr(), d_query.stride(0))
+    if n is None:
+        _lib.check(L.slu_attention_bwd(*io, float(inv_scale), B, T, Kd, Vd, _stream()), "slu_attention_bwd")
+    else:
+        _lib.check(L.slu_attention_len_bwd(*io, n.data_ptr(), float(inv_scale), B, T, Kd, Vd, _stream()), "slu_attention_len_bwd")
+
+
+def attention_fwd(keys, values, query, ctx, weights, inv_scale):
+    """keys (T, B, Kd) / values (T, B, Vd) time-major contiguous; query (B, Kd), ctx (B, Vd) row-strided views."""
+    _attention_fwd(keys, values, query, ctx, weights, inv_scale)
 
 
 def attention_bwd(keys, values, query, d_ctx, weights, d_keys, d_values, d_query, inv_scale):
-    L = _lib.load()
-    T, B, Kd = keys.shape
-    Vd = values.shape[2]
-    assert d_keys.stride() == keys.stride() and d_values.stride() == values.stride()
-    _lib.check(L.slu_attention_bwd(keys.data_ptr(), keys.stride(0), keys.stride(1), values.data_ptr(), values.stride(0),
-                                   values.stride(1), query.data_ptr(), query.stride(0), d_ctx.data_ptr(), d_ctx.stride(0),
-                                   weights.data_ptr(), d_keys.data_ptr(), d_values.data_ptr(), d_query.data_ptr(),
-                                   d_query.stride(0), float(inv_scale), B, T, Kd, Vd, _stream()), "slu_attention_bwd")
+    _attention_bwd(keys, values, query, d_ctx, weights, d_keys, d_values, d_query, inv_scale)
 
 
 def attention_len_fwd(keys, values, query, ctx, weights, inv_scale, n):
     """attention_fwd over the first n[b] frames of row b (n: int32 CUDA tensor of B frame counts; include/slu_hip.h has
     the rule): weights[b, n[b]:] = 0, keys / values beyond are never read; bit-equal to attention_fwd on every row alone."""
-    L = _lib.load()
-    T, B, Kd = keys.shape
-    Vd = values.shape[2]
-    _len_ok(n, B)
-    _lib.check(L.slu_attention_len_fwd(keys.data_ptr(), keys.stride(0), keys.stride(1), values.data_ptr(), values.stride(0),
-                                       values.stride(1), query.data_ptr(), query.stride(0), ctx.data_ptr(), ctx.stride(0),
-                                       weights.data_ptr(), n.data_ptr(), float(inv_scale), B, T, Kd, Vd, _stream()),
-               "slu_attention_len_fwd")
+    _attention_fwd(keys, values, query, ctx, weights, inv_scale, _given(n))
 
 
 def attention_len_bwd(keys, values, query, d_ctx, weights, d_keys, d_values, d_query, inv_scale, n):
     """attention_bwd over the first n[b] frames of row b: d_keys / d_values accumulated below n[b], untouched beyond."""
-    L = _lib.load()
-    T, B, Kd = keys.shape
-    Vd = values.shape[2]
-    _len_ok(n, B)
-    assert d_keys.stride() == keys.stride() and d_values.stride() == values.stride()
-    _lib.check(L.slu_attention_len_bwd(keys.data_ptr(), keys.stride(0), keys.stride(1), values.data_ptr(), values.stride(0),
-                                       values.stride(1), query.data_ptr(), query.stride(0), d_ctx.data_ptr(), d_ctx.stride(0),
-                                       weights.data_ptr(), d_keys.data_ptr(), d_values.data_ptr(), d_query.data_ptr(),
-                                       d_query.stride(0), n.data_ptr(), float(inv_scale), B, T, Kd, Vd, _stream()),
-               "slu_attention_len_bwd")
+    _attention_bwd(keys, values, query, d_ctx, weights, d_keys, d_values, d_query, inv_scale, _given(n))
 
 
 def logsoftmax_dot_fwd(logits, y_u, logp_acc, lse):
