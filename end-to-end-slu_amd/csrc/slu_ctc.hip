@@ -24,6 +24,13 @@
 //               block scan, Levenshtein distance to the target by anti-diagonals (three diagonals in LDS)
 //   ctc_ler     one workgroup: out2 = [1 - sum errors / sum S, sum S]
 //
+// slu_ctc_align ("CTC forced alignment" in the header), one launch, or two with a score, no host synchronisation:
+//   ctc_lse       as above, only where a score is wanted (the path does not depend on it)
+//   ctc_align<LT> one workgroup per utterance, LT threads = one state per lane: the max-recursion on the raw logits in an
+//               LDS ping-pong (one barrier per frame, the lane's own logit loaded a frame ahead), one back-pointer byte
+//               per (frame, state) to the workspace, coalesced across s; then lane 0 walks the n_b bytes back, and all
+//               lanes turn the path into pos and starts.
+//
 // Bad tables cannot index out of bounds: n_b is clamped into [1, N], an utterance whose rows leave [0, N) or that holds a
 // label outside [0, V) (clamped for addressing) or equal to the blank is infeasible; the host rejects all of these first.
 #include "slu_common.h"
@@ -375,6 +382,103 @@ ctc_ler_kernel(const int* __restrict__ errors, const int* __restrict__ tlen, int
   }
 }
 
+// ---- forced alignment: the Viterbi path through the same lattice -------------------------------------------------------
+// One workgroup per utterance, LT threads, one state per lane.  v_t(s) = x[t, l'_s] + max(stay, step, skip) on the RAW
+// logits (the frame's lse is common to every path), the first of equal candidates in that order winning: a later one
+// replaces the best so far only where it is strictly greater, so the -inf pads and a NaN never win and s - back >= 0.
+// One add per frame and state, nothing to reassociate.
+template <int LT>
+__global__ void __launch_bounds__(LT)
+ctc_align_kernel(const float* __restrict__ logits, const float* __restrict__ lse, const int* __restrict__ lengths,
+                 const int* __restrict__ offsets, const long long* __restrict__ targets, const int* __restrict__ tlen, int V,
+                 int S, int blank, long long N, unsigned char* bp, int* path, int* __restrict__ pos,
+                 int* __restrict__ starts, float* __restrict__ score, int* __restrict__ feas) {
+  __shared__ float pp[2][LT + 2];             // ping-pong; state s at index s + 2, two -inf pads in front
+  __shared__ int lab_s[LT], flags[2];
+  const int b = blockIdx.x, s = threadIdx.x;
+  const CtcRow r = ctc_row(lengths, offsets, tlen, b, S, N);
+  const int LS = 2 * S + 1;                   // row stride of bp
+  if (s < 2) flags[s] = 0;
+  bool bad = false;
+  const int lab = s < r.L ? ctc_label(targets, b, S, s, V, blank, &bad) : blank;
+  lab_s[s] = lab;
+  int* __restrict__ sb = starts + (long long)b * S;
+  for (int j = s; j < S; j += LT) sb[j] = -1;
+  __syncthreads();
+  if (s < r.L) {
+    if (bad) atomicOr(&flags[0], 1);
+    if ((s & 1) && s >= 3 && lab_s[s - 2] == lab) atomicAdd(&flags[1], 1);
+  }
+  __syncthreads();
+  const bool feasible = r.valid && flags[0] == 0 && r.n >= r.Sb + flags[1];
+  if (!feasible) {                            // uniform over the workgroup
+    if (r.valid)
+      for (int t = s; t < r.n; t += LT) pos[r.off + t] = -1;
+    if (s == 0) {
+      if (score) score[b] = -INFINITY;
+      feas[b] = 0;
+    }
+    return;
+  }
+  for (int i = s; i < 2 * (LT + 2); i += LT) (&pp[0][0])[i] = -INFINITY;
+  const bool live = s < r.L;
+  const bool skip = live && (s & 1) && s >= 3 && lab_s[s - 2] != lab;
+  const float* __restrict__ lcol = logits + lab;
+  unsigned char* bpb = bp + (long long)r.off * LS;
+  int* pb = path + r.off;
+  float x = live ? lcol[(long long)r.off * V] : 0.0f;
+  __syncthreads();
+  int p = 0;
+  for (int t = 0; t < r.n; ++t) {
+    float val = -INFINITY;
+    unsigned char back = 0;
+    if (live) {
+      if (t == 0) {
+        if (s < 2) val = x;
+      } else {
+        float best = pp[p][s + 2];
+        const float step = pp[p][s + 1], jump = skip ? pp[p][s] : -INFINITY;
+        if (step > best) { best = step; back = 1; }
+        if (jump > best) { best = jump; back = 2; }
+        val = x + best;
+      }
+    }
+    const float x_next = (live && t + 1 < r.n) ? lcol[((long long)r.off + t + 1) * V] : 0.0f;   // in flight across the barrier
+    pp[p ^ 1][s + 2] = val;
+    if (live) bpb[(long long)t * LS + s] = back;
+    p ^= 1;
+    x = x_next;
+    __syncthreads();                          // also orders the back-pointer bytes in front of the walk below
+  }
+  // the walk: n_b dependent byte loads by one lane
+  float vbest = 0.0f;
+  if (s == 0) {
+    const float a1 = pp[p][r.L - 1 + 2], a2 = r.L > 1 ? pp[p][r.L - 2 + 2] : -INFINITY;
+    int cur = r.L - 1;
+    vbest = a1;
+    if (a2 > a1) { cur = r.L - 2; vbest = a2; }
+    for (int t = r.n - 1; t >= 0; --t) {
+      pb[t] = cur;
+      if (t > 0) cur -= bpb[(long long)t * LS + cur];
+    }
+  }
+  __syncthreads();
+  for (int t = s; t < r.n; t += LT) {
+    const int st = pb[t], before = t > 0 ? pb[t - 1] : -1;
+    const int j = (st & 1) ? (st >> 1) : -1;
+    pos[r.off + t] = j;
+    if (j >= 0 && st != before) sb[j] = t;
+  }
+  if (s == 0) feas[b] = 1;
+  if (score && s < 64) {                      // sum of lse in float64: lane-strided partial sums, then one fixed tree
+    double acc = 0.0;
+    for (int t = s; t < r.n; t += 64) acc += (double)lse[r.off + t];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if (s == 0) score[b] = (float)((double)vbest - acc);
+  }
+}
+
 static int ctc_args(const char* who, int64_t N, int64_t V, int64_t B, int64_t S, int64_t blank) {
   SLU_REQUIRE(N > 0 && V > 0 && B > 0 && S > 0, "%s: non-positive size", who);
   SLU_REQUIRE(N < (1ll << 31) && V < (1ll << 31) && B < (1ll << 31) && S < (1ll << 31) && B * S < (1ll << 31),
@@ -384,6 +488,13 @@ static int ctc_args(const char* who, int64_t N, int64_t V, int64_t B, int64_t S,
     SLU_FAIL(SLU_ERR_UNSUPPORTED, "%s: 2 S + 1 = %lld states, instantiated up to %d", who, (long long)(2 * S + 1),
              CTC_MAX_STATES);
   return SLU_OK;
+}
+
+// the sizes ctc_args refuses (V and the blank apart): what the two workspace queries answer with 0
+static bool ctc_sizes_refused(int64_t N, int64_t B, int64_t S) {
+  if (N <= 0 || B <= 0 || S <= 0 || N >= (1ll << 31) || B >= (1ll << 31)) return true;
+  if (S > (CTC_MAX_STATES - 1) / 2) return true;                  // in front of the product: B * S cannot overflow
+  return B * S >= (1ll << 31);
 }
 
 // workspace: lse (N) | A (N, 2S+1) | Bt (N, 2S+1) floats, then own (B, 2S+1) | rowb (N) | feas (B) ints
@@ -406,12 +517,28 @@ static CtcWs ctc_ws(void* base, int64_t N, int64_t B, int64_t S) {
   return w;
 }
 
+// workspace of slu_ctc_align: lse (N) floats | path (N) ints | back-pointers (N, 2S+1) bytes, rounded up to 4 bytes
+struct CtcAlignWs {
+  float* lse;
+  int* path;
+  unsigned char* bp;
+  size_t bytes;
+};
+static CtcAlignWs ctc_align_ws(void* base, int64_t N, int64_t S) {
+  CtcAlignWs w;
+  w.lse = (float*)base;
+  w.path = (int*)(w.lse + N);
+  w.bp = (unsigned char*)(w.path + N);
+  w.bytes = 8 * (size_t)N + (((size_t)N * (size_t)(2 * S + 1) + 3) & ~(size_t)3);
+  return w;
+}
+
 }  // namespace slu
 
 using namespace slu;
 
 extern "C" size_t slu_ctc_workspace_bytes(int64_t N, int64_t B, int64_t S) {
-  if (N <= 0 || B <= 0 || S <= 0 || N >= (1ll << 31) || B >= (1ll << 31) || 2 * S + 1 > CTC_MAX_STATES) return 0;
+  if (ctc_sizes_refused(N, B, S)) return 0;
   return ctc_ws(nullptr, N, B, S).bytes;
 }
 
@@ -470,5 +597,41 @@ extern "C" int slu_ctc_greedy_errors(const float* logits, const int32_t* lengths
   hipLaunchKernelGGL(ctc_ler_kernel, dim3(1), dim3(CTC_THREADS), 0, st, (const int*)errors, (const int*)target_lengths,
                      (int)B, (int)S, out2);
   SLU_CHECK_LAUNCH("ctc_ler_kernel");
+  return SLU_OK;
+}
+
+extern "C" size_t slu_ctc_align_workspace_bytes(int64_t N, int64_t B, int64_t S) {
+  if (ctc_sizes_refused(N, B, S)) return 0;
+  return ctc_align_ws(nullptr, N, S).bytes;
+}
+
+#define CTC_LAUNCH_ALIGN(LT)                                                                                           \
+  hipLaunchKernelGGL(ctc_align_kernel<LT>, dim3((unsigned)B), dim3(LT), 0, st, logits, (const float*)(score ? w.lse : nullptr), \
+                     (const int*)lengths, (const int*)offsets, (const long long*)targets, (const int*)target_lengths,  \
+                     (int)V, (int)S, (int)blank, (long long)N, w.bp, w.path, (int*)pos, (int*)starts, score,           \
+                     (int*)feasible)
+
+extern "C" int slu_ctc_align(const float* logits, const int32_t* lengths, const int32_t* offsets, const int64_t* targets,
+                             const int32_t* target_lengths, int64_t N, int64_t V, int64_t B, int64_t S, int64_t blank,
+                             int32_t* pos, int32_t* starts, float* score, int32_t* feasible, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+  SLU_REQUIRE(logits && lengths && offsets && targets && target_lengths && pos && starts && feasible && workspace,
+              "slu_ctc_align: null pointer");
+  const int rc = ctc_args("slu_ctc_align", N, V, B, S, blank);
+  if (rc != SLU_OK) return rc;
+  const CtcAlignWs w = ctc_align_ws(workspace, N, S);
+  if (workspace_bytes < w.bytes)
+    SLU_FAIL(SLU_ERR_WORKSPACE, "slu_ctc_align: workspace of %zu bytes, %zu needed", workspace_bytes, w.bytes);
+  hipStream_t st = (hipStream_t)stream;
+  if (score) {                                   // the only pass over V: the path itself does not need it
+    hipLaunchKernelGGL(ctc_lse_kernel, dim3((unsigned)N), dim3(CTC_THREADS), 0, st, logits, (int)V, w.lse);
+    SLU_CHECK_LAUNCH("ctc_lse_kernel");
+  }
+  const int64_t L = 2 * S + 1;
+  if (L <= 64) CTC_LAUNCH_ALIGN(64);
+  else if (L <= 128) CTC_LAUNCH_ALIGN(128);
+  else if (L <= 256) CTC_LAUNCH_ALIGN(256);
+  else CTC_LAUNCH_ALIGN(512);
+  SLU_CHECK_LAUNCH("ctc_align_kernel");
   return SLU_OK;
 }

@@ -611,6 +611,100 @@ def _strip_stress(mark):
     return mark.rstrip("0123456789")
 
 
+# ---- CTC forced alignment -> frame labels and TextGrids ("CTC forced alignment") ----------------------
+def _label_end(pos):
+    """The frame behind the last frame that sits on a label (0: the path is all blanks)."""
+    return max((t + 1 for t, p in enumerate(pos) if p >= 0), default=0)
+
+
+def frame_labels(starts, labels, n_frames, fill="hold", pos=None):
+    """One label per frame from an alignment (PretrainedModel.align_phonemes(..., want_pos=True)): starts[j] the first
+    frame of labels[j], pos[t] the target position at frame t or -1 on a blank -> n_frames ints, -1 = no label.
+    fill="hold" (the project's own rule: CTC paths are peaky, most frames of a label sit on blanks): labels[j] lasts
+    from starts[j] to starts[j + 1]; the last one to the end of its own frames; the frames before the first label and the
+    trailing blank run are -1.  fill="none": only the frames on the label itself carry it.
+    pos is MANDATORY wherever there is a label, for both rules (the end of the last label's own frames, and which frames
+    are blanks, are known from it alone): without it, or with a pos of another length, the call is a ValueError.  Only
+    an empty target (all frames -1) needs none."""
+    if fill not in ("hold", "none"):
+        raise ValueError("frame_labels: fill must be 'hold' or 'none', got %r" % (fill,))
+    out = [-1] * int(n_frames)
+    if len(labels) == 0:
+        return out
+    if pos is None or len(pos) != n_frames or len(starts) != len(labels):
+        raise ValueError("frame_labels: needs pos (n_frames entries) and one start per label")
+    if fill == "none":
+        return [int(labels[p]) if p >= 0 else -1 for p in pos]
+    bounds = [int(v) for v in starts] + [_label_end(pos)]
+    for j, lab in enumerate(labels):
+        for t in range(bounds[j], bounds[j + 1]):
+            out[t] = int(lab)
+    return out
+
+
+def write_textgrid(path, tiers, xmax):
+    """The long "ooTextFile" format read_textgrid parses: tiers = {name: [(t0, t1, mark), ...]} with increasing times
+    inside [0, xmax].  ASRDataset._track ignores absolute times and concatenates round((t1 - t0) fs) repeats, so every
+    tier is made to tile [0, xmax]: gaps become "" intervals (read back as -1), empty intervals are dropped.  Times are
+    written with repr(float), which float() reads back to the bit.  A quote in a mark is doubled (read_textgrid undoes
+    it); a tier name with a quote is refused, since the reader takes names as they stand."""
+    xmax = float(xmax)
+    out = ['File type = "ooTextFile"', 'Object class = "TextGrid"', "", "xmin = 0.0", "xmax = %r" % xmax, "tiers? <exists>",
+           "size = %d" % len(tiers), "item []:"]
+    for k, (name, intervals) in enumerate(tiers.items()):
+        if '"' in name or "\n" in name:                  # read_textgrid takes a tier's name as it stands, unescaped
+            raise ValueError("write_textgrid: tier name %r holds a quote or a line break" % (name,))
+        tiled, at = [], 0.0
+        for t0, t1, mark in intervals:
+            t0, t1 = float(t0), float(t1)
+            if t0 < at or t1 < t0 or t1 > xmax:
+                raise ValueError("write_textgrid: tier %r: interval (%r, %r) overlaps its predecessor or leaves [0, %r]"
+                                 % (name, t0, t1, xmax))
+            if t0 > at:
+                tiled.append((at, t0, ""))
+            if t1 > t0:
+                tiled.append((t0, t1, str(mark)))
+            at = t1
+        if at < xmax:
+            tiled.append((at, xmax, ""))
+        out += ["    item [%d]:" % (k + 1), '        class = "IntervalTier"', '        name = "%s"' % name,
+                "        xmin = 0.0", "        xmax = %r" % xmax, "        intervals: size = %d" % len(tiled)]
+        for i, (t0, t1, mark) in enumerate(tiled):
+            out += ["        intervals [%d]:" % (i + 1), "            xmin = %r" % t0, "            xmax = %r" % t1,
+                    '            text = "%s"' % mark.replace('"', '""')]
+    with open(path, "w", encoding="utf-8") as f:
+        f.write("\n".join(out) + "\n")
+
+
+def alignment_tiers(starts, pos, words, lexicon, Sy_phoneme, num_samples, fs, factor):
+    """The two tiers of one utterance from its phoneme alignment (align_phonemes(..., want_pos=True): starts, pos) ->
+    ({"words": [...], "phones": [...]}, xmax) for write_textgrid.  words: the transcript; the aligned labels are
+    TranscriptASRDataset's — the lexicon's phonemes of every word that are in Sy_phoneme, in order.  Frame t covers the
+    samples [t factor, (t + 1) factor), cut at num_samples; times are samples / fs.
+    phones: frame_labels' "hold" rule, marks = the Sy_phoneme strings.  words: derived from the same alignment — a word
+    spans from its first phoneme's start to the next aligned word's start, the last one to the end of its last phoneme's
+    hold; a word without aligned phonemes gets no interval; marks = the transcript's words, so the reader maps
+    out-of-vocabulary words to -1 as it does for forced alignments made elsewhere."""
+    index = {}
+    for i, v in enumerate(Sy_phoneme):
+        index.setdefault(v, i)
+    per_word = [[index[p] for p in lexicon.get(w, ()) if p in index] for w in words]
+    labels = [v for ph in per_word for v in ph]
+    if len(labels) != len(starts):
+        raise ValueError("alignment_tiers: %d starts for %d phonemes of the transcript" % (len(starts), len(labels)))
+    ell = int(num_samples)
+    at = lambda frame: min(int(frame) * int(factor), ell) / float(fs)
+    bounds = [int(v) for v in starts] + [_label_end(pos)]
+    phones = [(at(bounds[j]), at(bounds[j + 1]), Sy_phoneme[lab]) for j, lab in enumerate(labels)]
+    first, j = [], 0
+    for w, ph in zip(words, per_word):
+        if ph:
+            first.append((w, bounds[j]))
+        j += len(ph)
+    word_tier = [(at(f0), at(first[k + 1][1] if k + 1 < len(first) else bounds[-1]), w) for k, (w, f0) in enumerate(first)]
+    return {"words": word_tier, "phones": phones}, ell / float(fs)
+
+
 class CollateWavsASR:
     """list of (waveform, phoneme labels, word labels) -> (x (B,T_max) float32 zero-padded, y_phoneme
     (B,U_p) int64, y_word (B,U_w) int64, both padded with the ignore index -1) — reference data.py:511-545.

@@ -1975,6 +1975,59 @@ class PretrainedModel(torch.nn.Module):
         offsets, _ = _ops.frame_pack_plan(ph.n_host)
         return [hyp[o:o + n] for o, n in zip(offsets, hyp_len)]
 
+    def _align(self, x, lengths, y, name, word, want_pos):
+        """The body of align_phonemes / align_words: the length-aware stages, the pack and the Linear of decode_phonemes
+        (the word layers on top for the word head), then ops.ctc_align.  One device-to-host copy at the end."""
+        if not self.ctc:
+            raise ValueError("ctc: %s needs a CTC model (SLU_ASR_CTC=1 at construction)" % name)
+        if self.training:
+            raise ValueError("lengths: the length-aware path is inference only (dropout is not applied): call eval() first")
+        if word and self.pretraining_type == 1:
+            raise ValueError("ctc: align_words needs a word head (pretraining_type 1 trains the phoneme head only)")
+        first = self._cnn_stages + self._phone_stages
+        more = list(self._word_stages) if word else []
+        B = x.shape[0] if torch.is_tensor(x) and x.dim() == 2 else -1
+        y, n_y = self._ctc_targets(y, "y_word" if word else "y_phoneme", B)
+        x, host = _enter_len(self, x, lengths, first + more)
+        with torch.no_grad():
+            run = _run_stages_len(first, x, host, pack=True)
+            if word:
+                run = _run_stages_len(more, run.out, run.n_host, pack=True)
+            n_dev, off = run.n_dev.contiguous(), run.pack[0].contiguous()
+            hp, _ = _ops.frame_pack_len(run.out, None, n_dev, off, run.pack[1])
+            lin = self.word_linear if word else self.phoneme_linear
+            logits = _ops.gemm(hp, lin.weight.detach().t(), lin.bias.detach())
+            pos, starts, score, feasible = _ops.ctc_align(logits, n_dev, off, y, n_y, lin.out_features - 1)
+            Bn, S = starts.shape
+            parts = [starts.reshape(-1), score, feasible] + ([pos] if want_pos else [])
+            out = torch.cat([p.to(torch.float64) for p in parts]).cpu().tolist()        # ints below 2^31 and fp32: exact
+        offsets, _ = _ops.frame_pack_plan(run.n_host)
+        res = []
+        for b, n in enumerate(run.n_host):
+            if out[Bn * S + Bn + b] == 0:
+                res.append(None)
+                continue
+            one = ([int(v) for v in out[b * S:b * S + int(n_y[b])]], int(n), out[Bn * S + b])
+            if want_pos:
+                o = Bn * S + 2 * Bn + offsets[b]
+                one += ([int(v) for v in out[o:o + n]],)
+            res.append(one)
+        return res
+
+    def align_phonemes(self, x, lengths, y_phoneme, want_pos=False):
+        """CTC forced alignment on the phoneme head (a CTC model in eval mode; include/slu_hip.h "CTC forced alignment"):
+        x (B, T) waveforms, lengths their sample counts, y_phoneme (B, S) int64 label sequences padded with -1 (the
+        format forward takes) -> per utterance (starts, n_frames, score): the first frame of every label on the best CTC
+        path, the utterance's frame count (stage_lengths) and the path's log-probability; None for an infeasible row
+        (fewer frames than the labels need).  want_pos: a fourth entry, the target position at each of the n_frames
+        frames, -1 on a blank (what data.frame_labels needs).  Row b's result is that of x[b:b+1, :lengths[b]] aligned
+        alone."""
+        return self._align(x, lengths, y_phoneme, "align_phonemes", False, want_pos)
+
+    def align_words(self, x, lengths, y_word, want_pos=False):
+        """align_phonemes on the word head (its frames are word_downsample_factor samples long)."""
+        return self._align(x, lengths, y_word, "align_words", True, want_pos)
+
     def _posteriors_len(self, x, lengths):
         """compute_posteriors with per-utterance lengths: the length-aware evaluation of compute_features(x, lengths), the two
         Linear layers on the packed valid frames only, and one scatter each that writes the zeros beyond them."""

@@ -1811,7 +1811,7 @@ class FrameHeadLenFn(torch.autograd.Function):
         return dh, None, None, None, dW, db, None
 
 
-CTC_MAX_STATES = 512       # 2 S + 1 states slu_ctc_loss_fwd is instantiated for (csrc/slu_ctc.hip)
+CTC_MAX_STATES = 512       # 2 S + 1 states slu_ctc_loss_fwd / slu_ctc_align are instantiated for (csrc/slu_ctc.hip)
 
 
 def ctc_prepare(targets, target_lengths, V, blank, device):
@@ -1912,6 +1912,39 @@ def ctc_greedy(logits, lengths, offsets, targets, target_lengths, blank):
         raise ValueError("ctc: targets must be an int64 tensor of shape (%d, S)" % B)
     tg, tl = ctc_prepare(targets, target_lengths, V, blank, logits.device)
     return _ctc_greedy_dev(logits, lengths, offsets, tg, tl, blank)
+
+
+def _ctc_align_dev(logits, lengths, offsets, tg, tl, blank, want_score=True):
+    L = _lib.load()
+    N, V = logits.shape
+    B, S = tg.shape
+    dev = logits.device
+    nbytes = L.slu_ctc_align_workspace_bytes(N, B, S)
+    ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=dev)
+    pos = torch.empty(N, dtype=torch.int32, device=dev)
+    starts = torch.empty(B, S, dtype=torch.int32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev) if want_score else None
+    feasible = torch.empty(B, dtype=torch.int32, device=dev)
+    _lib.check(L.slu_ctc_align(logits.data_ptr(), lengths.data_ptr(), offsets.data_ptr(), tg.data_ptr(), tl.data_ptr(), N, V, B,
+                               S, int(blank), pos.data_ptr(), starts.data_ptr(), score.data_ptr() if want_score else None,
+                               feasible.data_ptr(), ws.data_ptr(), nbytes, _stream()), "slu_ctc_align")
+    return pos, starts, score, feasible
+
+
+def ctc_align(logits, lengths, offsets, targets, target_lengths, blank, want_score=True):
+    """slu_ctc_align (include/slu_hip.h, "CTC forced alignment"): the best CTC path of every target through its rows of the
+    packed logits (read only).  Arguments as ctc_loss -> (pos (N) int32: the target position at every packed row, -1 on a
+    blank; starts (B, S) int32: the first frame of every target position, -1 behind the target; score (B) fp32: the
+    path's log-probability, None without want_score; feasible (B) int32).  An infeasible row: -1 / -1 / -inf / 0.  starts
+    has max(S, 1) columns (ctc_prepare).  The refusals of the targets and the blank come first (they need no device), then
+    those of the logits and the tables."""
+    if not torch.is_tensor(logits) or logits.dim() != 2:
+        raise ValueError("ctc: logits must be a contiguous float32 CUDA tensor (N, V)")
+    tg, tl = ctc_prepare(targets, target_lengths, logits.shape[1], blank, logits.device)
+    N, V, B = _ctc_logits(logits, lengths, offsets)
+    if tg.shape[0] != B:
+        raise ValueError("ctc: targets must be an int64 tensor of shape (%d, S)" % B)
+    return _ctc_align_dev(logits, lengths, offsets, tg, tl, blank, want_score)
 
 
 class CTCHeadLenFn(torch.autograd.Function):

@@ -920,6 +920,39 @@ int slu_ctc_greedy_errors(const float* logits, const int32_t* lengths, const int
                           const int32_t* target_lengths, int64_t N, int64_t V, int64_t B, int64_t S, int64_t blank,
                           int32_t* hyp, int32_t* hyp_len, int32_t* errors, float* out2, void* stream);
 
+/* -------- CTC forced alignment: frame labels from a transcript and a CTC model — added under ABI 10 (two new entry
+ * points; nothing existing changed, so the version number stays).  No counterpart in the reference, which reads forced
+ * alignments made elsewhere.  Layout, clamps, the "infeasible" conditions and their order: slu_ctc_loss_fwd's (above);
+ * logits are READ ONLY.
+ * Definition (slu_ctc_align): the best path (Viterbi) through the lattice slu_ctc_loss_fwd sums over.
+ *   lattice    the extended sequence l' of utterance b has L = 2 S_b + 1 states, blanks around every label.  The recursion
+ *              runs on the RAW logits x — the frame's lse is common to every path, so the arg-max path does not depend
+ *              on it:
+ *                v_0(s) = x[0, l'_s] for s < 2, else -inf;
+ *                v_t(s) = x[t, l'_s] + max(v_{t-1}(s), v_{t-1}(s-1), v_{t-1}(s-2)),
+ *              s-2 allowed iff s is odd, s >= 3 and l'_s != l'_{s-2}.
+ *   tie rule   among equal candidates the first in the order stay (s), step (s-1), skip (s-2) wins; the final state is
+ *              the larger of v_{n-1}(L-1) and v_{n-1}(L-2), L-1 winning a tie.  One fp32 add per (frame, state), in that
+ *              order, nothing reassociated: on inputs whose partial sums are exact in fp32 the path is defined bit for bit.
+ *   pos        (N) int32: for the packed row offsets[b] + t, the target position (s-1)/2 of the path's state at frame t,
+ *              or -1 for a blank;
+ *   starts     (B, S) int32: the first frame of target position j; -1 for j >= S_b;
+ *   score      (B), may be NULL: v_best - sum_t lse[t], the best path's log-probability.  lse[t] is the fp32 value of the
+ *              loss's own pass; the sum is taken in float64 in one fixed order (64 strided partial sums in increasing t,
+ *              then one fixed tree), and the difference is rounded to fp32 once.  score = NULL skips that pass;
+ *   feasible   (B) int32: 0 or 1;
+ *   infeasible row: pos = -1 on its rows (where they lie inside [0, N)), starts = -1, score = -inf, feasible = 0;
+ *   S_b = 0    the path is all blanks: pos = -1, starts = -1, feasible = 1, score = the blank's log-probability summed.
+ * No floating-point atomics, no host read: two runs are bit-equal.
+ * Supported: 2 S + 1 <= 512 (SLU_ERR_UNSUPPORTED beyond).  SLU_ERR_INVALID_ARG: a NULL pointer other than score, a
+ * non-positive size, blank outside [0, V), N or V or B * S >= 2^31; SLU_ERR_WORKSPACE: fewer than
+ * slu_ctc_align_workspace_bytes(N, B, S) bytes (0 for sizes the call would refuse): N floats (lse), N int32 (the path's
+ * states) and one back-pointer byte per (row, state).  All refusals happen before any launch.                         */
+size_t slu_ctc_align_workspace_bytes(int64_t N, int64_t B, int64_t S);
+int slu_ctc_align(const float* logits, const int32_t* lengths, const int32_t* offsets, const int64_t* targets,
+                  const int32_t* target_lengths, int64_t N, int64_t V, int64_t B, int64_t S, int64_t blank, int32_t* pos,
+                  int32_t* starts, float* score, int32_t* feasible, void* workspace, size_t workspace_bytes, void* stream);
+
 /* -------- Adam: torch.optim.Adam(model.parameters(), lr) (training.py:19, default betas / eps) ------
  * One launch updates up to slu_adam_max_tensors() tensors of one dtype (elem_bytes 4 / 8); the pointer
  * arrays are HOST arrays of device pointers (they travel in the kernel arguments: hipGraph-safe).
