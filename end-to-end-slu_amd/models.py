@@ -35,6 +35,7 @@ from slu_hip import ops as _ops
 from slu_hip import lib as _lib
 from slu_hip import knobs as _knobs
 from slu_hip import lexicon as _lexicon
+from slu_hip import decode as _decode
 
 
 # ------------------------------------------------------------------------------------------------
@@ -289,6 +290,16 @@ def mask_augment_enabled():
     with augment=True; "1" — its waveforms pass through the length-taking augmentation kernels (_enter_len) and the
     stages run on the lengths behind them.  training.mask_augment_enabled adds the Trainer's rule: 1 needs SLU_MASK_TRAIN=1."""
     return _knobs.get("SLU_MASK_AUGMENT")
+
+
+def _fold_log_mass(parts):
+    """log of the summed mass of `parts` (log-masses, Python floats) in their order; one part is returned as it is."""
+    if len(parts) == 1:
+        return parts[0]
+    m = max(parts)
+    if m == float("-inf"):
+        return m
+    return float(m + np.log(sum(np.exp(v - m) for v in parts)))
 
 
 def asr_ctc_enabled():
@@ -1952,28 +1963,76 @@ class PretrainedModel(torch.nn.Module):
         self.ctc_records.append(_ops.CTCHeadLenFn.last_out4)
         return phoneme_loss, word_loss, phoneme_acc, word_acc
 
-    def decode_phonemes(self, x, lengths):
-        """Greedy CTC decoding of the phoneme head (a CTC model in eval mode): x (B, T) waveforms, lengths their sample
-        counts -> one list of phoneme indices per utterance (per frame the first arg-max, repeats collapsed, blanks
-        dropped: slu_ctc_greedy_errors).  One device-to-host copy at the end."""
+    def _decode(self, x, lengths, name, word, beam, topk, nbest):
+        """The body of decode_phonemes / decode_words: the length-aware stages, the pack and the Linear (the word layers on
+        top for the word head), then ops.ctc_greedy (beam None) or decode.ctc_beam_search.  One device-to-host copy at the
+        end."""
         if not self.ctc:
-            raise ValueError("ctc: decode_phonemes needs a CTC model (SLU_ASR_CTC=1 at construction)")
+            raise ValueError("ctc: %s needs a CTC model (SLU_ASR_CTC=1 at construction)" % name)
         if self.training:
             raise ValueError("lengths: the length-aware path is inference only (dropout is not applied): call eval() first")
+        if word and self.pretraining_type == 1:
+            raise ValueError("ctc: decode_words needs a word head (pretraining_type 1 trains the phoneme head only)")
+        if beam is None:
+            if topk is not None or nbest != 1:
+                raise ValueError("ctc: topk and nbest belong to the beam search: pass beam=W")
+        else:
+            topk = _decode.MAX_TOPK if topk is None else topk
+            _decode.beam_params(beam, topk, _decode.MAX_LEN)
+            if isinstance(nbest, bool) or not isinstance(nbest, int) or not 1 <= nbest <= beam:
+                raise ValueError("ctc: nbest %r outside [1, beam = %d]" % (nbest, beam))
         first = self._cnn_stages + self._phone_stages
-        x, host = _enter_len(self, x, lengths, first)
+        more = list(self._word_stages) if word else []
+        x, host = _enter_len(self, x, lengths, first + more)
         with torch.no_grad():
-            ph = _run_stages_len(first, x, host, pack=True)
-            n_dev, off = ph.n_dev.contiguous(), ph.pack[0].contiguous()
-            hp, _ = _ops.frame_pack_len(ph.out, None, n_dev, off, ph.pack[1])
-            pl = self.phoneme_linear
-            logits = _ops.gemm(hp, pl.weight.detach().t(), pl.bias.detach())
+            run = _run_stages_len(first, x, host, pack=True)
+            if word:
+                run = _run_stages_len(more, run.out, run.n_host, pack=True)
+            n_dev, off = run.n_dev.contiguous(), run.pack[0].contiguous()
+            hp, _ = _ops.frame_pack_len(run.out, None, n_dev, off, run.pack[1])
+            lin = self.word_linear if word else self.phoneme_linear
+            logits = _ops.gemm(hp, lin.weight.detach().t(), lin.bias.detach())
             B = len(host)
-            _, hyp, hyp_len, _ = _ops.ctc_greedy(logits, n_dev, off, torch.zeros(B, 1, dtype=torch.int64), [0] * B,
-                                                 pl.out_features - 1)
-            hyp, hyp_len = hyp.cpu().tolist(), hyp_len.cpu().tolist()
-        offsets, _ = _ops.frame_pack_plan(ph.n_host)
-        return [hyp[o:o + n] for o, n in zip(offsets, hyp_len)]
+            if beam is None:
+                _, hyp, hyp_len, _ = _ops.ctc_greedy(logits, n_dev, off, torch.zeros(B, 1, dtype=torch.int64), [0] * B,
+                                                     lin.out_features - 1)
+                hyp, hyp_len = hyp.cpu().tolist(), hyp_len.cpu().tolist()
+                offsets, _ = _ops.frame_pack_plan(run.n_host)
+                return [hyp[o:o + n] for o, n in zip(offsets, hyp_len)]
+            # a labelling is no longer than its frames, so up to MAX_LEN = 255 frames (10.2 s at the phoneme head's 40 ms)
+            # the bound never binds and the copy stays small; beyond, prefixes stop growing at 255 labels
+            L = max(1, min(_decode.MAX_LEN, max(run.n_host)))
+            labels, lens, scores, n_hyp = _decode.ctc_beam_search(logits, (n_dev, off), lin.out_features - 1, beam, topk, L)
+            parts = [labels.reshape(-1), lens.reshape(-1), n_hyp, scores.reshape(-1)]
+            out = torch.cat([p.to(torch.float64) for p in parts]).cpu().tolist()        # ints below 2^31 and fp32: exact
+        o_len, o_n, o_sc = B * beam * L, B * beam * L + B * beam, B * beam * L + B * beam + B
+        res = []
+        for b in range(B):
+            # the search can hold a labelling twice with its mass split (include/slu_decode.h, "held twice"): fold the parts
+            # here, in rank order and in float64, then order again; a labelling held once keeps its score's bits
+            mass = {}
+            for k in range(int(out[o_n + b])):
+                at = (b * beam + k) * L
+                lab = tuple(int(v) for v in out[at:at + int(out[o_len + b * beam + k])])
+                mass.setdefault(lab, []).append(out[o_sc + b * beam + k])
+            hyps = [(list(lab), _fold_log_mass(v)) for lab, v in mass.items()]
+            hyps.sort(key=lambda h: -h[1] if h[1] == h[1] else float("inf"))             # stable; a NaN score goes last
+            res.append(hyps[:nbest])
+        return res
+
+    def decode_phonemes(self, x, lengths, beam=None, topk=None, nbest=1):
+        """CTC decoding of the phoneme head (a CTC model in eval mode): x (B, T) waveforms, lengths their sample counts.
+        beam=None: greedy -> one list of phoneme indices per utterance (per frame the first arg-max, repeats collapsed,
+        blanks dropped: slu_ctc_greedy_errors).  beam=W (1 .. 16): prefix beam search (include/slu_decode.h) -> per
+        utterance a list of at most nbest <= W pairs (labels, score) with distinct labels, best first, score = log
+        p(labelling | x) summed over the paths the search kept (a labelling the search holds twice is folded here); topk
+        (1 .. 32, default 32) labels per frame may extend a prefix; a labelling grows to at most 255 labels, which binds
+        only on utterances of more than 255 frames.  Row b's result is that of x[b:b+1, :lengths[b]] decoded alone."""
+        return self._decode(x, lengths, "decode_phonemes", False, beam, topk, nbest)
+
+    def decode_words(self, x, lengths, beam=None, topk=None, nbest=1):
+        """decode_phonemes on the word head (its frames are word_downsample_factor samples long)."""
+        return self._decode(x, lengths, "decode_words", True, beam, topk, nbest)
 
     def _align(self, x, lengths, y, name, word, want_pos):
         """The body of align_phonemes / align_words: the length-aware stages, the pack and the Linear of decode_phonemes

@@ -23,7 +23,7 @@ class SluHipError(RuntimeError):
     pass
 
 
-def _ctype(ctype, func, returned=False):
+def _ctype(ctype, func, returned=False, header="slu_hip.h"):
     """The one mapping rule, by C type: any parameter with a `*` is c_void_p (device pointers, host arrays, out-parameters,
     hipStream_t as void*), a returned const char* is c_char_p, every scalar comes from _SCALARS.  Nothing has a default."""
     words = " ".join(w for w in ctype.replace("*", " * ").split() if w != "const")
@@ -32,18 +32,20 @@ def _ctype(ctype, func, returned=False):
     if "*" in words and not returned:
         return ctypes.c_void_p
     if words not in _SCALARS:
-        raise SluHipError("slu_hip.h: %s: no ctypes mapping for the %s type '%s'"
-                          % (func, "return" if returned else "parameter", " ".join(ctype.split())))
+        raise SluHipError("%s: %s: no ctypes mapping for the %s type '%s'"
+                          % (header, func, "return" if returned else "parameter", " ".join(ctype.split())))
     return _SCALARS[words]
 
 
-def parse_header(text):
+def parse_header(text, version_macro="SLU_ABI_VERSION", header="slu_hip.h"):
     """Header text -> ({name: (restype, [argtypes])}, SLU_ABI_VERSION).  Every statement of the header that is not a typedef
-    must be a `RET slu_name(TYPE name, ...);` declaration; anything this cannot read raises SluHipError."""
+    must be a `RET slu_name(TYPE name, ...);` declaration; anything this cannot read raises SluHipError.  version_macro:
+    the name of the header's version #define, header: the file name the errors carry (include/slu_decode.h has its own
+    of both, slu_hip/decode.py)."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
-    version = re.search(r"^[ \t]*#[ \t]*define[ \t]+SLU_ABI_VERSION[ \t]+(\d+)[ \t]*$", text, flags=re.M)
+    version = re.search(r"^[ \t]*#[ \t]*define[ \t]+%s[ \t]+(\d+)[ \t]*$" % re.escape(version_macro), text, flags=re.M)
     if not version:
-        raise SluHipError("slu_hip.h: no #define SLU_ABI_VERSION")
+        raise SluHipError("%s: no #define %s" % (header, version_macro))
     text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
     text = re.sub(r"\btypedef\s+(?:enum|struct)\b[^{};]*\{[^{}]*\}[^{};]*;", "", text)
     text = re.sub(r'\bextern\s+"C"\s*\{|\}\s*\Z', "", text)
@@ -51,17 +53,17 @@ def parse_header(text):
     for stmt in filter(None, (s.strip() for s in text.split(";"))):
         m = re.fullmatch(r"([\w\s*]+?)\b(slu_\w+)\s*\((.*)\)", stmt, flags=re.S)
         if not m:
-            raise SluHipError("slu_hip.h: not a function declaration: '%s'" % " ".join(stmt.split()))
+            raise SluHipError("%s: not a function declaration: '%s'" % (header, " ".join(stmt.split())))
         ret, func, params = m.groups()
         if func in table:
-            raise SluHipError("slu_hip.h: %s is declared twice" % func)
+            raise SluHipError("%s: %s is declared twice" % (header, func))
         args = []
         for param in ([] if params.strip() == "void" else params.split(",")):
             p = re.fullmatch(r"\s*(\w[\w\s*]*[\s*])(\w+)\s*", param)
             if not p:                  # function pointers and arrays have ( ) [ ]; an unnamed one has no trailing identifier
-                raise SluHipError("slu_hip.h: %s: parameter '%s' is not `TYPE name`" % (func, " ".join(param.split())))
-            args.append(_ctype(p.group(1), func))
-        table[func] = (_ctype(ret, func, returned=True), args)
+                raise SluHipError("%s: %s: parameter '%s' is not `TYPE name`" % (header, func, " ".join(param.split())))
+            args.append(_ctype(p.group(1), func, header=header))
+        table[func] = (_ctype(ret, func, returned=True, header=header), args)
     return table, int(version.group(1))
 
 
