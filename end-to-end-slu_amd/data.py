@@ -571,6 +571,20 @@ def intent_lexicon(dataset):
     return sorted(strings)
 
 
+def intent_set(dataset):
+    """The sorted unique slot-index tuples of a fixed-slot SLU dataset: the closed set its targets come from (31 of the
+    6 x 14 x 4 combinations on Fluent Speech Commands), what Model.set_intent_set takes.  A real dataset's tuples are its
+    dataframe's (action, object, location) rows through Sy_intent (a value Sy_intent does not know raises KeyError, as
+    __getitem__ does); a synthetic dataset's are read off its targets."""
+    if getattr(dataset, "seq2seq", False):
+        raise ValueError("intent_set: the dataset has seq2seq targets, not slots (see intent_lexicon)")
+    if hasattr(dataset, "_values"):
+        S = dataset.Sy_intent
+        return sorted({tuple(int(S[slot][v]) for slot, v in zip(("action", "object", "location"), row))
+                       for row in set(dataset._values)})
+    return sorted({tuple(int(v) for v in row) for _, y in dataset.batches for row in y.tolist()})
+
+
 def read_textgrid(path):
     """Interval tiers of a Praat TextGrid (the long "ooTextFile" format the Montreal Forced Aligner writes
     for LibriSpeech): {tier name: [(minTime, maxTime, mark), ...]}; the first tier of a name wins, like

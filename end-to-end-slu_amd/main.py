@@ -2,9 +2,14 @@
 
     python main.py [--pretrain] [--train] [--restart] --config_path=experiments/<name>.cfg
 
-and one flag of the project's own, for a tree that has transcripts but no forced alignments:
+and two flags of the project's own: one for a tree that has transcripts but no forced alignments,
 
     SLU_ASR_CTC=1 ... python main.py --align --config_path=...   # TextGrids from the CTC pre-training checkpoint
+
+and one that decodes the fixed-slot head over the closed set of the training split's intents after the last epoch
+(Trainer.test_intent_set: free and constrained accuracy, free predictions that are no intent, posteriors):
+
+    python main.py --train --intent_set --config_path=...
 
 Data parallel over the GPUs of one node: launch one process per GPU, e.g.
 
@@ -16,7 +21,7 @@ import argparse
 import numpy as np
 import torch
 
-from data import get_ASR_datasets, get_SLU_datasets, intent_lexicon, read_config
+from data import get_ASR_datasets, get_SLU_datasets, intent_lexicon, intent_set, read_config
 from models import PretrainedModel, Model, beam_lexicon_enabled, set_dropout_seed
 from slu_hip import dp
 from training import Trainer
@@ -119,6 +124,8 @@ def run(args):
         model = Model(config=config)
         if beam_lexicon_enabled() and config.seq2seq:    # SLU_BEAM_LEXICON=1: decode only the training split's semantics
             model.set_lexicon(intent_lexicon(train_dataset))
+        if args.intent_set:                              # --intent_set: the training split's slot tuples are the closed set
+            model.set_intent_set(intent_set(train_dataset))
         trainer = Trainer(model=model, config=config)
         if args.restart:
             trainer.load_checkpoint()
@@ -136,15 +143,23 @@ def run(args):
         say("========= Test results =========")
         say("*intents*| test accuracy: %.2f| test loss: %.2f| valid accuracy: %.2f| valid loss: %.2f\n"
             % (test_acc, test_loss, valid_acc, valid_loss))
+        if args.intent_set:
+            trainer.test_intent_set(test_dataset)
         trainer.close()
 
 
-if __name__ == "__main__":
+def make_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("--pretrain", action="store_true", help="run ASR pre-training")
     parser.add_argument("--train", action="store_true", help="run SLU training")
     parser.add_argument("--align", action="store_true",
                         help="write forced alignments (TextGrids) from the CTC pre-training checkpoint")
+    parser.add_argument("--intent_set", action="store_true",
+                        help="with --train: decode the fixed-slot head over the training split's intents after the last epoch")
     parser.add_argument("--restart", action="store_true", help="load checkpoint from a previous run")
     parser.add_argument("--config_path", type=str, help="path to config file with hyperparameters, etc.")
-    run(parser.parse_args())
+    return parser
+
+
+if __name__ == "__main__":
+    run(make_parser().parse_args())

@@ -36,6 +36,7 @@ from slu_hip import lib as _lib
 from slu_hip import knobs as _knobs
 from slu_hip import lexicon as _lexicon
 from slu_hip import decode as _decode
+from slu_hip import intents as _intents
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2214,6 +2215,7 @@ class Model(torch.nn.Module):
             _ops.tempo_enabled()                  # likewise a bad SLU_AUGMENT_TEMPO
         self.seq2seq = config.seq2seq
         self.lexicon = None                       # set_lexicon: not a parameter, not a buffer, not in state_dict
+        self.intent_set = None                    # set_intent_set: likewise
         out_dim = config.word_rnn_num_hidden[-1] * (2 if config.word_rnn_bidirectional else 1)
         if self.seq2seq:
             # character-level decoder instead of the fixed slots (reference models.py:718-725)
@@ -2456,14 +2458,20 @@ class Model(torch.nn.Module):
                 out.append((la[0], la[1]))
         return out
 
-    def predict_intents(self, x, lengths=None):
+    def predict_intents(self, x, lengths=None, *, constrained=False):
         """-> (intent_logits (B, num_values_total), predicted_intent (B, num_slots)) (models.py:830-846); a seq2seq model:
         (scores (4, B), beam (4, B, U, |Sy|) one-hot) of the beam search, width 4 (models.py:848-851).
         lengths (not in the reference; None: the call as it was): the utterances' sample counts, each in [1, T] ->
         padding-invariant inference: row b's logits are those of x[b:b+1, :lengths[b]] run alone (eval mode, fixed-slot
         models, GRU hidden sizes 16 / 32 / 64 / 128; exact fp32 kernels whatever SLU_FROZEN_MATH says).  A seq2seq model
         (SLU_MASK_SEQ2SEQ=1): the beam search on the lengths — utterance b's hypotheses and scores are those of
-        x[b:b+1, :lengths[b]] searched alone."""
+        x[b:b+1, :lengths[b]] searched alone.
+        constrained (False: the call as it was, whether or not a set is stored): predicted_intent[b] is the tuple of the
+        stored intent set's best entry (set_intent_set; intent_set_scores' `best`), so it is always an intent that occurs."""
+        if constrained:
+            self._need_intent_set("predict_intents(constrained=True)")
+            res = self.intent_set_scores(x, lengths, n=1)
+            return res.logits, self.intent_set.table(res.logits.device)[res.best.long()].long()
         if self.seq2seq:
             self._beam_eos()             # a bad knob or a missing lexicon is an error before any launch
         h, n_host, n_dev = self._encode(x, lengths)
@@ -2471,12 +2479,80 @@ class Model(torch.nn.Module):
         if self.seq2seq:
             scores, _, beam = self._search(h, n_host, want_beam=True)
             return scores, beam
+        return self._head(h, n_dev)
+
+    def _head(self, h, n_dev):
+        """The fixed-slot head over h (time-major, contiguous; n_dev: its valid frames on the device, or None) -> (logits
+        (B, num_values_total), pred (B, num_slots)): the launch of predict_intents."""
         cls, slots = self.intent_layers[-2], tuple(self.values_per_slot)
         if n_dev is None:
             _, logits, pred, _, _ = _ops.cls_maxpool_ce_fwd(h.detach(), cls.weight.detach(), cls.bias.detach(), None, slots, False)
         else:
             _, logits, pred, _ = _ops.cls_maxpool_len_fwd(h, cls.weight.detach(), cls.bias.detach(), n_dev, None, slots)
         return logits, pred
+
+    # -- closed-set decoding of the fixed-slot head (slu_hip/intents.py; DESIGN.md section 7) ------
+    def set_intent_set(self, tuples):
+        """Stores the closed set of intents the fixed-slot head may be decoded over: an iterable of tuples of slot-value
+        indices (data.intent_set(train_dataset)), a slu_hip.intents.IntentSet, or None to drop it.  Not part of state_dict:
+        checkpoints are unchanged.  Nothing else changes until a caller asks (predict_intents(constrained=True),
+        intent_set_scores, intent_set_posteriors, predict_nbest)."""
+        if self.seq2seq:
+            raise ValueError("set_intent_set: the set constrains the fixed-slot head; a seq2seq model takes a lexicon "
+                             "(set_lexicon)")
+        if tuples is None:
+            self.intent_set = None
+            return
+        if not isinstance(tuples, _intents.IntentSet):
+            tuples = _intents.IntentSet(tuples, self.values_per_slot)
+        elif tuples.sizes != tuple(self.values_per_slot):
+            raise ValueError("intent set: the set was built for slot sizes %r, the head has %r"
+                             % (tuples.sizes, tuple(self.values_per_slot)))
+        self.intent_set = tuples
+
+    def _need_intent_set(self, who):
+        if self.seq2seq:
+            raise ValueError("%s: the intent set belongs to the fixed-slot head; a seq2seq model takes a lexicon" % who)
+        if self.intent_set is None:
+            raise ValueError("%s: no intent set, call Model.set_intent_set(tuples) first" % who)
+
+    def intent_set_tuples(self):
+        """The stored set's entries in the order of intent_set_scores' columns."""
+        self._need_intent_set("intent_set_tuples")
+        return list(self.intent_set.tuples)
+
+    def intent_set_scores(self, x, lengths=None, n=1):
+        """Fixed-slot, with a stored intent set: exact decoding over the closed set -> IntentSetScores, on the device:
+        entry_logp (B, M) float32, log p(entry | x) of every entry under the head's per-slot softmaxes, columns in
+        intent_set_tuples() order; log_z (B), the logsumexp over the entries; best (B) int32 = top_idx[:, 0]; top_idx /
+        top_logp (B, n), the n best, best first; free_idx (B) int32, the column of the free per-slot arg-max, -1 when that
+        is no entry; logits and pred, what predict_intents(x, lengths) returns.  The encoder path is predict_intents'
+        (lengths: padding-invariant in the same way); the scoring is one more launch behind the head with no host read
+        between them (include/slu_intents.h)."""
+        self._need_intent_set("intent_set_scores")
+        _intents.n_checked(n)
+        h, _, n_dev = self._encode(x, lengths)
+        logits, pred = self._head(h.contiguous(), n_dev)
+        entry_logp, log_z, top_idx, top_logp, free_idx = _intents.intent_set_scores(
+            logits, tuple(self.values_per_slot), self.intent_set, n)
+        return IntentSetScores(entry_logp, log_z, top_idx[:, 0], top_idx, top_logp, free_idx, logits, pred)
+
+    def intent_set_posteriors(self, x, lengths=None):
+        """-> (B, M) float32 on the device: p(entry | x, the intent is in the set) = exp(entry_logp - log_z) of
+        intent_set_scores, the number to threshold when an utterance may be none of the entries' business."""
+        res = self.intent_set_scores(x, lengths)
+        return torch.exp(res.entry_logp - res.log_z.unsqueeze(1))
+
+    def predict_nbest(self, x, n=4, lengths=None):
+        """Fixed-slot, with a stored intent set: -> list (batch) of min(n, M) pairs (tuple, log p(tuple | x) - log_z), best
+        first: the n best entries with their log-posterior over the set (top_logp - log_z, in float32 on the device).
+        Indices and scores cross to the host in one copy."""
+        self._need_intent_set("predict_nbest")
+        res = self.intent_set_scores(x, lengths, n=n)
+        # float64 holds both exactly
+        packed = torch.cat([res.top_idx.double(), (res.top_logp - res.log_z.unsqueeze(1)).double()], dim=1).cpu().tolist()
+        entries, k = self.intent_set.tuples, min(n, len(self.intent_set))
+        return [[(entries[int(row[j])], row[n + j]) for j in range(k)] for row in packed]
 
     def set_lexicon(self, strings):
         """Stores the closed set of strings the seq2seq search may return under SLU_BEAM_LEXICON=1: an iterable of
@@ -2659,6 +2735,10 @@ class Model(torch.nn.Module):
             return [_labels_to_string(row, self.Sy_intent) for row in labels[0].cpu().tolist()]
         beam = beam.cpu()
         return [self.one_hot_to_string(beam[0, i], self.Sy_intent) for i in range(beam.shape[1])]
+
+
+# what Model.intent_set_scores returns, every field on the device
+IntentSetScores = collections.namedtuple("IntentSetScores", "entry_logp log_z best top_idx top_logp free_idx logits pred")
 
 
 def _labels_to_string(labels, S):

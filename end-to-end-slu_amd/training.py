@@ -975,3 +975,39 @@ class Trainer:
         intent_loss, intent_acc = self._run(dataset, False, 0)
         self.log({"intent_loss": intent_loss, "intent_acc": intent_acc, "set": "valid"})
         return intent_acc, intent_loss
+
+    def test_intent_set(self, dataset):
+        """Closed-set decoding of the fixed-slot head over one pass of `dataset`'s loader (main.py --intent_set; the model
+        holds a set, Model.set_intent_set), with the lengths where the loader yields them -> a dict, also printed:
+          free_acc          utterances whose per-slot arg-max equals the target in every slot (what test() calls accuracy)
+          constrained_acc   utterances whose best entry of the set equals the target
+          outside           the share of free predictions that are no entry of the set
+          posterior_right / posterior_wrong
+                            the mean posterior of the best entry, exp(top_logp - log_z), over the utterances where it is
+                            right / wrong (nan where there is none)
+        The sums stay on the device; one read at the end."""
+        model = self.model
+        model._need_intent_set("test_intent_set")
+        model.eval()
+        dev = next(model.parameters()).device
+        table = model.intent_set.table(dev)
+        sums = torch.zeros(6, dtype=torch.float64, device=dev)     # n, free right, best right, outside, posterior right / wrong
+        with torch.no_grad():
+            for batch in dataset.loader:
+                x, y = batch[0], batch[1].to(dev)
+                res = model.intent_set_scores(x, batch[2] if len(batch) == 3 else None, n=1)
+                right = (table[res.best.long()].long() == y).all(dim=1)
+                post = torch.exp(res.top_logp[:, 0] - res.log_z).double()
+                sums += torch.stack([right.new_tensor(len(y), dtype=torch.float64), (res.pred == y).all(dim=1).sum().double(),
+                                     right.sum().double(), (res.free_idx < 0).sum().double(),
+                                     torch.where(right, post, torch.zeros_like(post)).sum(),
+                                     torch.where(right, torch.zeros_like(post), post).sum()])
+        n, free, best, outside, p_right, p_wrong = sums.tolist()
+        div = lambda a, b: a / b if b else float("nan")
+        out = {"free_acc": div(free, n), "constrained_acc": div(best, n), "outside": div(outside, n),
+               "posterior_right": div(p_right, best), "posterior_wrong": div(p_wrong, n - best), "entries": len(model.intent_set)}
+        self._say("*intent set* %d entries| free accuracy: %.4f| constrained accuracy: %.4f| free predictions outside the set: "
+                  "%.4f| mean posterior of the best entry, right: %.4f| wrong: %.4f"
+                  % (out["entries"], out["free_acc"], out["constrained_acc"], out["outside"], out["posterior_right"],
+                     out["posterior_wrong"]))
+        return out
