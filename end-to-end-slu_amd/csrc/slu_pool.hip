@@ -271,7 +271,10 @@ dropout_pool_bwd4_kernel(const float* __restrict__ dy, const float* __restrict__
 
 // ---- MaxPool1d(k, ceil_mode) + [Abs before it] + LeakyReLU / ReLU after it, for pool widths the convolution's
 // epilogue does not fuse (k > 2; reference models.py:163-168, :205, :211-213 allow any cnn_max_pool_len).  x channels-last
-// (B, L, C); y[b, lo, c] at b * out_sb + lo * out_sl + c; route (B, L_out, C) = arg-max offset | sign bit (abs) << 7.
+// (B, L, C); y[b, lo, c] at b * out_sb + lo * out_sl + c; route (B, L_out, C) = offset of the first maximum | (picked element
+// not positive before abs) << 7.  Under abs y >= 0 and y == 0 exactly when the picked element is +-0, so the backward reads
+// sign(picked) off (bit 7, y): clear -> +1, set and y > 0 -> -1, set and y == 0 -> 0 (torch: d|x|/dx = 0 at +-0).  Without
+// abs bit 7 is never set and LeakyReLU's derivative at 0 is the slope.
 __global__ void __launch_bounds__(256)
 pool_act_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, unsigned char* __restrict__ route, int B, int L,
                     int C, int L_out, int pool, int do_abs, float slope, long long out_sb, long long out_sl) {
@@ -286,7 +289,7 @@ pool_act_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, unsigned
   for (int l = l0; l < l1; ++l) {
     const float v = x[((size_t)b * L + l) * C + c];
     const float u = do_abs ? fabsf(v) : v;
-    if (u > best) { best = u; arg = l - l0; neg = (do_abs && v < 0.0f) ? 1 : 0; }
+    if (u > best) { best = u; arg = l - l0; neg = (do_abs && !(v > 0.0f)) ? 1 : 0; }
   }
   y[(size_t)b * out_sb + (size_t)lo * out_sl + c] = best > 0.0f ? best : best * slope;
   if (route) route[e] = (unsigned char)(arg | (neg << 7));
@@ -304,8 +307,9 @@ pool_act_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y, c
   const int l0 = lo * pool, l1 = min(L, l0 + pool);
   const size_t o = (size_t)b * out_sb + (size_t)lo * out_sl + c;
   const unsigned char r = route[e];
-  float g = dy[o] * (y[o] > 0.0f ? 1.0f : slope);
-  if (r & 0x80) g = -g;
+  const float yv = y[o];
+  float g = dy[o] * (yv > 0.0f ? 1.0f : slope);
+  if (r & 0x80) g = yv > 0.0f ? -g : 0.0f;
   const int arg = r & 0x7f;
   for (int l = l0; l < l1; ++l) dx[((size_t)b * L + l) * C + c] = (l - l0 == arg) ? g : 0.0f;
 }

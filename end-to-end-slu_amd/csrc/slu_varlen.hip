@@ -340,7 +340,7 @@ dropout_pool_len_bwd4_kernel(const float* __restrict__ dy, const float* __restri
 // ---- [abs ->] MaxPool1d(pool, ceil_mode) over the valid frames -> LeakyReLU(slope), zero beyond, and its backward ------
 // The forward is pool_act_fwd_kernel (slu_pool.hip) with the window clipped to n_b instead of L.  With ROUTE (a trainable
 // CNN block under masked training) it also records, per output, that kernel's route byte: arg-max offset inside the
-// window | negative-before-abs << 7, 0 at a padded output; without, it takes no route pointer, keeps no route bookkeeping
+// window | not-positive-before-abs << 7 (with y == 0 that is a picked +-0, whose gradient under abs is 0), 0 at a padded output; without, it takes no route pointer, keeps no route bookkeeping
 // and stores the same y.  The backward is pool_act_bwd_kernel with every window clipped to n_b: dx is exactly 0 at
 // l >= n_b (selected, never a product), dy / y are not read at lo >= ceil(n_b / pool), and the activation's derivative is
 // that kernel's (y > 0 ? 1 : slope).  x / dx channels-last (B, L, C); y / dy at b * out_sb + lo * out_sl + c.
@@ -360,7 +360,7 @@ __device__ __forceinline__ void route_take(float v, int do_abs, int off, float& 
   const float u = do_abs ? fabsf(v) : v;
   if (u > best) {                                                                           // first maximum wins
     best = u;
-    if constexpr (ROUTE) r = (unsigned)off | ((do_abs && v < 0.0f) ? 0x80u : 0u);
+    if constexpr (ROUTE) r = (unsigned)off | ((do_abs && !(v > 0.0f)) ? 0x80u : 0u);
   }
 }
 
@@ -387,6 +387,12 @@ pool_act_len_fwd_route_kernel(const float* __restrict__ x, float* __restrict__ y
   if constexpr (ROUTE) route.bytes[e] = (unsigned char)r;
 }
 
+// bit 7 set: the picked element was not positive before abs — negative where y > 0, +-0 where y == 0 (gradient 0)
+__device__ __forceinline__ float route_grad(float dy, float y, unsigned r, float slope) {
+  const float g = dy * (y > 0.0f ? 1.0f : slope);
+  return (r & 0x80u) ? (y > 0.0f ? -g : 0.0f) : g;
+}
+
 // scalar path: one thread per input element
 __global__ void __launch_bounds__(256)
 pool_act_len_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y, const unsigned char* __restrict__ route,
@@ -403,8 +409,7 @@ pool_act_len_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ 
     const unsigned char r = route[((size_t)b * q.L_out + lo) * q.C + c];
     if (l - lo * q.pool == (r & 0x7f)) {
       const size_t o = (size_t)b * q.out_sb + (size_t)lo * q.out_sl + c;
-      const float g = dy[o] * (y[o] > 0.0f ? 1.0f : q.slope);
-      out = (r & 0x80) ? -g : g;
+      out = route_grad(dy[o], y[o], r, q.slope);
     }
   }
   dx[e] = out;
@@ -441,11 +446,6 @@ pool_act_len_fwd_route4_kernel(const float* __restrict__ x, float* __restrict__ 
   }
   *reinterpret_cast<float4*>(y + (size_t)b * q.out_sb + (size_t)lo * q.out_sl + c) = out;
   if constexpr (ROUTE) *reinterpret_cast<unsigned*>(route.bytes + (size_t)bl * q.C + c) = rx | (ry << 8) | (rz << 16) | (rw << 24);
-}
-
-__device__ __forceinline__ float route_grad(float dy, float y, unsigned r, float slope) {
-  const float g = dy * (y > 0.0f ? 1.0f : slope);
-  return (r & 0x80u) ? -g : g;
 }
 
 __global__ void __launch_bounds__(256)

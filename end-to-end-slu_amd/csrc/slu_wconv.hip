@@ -208,7 +208,11 @@ wconv_bwd_act_kernel(const float* __restrict__ dy, const float* __restrict__ y,
   const float yv = y[src];
   float g = dy[src] * (yv > 0.0f ? 1.0f : slope);
   const uint8_t rt = route ? route[idx] : 0;
-  if (do_abs && (rt & 2)) g = -g;
+  if (do_abs) {
+    // under |.| the pooled value is >= 0 and y == 0 exactly when the picked |t| is 0: d|t|/dt = sign(t), sign(+-0) = 0
+    if (yv == 0.0f) g = 0.0f;
+    else if (rt & 2) g = -g;
+  }
   if (pool == 2) {
     const int f0 = 2 * lo;
     const size_t d0 = ((size_t)b * l_conv + f0) * c_out + c;

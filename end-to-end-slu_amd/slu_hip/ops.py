@@ -218,6 +218,8 @@ def wconv_fwd(x, weight, bias, B, l_in, c_in, stride, do_abs, pool, slope, time_
 
 
 def wconv_bwd_act(dy, y, route, B, l_conv, c_out, do_abs, pool, slope, time_major):
+    """-> d_conv (B, l_conv, c_out) by ATen's conventions (include/slu_hip.h): the first maximum of a pool window takes
+    the gradient, LeakyReLU has the negative slope at 0, and under |.| a pre-activation of +-0 takes 0 (sign(+-0) = 0)."""
     L = _lib.load()
     dy = _f32c(dy, "dy")
     l_out = -(-l_conv // pool)
@@ -374,7 +376,8 @@ def scale_multi(tensors, scale_dev):
 class PoolActFn(torch.autograd.Function):
     """[Abs ->] MaxPool1d(pool, ceil) -> LeakyReLU / ReLU for pool widths the convolution epilogue does not fuse
     (cnn_max_pool_len > 2; reference models.py:163-168, :205, :211-213).  x channels-last (B, L, C) ->
-    (B, L_out, C), or time-major (L_out, B, C)."""
+    (B, L_out, C), or time-major (L_out, B, C).  Backward by ATen's conventions: the first maximum of a window takes the
+    gradient, sign(+-0) = 0 under |.|, LeakyReLU has the negative slope at 0."""
 
     @staticmethod
     def forward(ctx, x, pool, do_abs, slope, time_major):
@@ -1312,6 +1315,7 @@ def _dropout_pool_bwd(dy, x, mask, p, seed, offset, method, factor, offset_dev=N
 
 
 def dropout_pool_bwd(dy, x, mask, p, seed, offset, method, factor, offset_dev=None):
+    """method 'max': the first maximum of a window of x * keep takes dy * keep (ATen's max_pool1d), dropped zeros included."""
     return _dropout_pool_bwd(dy, x, mask, p, seed, offset, method, factor, offset_dev)
 
 
@@ -1457,7 +1461,8 @@ def pool_act_len_fwd_route(x, lengths, pool, do_abs, slope, time_major):
 
 def pool_act_len_bwd(dy, y, route, lengths, Lin, pool, slope, time_major):
     """dy / y as pool_act_len_fwd_route returned y, lengths = valid frames of the pooled tensor's input -> dx (B, Lin, C):
-    exactly zero at l >= lengths[b] whatever dy and y hold beyond the valid outputs (they are not read there)."""
+    exactly zero at l >= lengths[b] whatever dy and y hold beyond the valid outputs (they are not read there).  PoolActFn's
+    conventions on each clipped window: first maximum, sign(+-0) = 0 under |.|, the negative slope at 0."""
     L = _lib.load()
     B, l_out, C = route.shape
     _len_ok(lengths, B)

@@ -19,7 +19,14 @@
  *   - sizes are int64_t, strides are in ELEMENTS;
  *   - activation layouts: waveform (B,T); CNN activations channels-last (B,L,C) or, through the
  *     output strides, time-major (L,B,C); RNN activations TIME-MAJOR (T,B,C).  The host mirror
- *     presents them to callers in the reference's (B,C,L)/(B,T,C) shapes as strided views.
+ *     presents them to callers in the reference's (B,C,L)/(B,T,C) shapes as strided views;
+ *   - gradients at ties, exact zeros and kinks follow ATen's CPU kernels (tests/test_hip_kinks.py):
+ *       the FIRST maximum wins — of a max-pool window (conv epilogue, slu_pool_act_*, the `max`
+ *       Downsample of slu_dropout_pool_*), of FinalPool's max over time, of a slot's or a frame's
+ *       top logit;
+ *       sign(+0.0) = sign(-0.0) = 0 under |.|: a pre-activation of +-0 in front of Abs, and a SincNet
+ *       cut-off filt_b1 / filt_band of +-0, receive the gradient 0;
+ *       LeakyReLU takes the negative slope at 0 (y > 0 ? 1 : slope).
  */
 #ifndef SLU_HIP_H
 #define SLU_HIP_H
@@ -471,8 +478,10 @@ int slu_dropout_pool_bwd(const float* dy, const float* x, const float* y, const 
 /* [Abs ->] MaxPool1d(pool, ceil_mode=True) -> LeakyReLU(slope) / ReLU (slope 0) for pool widths the convolution's
  * epilogue does not fuse (any cnn_max_pool_len > 2: models.py:163-168, :205, :211-213).  x channels-last (B, L, C);
  * y[b, lo, c] at b * out_sb + lo * out_sl + c (channels-last or time-major); route (B, ceil(L / pool), C) bytes =
- * arg-max offset inside the window | (input was negative, abs) << 7, NULL when no backward follows; pool <= 127.
- * Backward: dx (B, L, C) fully written (zeros off the arg-max).                                                    */
+ * offset of the first maximum inside the window | (the picked input was not positive, abs) << 7, NULL when no backward
+ * follows; pool <= 127.  Under abs y == 0 exactly when the picked input is +-0, so (bit 7, y) give its sign: clear +1,
+ * set and y > 0: -1, set and y == 0: 0.  Backward: dx (B, L, C) fully written (zeros off the arg-max and at a picked +-0
+ * under abs).                                                                                                      */
 int slu_pool_act_fwd(const float* x, float* y, uint8_t* route, int64_t B, int64_t L, int64_t C, int64_t pool,
                      int do_abs, float slope, int64_t out_sb, int64_t out_sl, void* stream);
 int slu_pool_act_bwd(const float* dy, const float* y, const uint8_t* route, float* dx, int64_t B, int64_t L,
@@ -802,7 +811,7 @@ int slu_cls_maxpool_len_ce_fwd(const float* h, const float* weight, const float*
  *                     valid frames reaches nothing — they are not read there); at a valid frame the gradient of
  *                     [abs ->] max over the clipped window [lo * pool, min(n_b, lo * pool + pool)) -> LeakyReLU(slope): the
  *                     first maximum of the window takes dy * (y > 0 ? 1 : slope) (slu_pool_act_bwd's convention), negated
- *                     where abs flipped the sign; every other frame of the window takes 0;
+ *                     where abs flipped the sign and 0 where abs met +-0; every other frame of the window takes 0;
  *   dW, db, d filt_b1 / d filt_band   slu_wconv_bwd_weight (+ slu_sinc_filters_bwd) on this d_conv and the saved
  *                     zero-tailed input: the sum over the rows of what each row truncated to m_b gives alone (the zero tail
  *                     is the truncated row's "same" padding);
@@ -814,7 +823,7 @@ int slu_cls_maxpool_len_ce_fwd(const float* h, const float* weight, const float*
  * or per four channels where C % 4 == 0 and the buffers are 16-byte aligned.  NULL lengths or pointers, pool outside
  * [1, 127]: SLU_ERR_INVALID_ARG.
  *   slu_pool_act_len_fwd_route   slu_pool_act_len_fwd (the same kernels with the route store compiled in: y bit-equal) that
- *                            also writes the route bytes: arg-max offset inside the window | negative-before-abs << 7; 0 at
+ *                            also writes the route bytes: arg-max offset inside the window | not-positive-before-abs << 7; 0 at
  *                            lo >= ceil(n_b / pool).
  *   slu_pool_act_len_bwd     dx (B, L, C), every element written, by the definition of d_conv above.                    */
 int slu_pool_act_len_fwd_route(const float* x, float* y, uint8_t* route, const int32_t* lengths, int64_t B, int64_t L,
