@@ -1,6 +1,6 @@
 #!/bin/bash
-# Builds libslu_hip.so and, next to it, libslu_decode.so (include/slu_decode.h) and libslu_intents.so
-# (include/slu_intents.h) for gfx950 (MI355X) in-tree.  hipcc cross-compiles without a GPU.
+# Builds libslu_hip.so and, next to it, libslu_decode.so (include/slu_decode.h), libslu_intents.so
+# (include/slu_intents.h) and libslu_resample.so (include/slu_resample.h) for gfx950 (MI355X) in-tree.  hipcc cross-compiles without a GPU.
 # Out-of-date translation units are compiled in parallel (SLU_BUILD_JOBS, default = the host's cores, max 16).
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
@@ -14,11 +14,14 @@ UNITS="slu_api slu_sinc slu_wconv slu_wconv_bf16 slu_gemm slu_gemm_bf16 slu_gru 
 DECODE_UNITS="slu_ctc_beam"
 # libslu_intents.so: its units see include/slu_intents.h as well
 INTENTS_UNITS="slu_intent_set"
+# libslu_resample.so: its units see include/slu_resample.h as well
+RESAMPLE_UNITS="slu_resample"
 OBJS=()
 DECODE_OBJS=()
 INTENTS_OBJS=()
+RESAMPLE_OBJS=()
 STALE=()
-for f in $UNITS $DECODE_UNITS $INTENTS_UNITS; do
+for f in $UNITS $DECODE_UNITS $INTENTS_UNITS $RESAMPLE_UNITS; do
   if [ ! -f "$OUT/$f.o" ] || [ "$HERE/$f.hip" -nt "$OUT/$f.o" ] || [ "$HERE/slu_common.h" -nt "$OUT/$f.o" ] || [ "$HERE/slu_bf16.h" -nt "$OUT/$f.o" ] || [ "$HERE/slu_philox.h" -nt "$OUT/$f.o" ] || [ "$HERE/slu_gemm_tile.h" -nt "$OUT/$f.o" ] || [ "$HERE/slu_reduce.h" -nt "$OUT/$f.o" ] \
      || [ "$HERE/../../include/slu_hip.h" -nt "$OUT/$f.o" ]; then
     STALE+=("$f")
@@ -26,9 +29,12 @@ for f in $UNITS $DECODE_UNITS $INTENTS_UNITS; do
     STALE+=("$f")
   elif [[ " $INTENTS_UNITS " == *" $f "* ]] && [ "$HERE/../../include/slu_intents.h" -nt "$OUT/$f.o" ]; then
     STALE+=("$f")
+  elif [[ " $RESAMPLE_UNITS " == *" $f "* ]] && [ "$HERE/../../include/slu_resample.h" -nt "$OUT/$f.o" ]; then
+    STALE+=("$f")
   fi
   if [[ " $DECODE_UNITS " == *" $f "* ]]; then DECODE_OBJS+=("$OUT/$f.o")
   elif [[ " $INTENTS_UNITS " == *" $f "* ]]; then INTENTS_OBJS+=("$OUT/$f.o")
+  elif [[ " $RESAMPLE_UNITS " == *" $f "* ]]; then RESAMPLE_OBJS+=("$OUT/$f.o")
   else OBJS+=("$OUT/$f.o"); fi
 done
 if [ "${#STALE[@]}" -gt 0 ]; then
@@ -43,3 +49,6 @@ echo "[build] $OUT/libslu_decode.so"
 # the closed-set decoder of the fixed-slot head: the same one undefined project symbol, the same link
 "$HIPCC" --offload-arch=gfx950 -shared -fPIC "${INTENTS_OBJS[@]}" -L"$OUT" -lslu_hip -Wl,-rpath,'$ORIGIN' -o "$OUT/libslu_intents.so"
 echo "[build] $OUT/libslu_intents.so"
+# the sample-rate converter: the same one undefined project symbol, the same link
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC "${RESAMPLE_OBJS[@]}" -L"$OUT" -lslu_hip -Wl,-rpath,'$ORIGIN' -o "$OUT/libslu_resample.so"
+echo "[build] $OUT/libslu_resample.so"

@@ -16,6 +16,7 @@ SURVEY.md §8(f) rank 1), feeding pinned, zero-padded (B, T_max) batches to the 
 datasets with the same duck type are served (`.loader` yielding the same batch tuples;
 `training.Trainer` dispatches on `SLUDataset` / `ASRDataset`).
 """
+import collections
 import configparser
 import os
 import shutil
@@ -185,6 +186,44 @@ def pcm16_batches():
     return _knobs.get("SLU_PCM16_BATCHES")
 
 
+def resample_enabled():
+    """SLU_RESAMPLE: "0" (default) — a wav file's sample rate is ignored: every file is taken to be sampled at the model's
+    config.fs, as in the reference; "1" — SLU datasets keep each file's rate, CollateWavsSLU hands the batch over as a
+    SourceWaves and the training loops convert it to config.fs on the device (slu_hip.ops.wave_resample) in front of
+    everything else; the ASR pre-training datasets refuse a file at another rate."""
+    return _knobs.added("SLU_RESAMPLE")
+
+
+RatedWave = collections.namedtuple("RatedWave", "x rate")    # an SLUDataset item's waveform under SLU_RESAMPLE=1
+
+
+class SourceWaves:
+    """The first element of an SLU batch under SLU_RESAMPLE=1: the waveforms as the files hold them.  x (B, T_src) host
+    tensor (float32, or int16 under SLU_PCM16_BATCHES=1), zero-padded at the end in SOURCE samples; lengths (B) int32
+    host tensor, the rows' source sample counts; rates: B ints; target: the rate they are to be converted to; out_T: the
+    width of the converted batch (the largest output length, rounded up to SLU_PAD_TO_MULTIPLE); out_lengths: the B
+    output lengths (ops.resample_out_lengths).  Everything downstream of the conversion needs is known on the host."""
+
+    def __init__(self, x, lengths, rates, target, out_T, out_lengths):
+        self.x, self.lengths, self.rates, self.target = x, lengths, [int(r) for r in rates], int(target)
+        self.out_T, self.out_lengths = int(out_T), [int(n) for n in out_lengths]
+
+    def __len__(self):
+        return self.x.shape[0]
+
+    def pin_memory(self):
+        """What the DataLoader's pinning calls on a batch element it does not know."""
+        return SourceWaves(self.x.pin_memory(), self.lengths.pin_memory(), self.rates, self.target, self.out_T,
+                           self.out_lengths)
+
+
+def _require_rate(path, fs, config_fs, who):
+    if int(fs) != int(config_fs):
+        raise ValueError("resample: %s: %s is sampled at %d Hz, the model at %d Hz; ASR pre-training builds its label "
+                         "tracks from the file's own rate and is not converted (SLU_RESAMPLE=1 covers the SLU datasets)"
+                         % (who, path, int(fs), int(config_fs)))
+
+
 def read_wav(path, keep_pcm16=False):
     """First channel of a wav file as float32 in [-1, 1) and its sample rate — the array
     `SoxEffectsChain.sox_build_flow_effects()` hands the reference (data.py:273-293; augmentation is
@@ -297,7 +336,11 @@ class CollateWavsSLU:
     pins it (pin_memory=True, in the parent process — never in a forked worker) so that the H2D copy of the
     look-ahead slots is asynchronous."""
 
-    def __init__(self, Sy_intent, seq2seq, pad_multiple=None, mask_padding=None):
+    def __init__(self, Sy_intent, seq2seq, pad_multiple=None, mask_padding=None, resample_to=None):
+        # SLU_RESAMPLE=1 (SLUDataset passes config.fs): the items' waveforms are RatedWave(x, rate); x of the batch is a
+        # SourceWaves padded in SOURCE samples, the lengths (SLU_MASK_PADDING=1) are the CONVERTED ones and
+        # SLU_PAD_TO_MULTIPLE rounds the converted width.  None: the batch documented above, whatever the files' rates.
+        self.resample_to = None if resample_to is None else int(resample_to)
         self.Sy_intent = Sy_intent
         self.num_labels = len(self.Sy_intent)
         self.seq2seq = seq2seq
@@ -314,7 +357,25 @@ class CollateWavsSLU:
         # drop them (training.Trainer).  Off: the batch is the reference's 2-tuple.
         self.mask_padding = mask_padding_enabled() if mask_padding is None else bool(mask_padding)
 
+    def _source_waves(self, batch):
+        from slu_hip import resample as _resample
+        waves = [w.x for w, _ in batch]
+        rates = [int(w.rate) for w, _ in batch]
+        lengths = [len(x) for x in waves]
+        n_out = _resample.out_lengths(lengths, rates, self.resample_to)
+        T_out = max(n_out)
+        if self.pad_multiple > 1:
+            T_out = -(-T_out // self.pad_multiple) * self.pad_multiple
+        x = SourceWaves(_pad_waveforms(waves, max(lengths)), torch.tensor(lengths, dtype=torch.int32), rates,
+                        self.resample_to, T_out, n_out)
+        if self.mask_padding:
+            x, y = self._labels(batch, x)
+            return x, y, torch.tensor(n_out, dtype=torch.int32)
+        return self._labels(batch, x)
+
     def __call__(self, batch):
+        if self.resample_to is not None:
+            return self._source_waves(batch)
         T = max(len(x) for x, _ in batch)
         if self.pad_multiple > 1:
             T = -(-T // self.pad_multiple) * self.pad_multiple
@@ -450,7 +511,9 @@ class SLUDataset(torch.utils.data.Dataset):
             self._index = {c: i for i, c in enumerate(self.Sy_intent)}       # label -> index (list.index per char otherwise)
         else:
             self._values = list(zip(df["action"].tolist(), df["object"].tolist(), df["location"].tolist()))
-        collate = CollateWavsSLU(self.Sy_intent, self.seq2seq)
+        # SLU_RESAMPLE=1: the items keep their files' rates; read once, here, so that the workers and the collate agree
+        self.resample_to = int(config.fs) if resample_enabled() else None
+        collate = CollateWavsSLU(self.Sy_intent, self.seq2seq, resample_to=self.resample_to)
         pin = torch.cuda.is_available()
         # Data parallelism (`shard`: the training split only): every rank draws a disjoint 1/world of the
         # epoch (DistributedSampler pads by repetition so that all ranks run the same number of steps);
@@ -458,7 +521,13 @@ class SLUDataset(torch.utils.data.Dataset):
         rank, world = _world() if shard else (0, 1)
         seed = getattr(config, "seed", 0)
         if _knobs.get("SLU_BUCKET_BATCHES") and collate.pad_multiple > 1:
-            lengths = [wav_num_samples(p) for p in self._paths] * self.upsample_factor
+            if self.resample_to is None:
+                lengths = [wav_num_samples(p) for p in self._paths] * self.upsample_factor
+            else:                                # bucket by what the model will see: the converted lengths
+                from slu_hip import resample as _resample
+                frames_rates = [_wav_frames_rate(p) for p in self._paths]
+                lengths = _resample.out_lengths([max(1, n) for n, _ in frames_rates], [fs for _, fs in frames_rates],
+                                                self.resample_to) * self.upsample_factor
             self.loader = ForkSafeDataLoader(
                 self, num_workers=_loader_workers(), collate_fn=collate, pin_memory=pin,
                 batch_sampler=LengthBucketBatchSampler(lengths, config.training_batch_size, collate.pad_multiple,
@@ -480,6 +549,8 @@ class SLUDataset(torch.utils.data.Dataset):
     def __getitem__(self, idx):
         idx = idx % len(self._paths)
         x, _fs = read_wav(self._paths[idx], keep_pcm16=pcm16_batches())
+        if getattr(self, "resample_to", None) is not None:
+            x = RatedWave(x, int(_fs))
         if self.seq2seq:                         # <sos> + the characters of the semantics string + <eos> (data.py:322-326)
             y_intent = [self._index["<sos>"]] + [self._index[c] for c in self._values[idx]] + [self._index["<eos>"]]
             return x, y_intent
@@ -781,6 +852,7 @@ class ASRDataset(torch.utils.data.Dataset):
         self.Sy_word = Sy_word
         self.phone_downsample_factor = config.phone_downsample_factor
         self.word_downsample_factor = config.word_downsample_factor
+        self.require_fs = int(config.fs) if resample_enabled() else None     # SLU_RESAMPLE=1: refuse, do not mistrain
         self._phone_idx, self._word_idx = {}, {}
         for i, v in enumerate(Sy_phoneme):
             self._phone_idx.setdefault(v, i)
@@ -809,6 +881,8 @@ class ASRDataset(torch.utils.data.Dataset):
 
     def __getitem__(self, idx):
         x32, fs = read_wav(self.wav_paths[idx])
+        if getattr(self, "require_fs", None) is not None:
+            _require_rate(self.wav_paths[idx], fs, self.require_fs, "ASRDataset")
         x = x32.astype(np.float64)                     # soundfile.read hands the reference float64
         tg = read_textgrid(self.textgrid_paths[idx])
         y_phoneme = self._track(tg["phones"], lambda m: -1 if m == "" else self._phone_idx.get(_strip_stress(m), -1), fs)
@@ -911,8 +985,11 @@ class TranscriptASRDataset(ASRDataset):
             self._word_idx.setdefault(v, i)
         self.Sy_phoneme, self.Sy_word = Sy_phoneme, Sy_word
         limit, kept, skipped = ctc_max_seconds(), [], 0
+        require_fs = int(config.fs) if resample_enabled() else None          # SLU_RESAMPLE=1: refuse, do not mistrain
         for wav, words in items:
             n, fs = _wav_frames_rate(wav)
+            if require_fs is not None:
+                _require_rate(wav, fs, require_fs, "TranscriptASRDataset")
             wd = [self._word_idx[w] for w in words if w in self._word_idx]
             ph = [self._phone_idx[p] for w in words for p in lexicon.get(w, ()) if p in self._phone_idx]
             if n > limit * fs or n < 1 or max(len(wd), len(ph)) > CTC_MAX_LABELS:

@@ -2189,6 +2189,7 @@ class Model(torch.nn.Module):
         super().__init__()
         self.is_cuda = torch.cuda.is_available()
         self.Sy_intent = config.Sy_intent
+        self.fs = int(getattr(config, "fs", 16000))        # the rate `rates=` converts to (predict_intents, decode_*)
         pretrained_model = PretrainedModel(config)
         if config.pretraining_type != 0:
             path = os.path.join(config.folder, "pretraining", "model_state.pth")
@@ -2298,6 +2299,20 @@ class Model(torch.nn.Module):
             _refuse_seq2seq_lengths()
         run = self.pretrained_model._features_tm_len(x, lengths, self._intent_stages)
         return run.out, run.n_host, run.n_dev
+
+    def _at_model_rate(self, x, lengths, rates):
+        """predict_intents / decode_intents / decode_nbest with rates=: x (B, T) float32 or int16 as the sources hold it,
+        rates an int or B ints, lengths None or the B SOURCE sample counts -> (x converted to config.fs on the device by
+        ops.wave_resample, the converted lengths as a list, or None without lengths: the dense call on the zero-padded
+        result).  Every refusal is ops.wave_resample's ValueError("resample: ..."), before any launch."""
+        if not torch.is_tensor(x):
+            raise ValueError("resample: x must be a float32 or int16 (B, T) tensor")
+        host = None
+        if lengths is not None:
+            host = [int(n) for n in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+        dev = next(self.parameters()).device
+        y, _ = _ops.wave_resample(x.to(dev), rates, host, target=self.fs)
+        return y, (None if host is None else _ops.resample_out_lengths(host, rates, self.fs))
 
     def _encode(self, x, lengths=None):
         """What predict_intents, decode_intents and decode_nbest run in front of their head -> (h time-major, host lengths,
@@ -2458,7 +2473,7 @@ class Model(torch.nn.Module):
                 out.append((la[0], la[1]))
         return out
 
-    def predict_intents(self, x, lengths=None, *, constrained=False):
+    def predict_intents(self, x, lengths=None, *, constrained=False, rates=None):
         """-> (intent_logits (B, num_values_total), predicted_intent (B, num_slots)) (models.py:830-846); a seq2seq model:
         (scores (4, B), beam (4, B, U, |Sy|) one-hot) of the beam search, width 4 (models.py:848-851).
         lengths (not in the reference; None: the call as it was): the utterances' sample counts, each in [1, T] ->
@@ -2467,7 +2482,11 @@ class Model(torch.nn.Module):
         (SLU_MASK_SEQ2SEQ=1): the beam search on the lengths — utterance b's hypotheses and scores are those of
         x[b:b+1, :lengths[b]] searched alone.
         constrained (False: the call as it was, whether or not a set is stored): predicted_intent[b] is the tuple of the
-        stored intent set's best entry (set_intent_set; intent_set_scores' `best`), so it is always an intent that occurs."""
+        stored intent set's best entry (set_intent_set; intent_set_scores' `best`), so it is always an intent that occurs.
+        rates (None: the call as it was, bit for bit): the rows' source sample rates, an int or B ints; x and lengths are
+        then in SOURCE samples and are converted to config.fs first (ops.wave_resample; _at_model_rate)."""
+        if rates is not None:
+            x, lengths = self._at_model_rate(x, lengths, rates)
         if constrained:
             self._need_intent_set("predict_intents(constrained=True)")
             res = self.intent_set_scores(x, lengths, n=1)
@@ -2657,7 +2676,7 @@ class Model(torch.nn.Module):
             labels = torch.cat([labels, labels.new_full((n - k,) + tuple(labels.shape[1:]), eos)])
         return scores, labels
 
-    def decode_nbest(self, x, n=4, lengths=None):
+    def decode_nbest(self, x, n=4, lengths=None, rates=None):
         """seq2seq: -> list (batch) of lists of (string, score): the n <= 4 best hypotheses of the width-4 device search
         (Seq2SeqDecoder.search), best first; score = the hypothesis' log-probability as the search ranks it.  With
         SLU_BEAM_EOS=1 a hypothesis is cut at its length before the cleaning decode_intents applies (so entry 0 is
@@ -2666,9 +2685,12 @@ class Model(torch.nn.Module):
         Under SLU_BEAM_LEXICON=1 the dead slots (score -inf: the lexicon had fewer continuations than the beam is wide) are
         dropped, so an utterance's list may have fewer than n items.
         Under SLU_LEXICON_EXACT=1 there is no beam: the min(n, M) best of the lexicon's M entries, each with its exact
-        log p(entry | x) (lexicon_scores), any n >= 1."""
+        log p(entry | x) (lexicon_scores), any n >= 1.
+        rates: as predict_intents."""
         if not self.seq2seq:
             raise ValueError("decode_nbest: the n-best list comes from the seq2seq decoder's beam search")
+        if rates is not None:
+            x, lengths = self._at_model_rate(x, lengths, rates)
         W = 4
         if lexicon_exact_enabled():
             # SLU_LEXICON_EXACT=1: the min(n, M) best entries of the sweep with their log p(entry | x); no beam, no cap
@@ -2718,11 +2740,13 @@ class Model(torch.nn.Module):
         upto = (is_eos.cumsum(dim=1) - is_eos.long()) == 0                            # no <eos> strictly before
         return int(((best[:, :Uy] == y) | ~upto).all(dim=1).sum())
 
-    def decode_intents(self, x, lengths=None):
+    def decode_intents(self, x, lengths=None, rates=None):
         """-> list (batch) of lists (slots) of slot-value strings (reference models.py:853-865).  A seq2seq model: list
         (batch) of the best hypotheses' strings (models.py:866-874) — under SLU_BEAM_SEARCH=device from their labels
         (batch, U): the string one_hot_to_string builds, without the one-hot beam crossing to the host.
-        lengths: as predict_intents (a seq2seq model: SLU_MASK_SEQ2SEQ=1)."""
+        lengths: as predict_intents (a seq2seq model: SLU_MASK_SEQ2SEQ=1).  rates: as predict_intents."""
+        if rates is not None:
+            x, lengths = self._at_model_rate(x, lengths, rates)
         if not self.seq2seq:
             # (the dense call keeps its one-argument form: callers and tests replace predict_intents by a function of x)
             pred = (self.predict_intents(x) if lengths is None else self.predict_intents(x, lengths))[1].cpu()

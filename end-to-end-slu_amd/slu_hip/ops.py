@@ -843,6 +843,31 @@ def tempo_out_lengths(lengths, T, seed, offset, sub_batch=0, sub_stride=16, fixe
     return out
 
 
+# ---- sample-rate conversion in front of everything else (libslu_resample.so; slu_hip/resample.py holds the definition) ----
+def wave_resample(x, rates, lengths=None, target=16000, out_T=None):
+    """Rows of x (B, T_in), fp32 or PCM16 on the device, each from its own source rate to `target`
+    (slu_wave_resample, include/slu_resample.h) -> (y (B, out_T) fp32, zero from each row's n_out on; out_lengths int32
+    (B) on the device).  rates: an int or B ints; lengths: None (full rows) or B host values; out_T defaults to the
+    largest n_out.  Refuses a tensor that requires a gradient; every refusal is a ValueError("resample: ...") before any
+    launch.  The (L, K) banks are computed once per (source rate, target, device) and stay on the device."""
+    from . import resample
+    with torch.no_grad():
+        return resample.wave_resample(x, rates, lengths, target, out_T)
+
+
+def resample_out_lengths(lengths, rates, target=16000):
+    """Host mirror of slu_wave_resample's lengths_out: n_out = (len L + M - 1) // M per row, L = target / gcd,
+    M = rate / gcd (integer arithmetic, no launch, no device read) -> list of ints."""
+    from . import resample
+    return resample.out_lengths(lengths, rates, target)
+
+
+def resample_bank(fi, fo=16000):
+    """The (L, K) float32 bank of the pair of rates as a numpy array (float64 arithmetic, rounded once)."""
+    from . import resample
+    return resample.bank(fi, fo)
+
+
 def gru_pool_fused_ok(H, D, T, p, mask, method, factor):
     """Can the recurrence apply the layer's Dropout + Downsample in its epilogue (slu_gru_seq_fwd_pool_bf16)?  Average
     pooling over two frames with an in-kernel Philox mask (or no dropout): every layer of the reference cfgs.  Injected

@@ -25,6 +25,7 @@ from tqdm import tqdm
 
 from data import SLUDataset, ASRDataset, mask_padding_enabled as data_mask_padding_enabled
 from data import asr_ctc_enabled, mask_asr_enabled
+from data import SourceWaves, resample_enabled as data_resample_enabled
 from models import PretrainedModel, Model, next_rng_step, mask_augment_enabled as models_mask_augment_enabled
 from models import dropout_masks_injected, rng_step_held
 from slu_hip import dp, ops, pipeline
@@ -208,6 +209,31 @@ class _drop_lengths:
 
     def __len__(self):
         return len(self.loader)           # TypeError for a generator, as on the loader itself
+
+
+class _resample_batches:
+    """SLU batches under SLU_RESAMPLE=1: the loader's first element is a data.SourceWaves (the files' own samples and
+    rates, on the host); this wrapper copies it to the device and converts it to the model's rate there, on the stream
+    that is current where the loop iterates — the training stream — as one launch (ops.wave_resample), and yields the
+    ordinary batch tuple: (x at config.fs, y), or (x, y, lengths) under SLU_MASK_PADDING=1, whose lengths the collate
+    function already gave in converted samples.  Everything downstream is untouched.  Keeps the loader's len()."""
+
+    def __init__(self, loader, device):
+        self.loader = loader
+        self.device = device
+
+    def __iter__(self):
+        for batch in self.loader:
+            sw = batch[0]
+            if not isinstance(sw, SourceWaves):        # a synthetic dataset: generated at the model's rate, nothing to convert
+                yield batch
+                continue
+            x = sw.x.to(self.device, non_blocking=True)
+            y, _ = ops.wave_resample(x, sw.rates, sw.lengths.tolist(), sw.target, sw.out_T)
+            yield (y,) + tuple(batch[1:])
+
+    def __len__(self):
+        return len(self.loader)
 
 
 def _input_version(batch):
@@ -800,6 +826,21 @@ class Trainer:
         finally:
             outer.wait_stream(main)
 
+    def _resampled(self, loader, train, asr):
+        """SLU_RESAMPLE=1: the SLU loader behind _resample_batches, so that every loop sees device-resident waveforms at the
+        model's rate (a loader already wrapped passes through).  The look-ahead pipeline reads its batches ahead of the
+        training stream, on streams of its own, and builds its super-batches from host rows: it is refused here, before
+        the first step; nothing is copied back to the host."""
+        if asr or not data_resample_enabled():
+            return loader
+        if not self._on_gpu():
+            raise ValueError("resample: SLU_RESAMPLE=1 converts on the device; the model is on the CPU")
+        if train and not mask_train_enabled() and self.lookahead_depth(train, asr)[0] != 0:
+            raise ValueError("resample: SLU_RESAMPLE=1 does not run under the look-ahead pipeline (its super-batches are "
+                             "read ahead of the training stream); set SLU_LOOKAHEAD=0, or train on the lengths "
+                             "(SLU_MASK_PADDING=1 SLU_MASK_TRAIN=1)")
+        return _resample_batches(loader, next(self.model.parameters()).device)
+
     def _iterate(self, loader, train, asr, accumulate=False):
         """Yields ([metric tensors], batch_size) per batch, doing the optimisation step when `train`.
         NOTE for consumers: the metrics of a hipGraph-captured step are ONE static device buffer that the next replay
@@ -819,6 +860,7 @@ class Trainer:
                 yield from self._iterate_eager(loader, train, asr, sums)
                 return
             loader = _drop_lengths(loader, 3)    # SLU_MASK_ASR=1 alone: training drops the lengths, evaluation uses them
+        loader = self._resampled(loader, train, asr)
         if train and not asr:
             if mask_train_enabled():
                 # masked steps are eager: no look-ahead super-batches, no captured steps (a step's lengths table and the
@@ -864,6 +906,7 @@ class Trainer:
         # the batch_size-weighted sums of the metrics (reference training.py:100-104) stay on the device:
         # self.epoch_sums, filled by the step loop itself (inside the captured step's kernels where it can)
         seq2seq = not asr and getattr(self.model, "seq2seq", False)
+        it = self._resampled(it, train, asr)     # SLU_RESAMPLE=1: in front of the tee below, which decodes what it read
         batches_read = collections.deque()
         if seq2seq:                      # the decoded strings need the batch the step consumed
             # the step loop reads AHEAD of the step it yields (look-ahead super-batches, grouped evaluation) but
@@ -993,7 +1036,7 @@ class Trainer:
         table = model.intent_set.table(dev)
         sums = torch.zeros(6, dtype=torch.float64, device=dev)     # n, free right, best right, outside, posterior right / wrong
         with torch.no_grad():
-            for batch in dataset.loader:
+            for batch in self._resampled(dataset.loader, False, False):
                 x, y = batch[0], batch[1].to(dev)
                 res = model.intent_set_scores(x, batch[2] if len(batch) == 3 else None, n=1)
                 right = (table[res.best.long()].long() == y).all(dim=1)
