@@ -1,6 +1,6 @@
 #!/bin/bash
 # Builds libslu_hip.so and, next to it, libslu_decode.so (include/slu_decode.h), libslu_intents.so
-# (include/slu_intents.h) and libslu_resample.so (include/slu_resample.h) for gfx950 (MI355X) in-tree.  hipcc cross-compiles without a GPU.
+# (include/slu_intents.h), libslu_resample.so (include/slu_resample.h) and libslu_room.so (include/slu_room.h) for gfx950 (MI355X) in-tree.  hipcc cross-compiles without a GPU.
 # Out-of-date translation units are compiled in parallel (SLU_BUILD_JOBS, default = the host's cores, max 16).
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
@@ -16,12 +16,15 @@ DECODE_UNITS="slu_ctc_beam"
 INTENTS_UNITS="slu_intent_set"
 # libslu_resample.so: its units see include/slu_resample.h as well
 RESAMPLE_UNITS="slu_resample"
+# libslu_room.so: its units see include/slu_room.h as well
+ROOM_UNITS="slu_room"
 OBJS=()
 DECODE_OBJS=()
 INTENTS_OBJS=()
 RESAMPLE_OBJS=()
+ROOM_OBJS=()
 STALE=()
-for f in $UNITS $DECODE_UNITS $INTENTS_UNITS $RESAMPLE_UNITS; do
+for f in $UNITS $DECODE_UNITS $INTENTS_UNITS $RESAMPLE_UNITS $ROOM_UNITS; do
   if [ ! -f "$OUT/$f.o" ] || [ "$HERE/$f.hip" -nt "$OUT/$f.o" ] || [ "$HERE/slu_common.h" -nt "$OUT/$f.o" ] || [ "$HERE/slu_bf16.h" -nt "$OUT/$f.o" ] || [ "$HERE/slu_philox.h" -nt "$OUT/$f.o" ] || [ "$HERE/slu_gemm_tile.h" -nt "$OUT/$f.o" ] || [ "$HERE/slu_reduce.h" -nt "$OUT/$f.o" ] \
      || [ "$HERE/../../include/slu_hip.h" -nt "$OUT/$f.o" ]; then
     STALE+=("$f")
@@ -31,10 +34,13 @@ for f in $UNITS $DECODE_UNITS $INTENTS_UNITS $RESAMPLE_UNITS; do
     STALE+=("$f")
   elif [[ " $RESAMPLE_UNITS " == *" $f "* ]] && [ "$HERE/../../include/slu_resample.h" -nt "$OUT/$f.o" ]; then
     STALE+=("$f")
+  elif [[ " $ROOM_UNITS " == *" $f "* ]] && [ "$HERE/../../include/slu_room.h" -nt "$OUT/$f.o" ]; then
+    STALE+=("$f")
   fi
   if [[ " $DECODE_UNITS " == *" $f "* ]]; then DECODE_OBJS+=("$OUT/$f.o")
   elif [[ " $INTENTS_UNITS " == *" $f "* ]]; then INTENTS_OBJS+=("$OUT/$f.o")
   elif [[ " $RESAMPLE_UNITS " == *" $f "* ]]; then RESAMPLE_OBJS+=("$OUT/$f.o")
+  elif [[ " $ROOM_UNITS " == *" $f "* ]]; then ROOM_OBJS+=("$OUT/$f.o")
   else OBJS+=("$OUT/$f.o"); fi
 done
 if [ "${#STALE[@]}" -gt 0 ]; then
@@ -52,3 +58,6 @@ echo "[build] $OUT/libslu_intents.so"
 # the sample-rate converter: the same one undefined project symbol, the same link
 "$HIPCC" --offload-arch=gfx950 -shared -fPIC "${RESAMPLE_OBJS[@]}" -L"$OUT" -lslu_hip -Wl,-rpath,'$ORIGIN' -o "$OUT/libslu_resample.so"
 echo "[build] $OUT/libslu_resample.so"
+# reverberation and noise banks: the same one undefined project symbol, the same link
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC "${ROOM_OBJS[@]}" -L"$OUT" -lslu_hip -Wl,-rpath,'$ORIGIN' -o "$OUT/libslu_room.so"
+echo "[build] $OUT/libslu_room.so"

@@ -121,7 +121,10 @@ def run(args):
 
     if args.train:
         train_dataset, valid_dataset, test_dataset = get_SLU_datasets(config)
-        model = Model(config=config)
+        model = Model(config=config)                     # SLU_AUGMENT_ROOM: reads SLU_RIR_PATH / SLU_NOISE_PATH into its banks
+        if getattr(model, "_room", None) is not None:
+            say("room augmentation (p = %g): %s" % (model._room.p, ", ".join(
+                "%s from %d entries" % (name, len(model._room.banks[name])) for name in model._room.names)))
         if beam_lexicon_enabled() and config.seq2seq:    # SLU_BEAM_LEXICON=1: decode only the training split's semantics
             model.set_lexicon(intent_lexicon(train_dataset))
         if args.intent_set:                              # --intent_set: the training split's slot tuples are the closed set

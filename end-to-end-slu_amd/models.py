@@ -37,6 +37,7 @@ from slu_hip import knobs as _knobs
 from slu_hip import lexicon as _lexicon
 from slu_hip import decode as _decode
 from slu_hip import intents as _intents
+from slu_hip import room as _room
 
 
 # ------------------------------------------------------------------------------------------------
@@ -153,16 +154,46 @@ def _site(module, idx):
 AUGMENT_KEY = 0xA0761D6478BD642F
 
 
-def _augment(x, training_augment):
+# Reverberation and the noise bank (SLU_AUGMENT_ROOM; ops.wave_reverb / wave_mix_noise) draw on the same layout under a
+# third key, so neither the dropout masks nor the draws of tempo, gain, crop and white noise move when the knob is set.
+ROOM_KEY = 0xE7037ED1A0B428DB
+
+
+class _Room:
+    """What a model with augment=True needs for SLU_AUGMENT_ROOM: the named effects in the order they run, the probability
+    of each and the banks.  Not a module: the banks are not parameters, not buffers and not part of state_dict."""
+
+    def __init__(self, names, p, banks):
+        self.names, self.p, self.banks = tuple(names), float(p), dict(banks)
+
+    def apply(self, x, lengths):
+        """x (B, T) fp32 / PCM16 on the device -> reverberant speech plus noise (fp32) for the current dropout step;
+        lengths: None (the dense rule) or the int32 device table, which the effects leave as it is."""
+        stream = _rng_stream(0, ROOM_KEY)
+        for name in self.names:
+            if name == "reverb":
+                x = _ops.wave_reverb(x, self.banks[name], lengths, *stream, p=self.p)
+            else:
+                if torch.is_tensor(x) and x.dtype == torch.int16:
+                    x = _ops.pcm16_to_f32(x)
+                x = _ops.wave_mix_noise(x, self.banks[name], lengths, *stream, p=self.p)
+        return x
+
+
+def _augment(x, training_augment, room=None):
     """x (B, T) waveform batch (fp32 / PCM16 tensor or ops.RowTable) -> its augmentation for the current dropout step
     (dense fp32), when `training_augment`; else x itself.  The tempo perturbation (SLU_AUGMENT_TEMPO=1) runs first, on the
-    same stream: its factor comes from a Philox block of its own, so the other effects' draws do not move."""
+    same stream: its factor comes from a Philox block of its own, so the other effects' draws do not move.  room (a _Room:
+    SLU_AUGMENT_ROOM): reverberation and the noise bank run behind the tempo perturbation and in front of gain, crop and
+    white noise — reverberant speech plus noise, then level and framing."""
     if not training_augment:
         return x
     flags, stream = _ops.augment_flags(), _rng_stream(0, AUGMENT_KEY)
     with torch.no_grad():
         if _ops.tempo_enabled():                  # SLU_AUGMENT_TEMPO=1: the reference's order tempo -> gain -> crop -> noise
             x = _ops.wave_tempo(x, *stream)
+        if room is not None:
+            x = room.apply(x, None)
         return _ops.wave_augment(x, flags, *stream)
 
 
@@ -1251,7 +1282,7 @@ def _check_len_stages(stages):
                                 ", ".join(map(str, _ops.LEN_HIDDEN_SIZES))))
 
 
-def _enter_len(pm, x, lengths, stages, train_ok=False, rng_step=None, augment=False, labels=()):
+def _enter_len(pm, x, lengths, stages, train_ok=False, rng_step=None, augment=False, labels=(), room=None):
     """The one way into a lengths=... call of `pm` (a PretrainedModel) that runs `stages`: every host-side refusal, then —
     the first launches — the waveform preamble.  -> (x on the device, fp32, exactly zero from every row's end on; the rows'
     sample counts on the host).
@@ -1261,7 +1292,8 @@ def _enter_len(pm, x, lengths, stages, train_ok=False, rng_step=None, augment=Fa
     labels) — each y (or None) must have the dense call's (B, T') int64 shape.  augment: the waveforms pass through
     _augment's effects on the length-taking kernels (SLU_MASK_AUGMENT=1) instead of the tail mask: same stream, order and
     knobs, a PCM16 batch taken as it is; the new sample counts come from the host mirrors (ops.tempo_out_lengths /
-    augment_out_lengths, no device read)."""
+    augment_out_lengths, no device read).  room (a _Room: SLU_AUGMENT_ROOM): reverberation and the noise bank between the
+    two, on the table of lengths, which they leave as it is: no host mirror."""
     if train_ok and torch.is_tensor(rng_step):
         raise ValueError("lengths: captured steps (a device-resident rng_step) are not supported")
     if x.dim() != 2:
@@ -1294,6 +1326,8 @@ def _enter_len(pm, x, lengths, stages, train_ok=False, rng_step=None, augment=Fa
         if _ops.tempo_enabled():
             x, n_dev = _ops.wave_tempo_len(x, n_dev, *stream)
             host = _ops.tempo_out_lengths(host, T, *mirror)
+        if room is not None:
+            x = room.apply(x, n_dev)
         x, _ = _ops.wave_augment_len(x, n_dev, flags, *stream)
         return x, _ops.augment_out_lengths(host, T, flags, *mirror)
 
@@ -2214,6 +2248,14 @@ class Model(torch.nn.Module):
         if self.augment:
             _ops.augment_flags()                  # an unknown component name fails here, not at the first step
             _ops.tempo_enabled()                  # likewise a bad SLU_AUGMENT_TEMPO
+        # SLU_AUGMENT_ROOM: reverberation and / or a noise bank in front of them (set_rir_bank / set_noise_bank replace the
+        # banks read here); a name that is not an effect, a bad probability or noise without a bank fails here
+        self._room = None
+        self._room_seed = int(getattr(config, "seed", 0) or 0)
+        names = _room.effects() if self.augment else ()
+        if names:
+            banks = _room.banks_from_knobs(names, self.fs, "cuda" if self.is_cuda else "cpu", seed=self._room_seed)
+            self._room = _Room(names, _room.probability(), banks)
         self.seq2seq = config.seq2seq
         self.lexicon = None                       # set_lexicon: not a parameter, not a buffer, not in state_dict
         self.intent_set = None                    # set_intent_set: likewise
@@ -2338,7 +2380,7 @@ class Model(torch.nn.Module):
         sub_batch > 0: x is the concatenation of several upcoming batches of that size belonging to
         consecutive steps rng_step, rng_step+1, ...; each draws its own step's dropout masks."""
         with torch.no_grad(), _rng_step(rng_step, sub_batch):
-            x = _augment(self.pretrained_model._to_device(x)[0], self.augment and self.training)
+            x = _augment(self.pretrained_model._to_device(x)[0], self.augment and self.training, self._room)
             return self.pretrained_model.run_stages(x, 0, n_stages)
 
     def forward_from(self, h, n_stages, y_intent, rng_step):
@@ -2346,7 +2388,7 @@ class Model(torch.nn.Module):
         pm = self.pretrained_model
         with _rng_step(rng_step):                  # a tensor under hipGraph capture: step*16 lives on the device
             if n_stages == 0:
-                h = _augment(h, self.augment and self.training)
+                h = _augment(h, self.augment and self.training, self._room)
             h = pm.run_stages(h, n_stages, len(pm._stages()))
             drop = None
             for st in self._intent_stages:
@@ -2403,7 +2445,8 @@ class Model(torch.nn.Module):
             _refuse_seq2seq_lengths()
         pm = self.pretrained_model
         stages = pm._stages() + list(self._intent_stages)
-        x, host = _enter_len(pm, x, lengths, stages, train_ok=True, rng_step=rng_step, augment=self.augment and self.training)
+        x, host = _enter_len(pm, x, lengths, stages, train_ok=True, rng_step=rng_step, augment=self.augment and self.training,
+                             room=self._room)
         run = _run_stages_len(stages, x, host, training=self.training)
         h, n_dev = run.out, run.n_dev
         if self.seq2seq:
@@ -2509,6 +2552,30 @@ class Model(torch.nn.Module):
         else:
             _, logits, pred, _ = _ops.cls_maxpool_len_fwd(h, cls.weight.detach(), cls.bias.detach(), n_dev, None, slots)
         return logits, pred
+
+    # -- the banks of SLU_AUGMENT_ROOM (slu_hip/room.py) -----------------------
+    def _set_room_bank(self, name, kind, bank):
+        names = _room.effects() if self.augment else ()
+        if name not in names:
+            raise ValueError("room: the model does not apply %s (augment=%s, SLU_AUGMENT_ROOM=%r): a bank would never be used"
+                             % (name, self.augment, ",".join(names)))
+        if bank is None:
+            if name == "noise":
+                raise ValueError("room: SLU_AUGMENT_ROOM names noise: the model cannot be left without a noise bank")
+            bank = _room.synthetic_rirs(64, self.fs, seed=self._room_seed)
+        self._room.banks[name] = _room.as_bank(kind, bank)
+
+    def set_rir_bank(self, bank):
+        """The impulse responses `reverb` of SLU_AUGMENT_ROOM draws from: a slu_hip.room.RirBank, a list of 1-D float arrays
+        (finite, 1 to 8192 taps each), or None for the synthetic default (room.synthetic_rirs(64, fs, seed=config.seed)).
+        Not part of state_dict.  ValueError when the model does not apply the effect."""
+        self._set_room_bank("reverb", _room.RirBank, bank)
+
+    def set_noise_bank(self, bank):
+        """The recordings `noise` of SLU_AUGMENT_ROOM draws from, at the model's sampling rate: a slu_hip.room.NoiseBank or
+        a list of 1-D float arrays.  Not part of state_dict.  ValueError for None, or when the model does not apply the
+        effect."""
+        self._set_room_bank("noise", _room.NoiseBank, bank)
 
     # -- closed-set decoding of the fixed-slot head (slu_hip/intents.py; DESIGN.md section 7) ------
     def set_intent_set(self, tuples):

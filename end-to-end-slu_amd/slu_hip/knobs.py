@@ -99,7 +99,16 @@ RANKS_AGREE = tuple(name for name, k in KNOBS.items() if k.agree)
 ADDED = {
     # data (data.py, training.py)
     "SLU_RESAMPLE": Knob("flag", "0", doc=False),
+    # reverberation and noise banks under augment=True (slu_hip/room.py, models.py; tests/test_room_cpu.py)
+    "SLU_AUGMENT_ROOM": Knob("text", "", doc=False, agree=True),
+    "SLU_AUGMENT_ROOM_P": Knob("text", "0.5", doc=False),
+    "SLU_RIR_PATH": Knob("text", "", doc=False),
+    "SLU_NOISE_PATH": Knob("text", "", doc=False),
 }
+
+# knobs of ADDED the data-parallel ranks must agree on: ops.wgrad_signature appends NAME=value for each that is set to
+# something else than its default, so the string without them is the one tests/test_knobs_cpu.py records
+ADDED_RANKS_AGREE = tuple(name for name, k in ADDED.items() if k.agree)
 
 
 def _declared(name):

@@ -868,6 +868,29 @@ def resample_bank(fi, fo=16000):
     return resample.bank(fi, fo)
 
 
+# ---- reverberation and noise banks between tempo and slu_wave_augment (libslu_room.so; slu_hip/room.py holds the definition) ----
+def wave_reverb(x, bank, lengths=None, seed=0, offset=0, offset_dev=None, sub_batch=0, p=0.5, fixed_idx=None, want_params=False):
+    """Rows of x (B, T), fp32 or PCM16 on the device, each convolved with one impulse response of `bank` (a room.RirBank or
+    its arrays), "same" length (slu_wave_reverb, include/slu_room.h): the response is drawn per row with probability p on
+    the row's Philox stream (stream arguments as wave_augment), or fixed_idx[b] (-1 = none).  lengths: None (the dense rule)
+    or an int32 device tensor; they do not change.  -> y (B, T) fp32 [, params (B, 4) = applied, idx, K, len].  A RowTable is
+    refused (SLU_LOOKAHEAD=0); every refusal is a ValueError("room: ...") before any launch."""
+    from . import room
+    with torch.no_grad():
+        return room.wave_reverb(x, bank, lengths, seed, offset, offset_dev, sub_batch, p, fixed_idx, want_params)
+
+
+def wave_mix_noise(x, bank, lengths=None, seed=0, offset=0, offset_dev=None, sub_batch=0, p=0.5, snr=(0.0, 20.0), fixed=None,
+                   want_params=False):
+    """Rows of x (B, T) fp32 on the device plus a segment of one clip of `bank` (a room.NoiseBank or its arrays) at an SNR
+    over the row's own samples (slu_wave_mix_noise, include/slu_room.h): clip, start and SNR in `snr` dB drawn per row with
+    probability p, or fixed[b] = (clip, start, snr) (clip -1 = none).  Arguments and refusals as wave_reverb.
+    -> y (B, T) fp32 [, params (B, 8) = applied, clip, start, snr, g, Es, En, len]."""
+    from . import room
+    with torch.no_grad():
+        return room.wave_mix_noise(x, bank, lengths, seed, offset, offset_dev, sub_batch, p, snr, fixed, want_params)
+
+
 def gru_pool_fused_ok(H, D, T, p, mask, method, factor):
     """Can the recurrence apply the layer's Dropout + Downsample in its epilogue (slu_gru_seq_fwd_pool_bf16)?  Average
     pooling over two frames with an in-kernel Philox mask (or no dropout): every layer of the reference cfgs.  Injected
@@ -1121,6 +1144,9 @@ def wgrad_signature():
         if not name.startswith("SLU_WGRAD_"):               # those two as resolved above, not as written
             v = _knobs.raw(name)
             parts.append("off" if v is None else v)
+    for name in _knobs.ADDED_RANKS_AGREE:                   # later knobs: named, and only when set away from the default
+        if _knobs.raw(name) != _knobs.ADDED[name].default:
+            parts.append("%s=%s" % (name, _knobs.raw(name)))
     return "/".join(parts)
 
 

@@ -841,6 +841,16 @@ class Trainer:
                              "(SLU_MASK_PADDING=1 SLU_MASK_TRAIN=1)")
         return _resample_batches(loader, next(self.model.parameters()).device)
 
+    def _refuse_room_lookahead(self, train, asr):
+        """SLU_AUGMENT_ROOM: ops.wave_reverb / wave_mix_noise read a dense batch; the look-ahead pipeline's super-batches are
+        row tables.  A model that applies the effects is refused here, before the first step."""
+        if not train or asr or getattr(self.model, "_room", None) is None or mask_train_enabled():
+            return
+        if self.lookahead_depth(train, asr)[0] != 0:
+            raise ValueError("room: SLU_AUGMENT_ROOM does not run under the look-ahead pipeline (its super-batches are row "
+                             "tables); set SLU_LOOKAHEAD=0, or train on the lengths (SLU_MASK_PADDING=1 SLU_MASK_TRAIN=1 "
+                             "SLU_MASK_AUGMENT=1)")
+
     def _iterate(self, loader, train, asr, accumulate=False):
         """Yields ([metric tensors], batch_size) per batch, doing the optimisation step when `train`.
         NOTE for consumers: the metrics of a hipGraph-captured step are ONE static device buffer that the next replay
@@ -861,6 +871,7 @@ class Trainer:
                 return
             loader = _drop_lengths(loader, 3)    # SLU_MASK_ASR=1 alone: training drops the lengths, evaluation uses them
         loader = self._resampled(loader, train, asr)
+        self._refuse_room_lookahead(train, asr)
         if train and not asr:
             if mask_train_enabled():
                 # masked steps are eager: no look-ahead super-batches, no captured steps (a step's lengths table and the
